@@ -13,7 +13,23 @@ all-gather of the poses after the timed steps.
                  --batch problems (at N = 1 both splits are the same 1024 problems)
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--split weak|strong]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: it generates and uploads the batch,
+runs W warm-up steps, times K steps, writes the last step's poses when --dump-outputs is given and
+prints one JSON line (metric, value, unit, ms_per_step, ...).  --full adds every other measurement
+to that line: the other split and the 8-GPU share, the fed-from-host and unpipelined legs, the
+host-upload rate, the per-kernel times and rooflines (a profiling pass of its own), the CPU oracle
+baseline and parity, the config-2/3 streaming and latency legs and the config-5 dense batch; each
+of them keeps its own switch (--cpu-sample 0, --stream-sweeps 0, ...), which only matters with
+--full.
+
+--dump-outputs DIR writes what the timed path hands its caller after the last timed step
+(loam_batch_download): DIR/odometry.npy and DIR/mapping.npy, one 6-DoF pose per problem in global
+problem order (float64 at N = 1; the float32 all-gathered poses with more ranks).  The inputs are
+seeded (BASE_SEED + global index), so two builds run with the same arguments can be compared pose
+for pose.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches the N ranks itself
 (torch.distributed.run as a child process; the parent touches no GPU).  Ranks use RCCL ("nccl")
@@ -574,6 +590,20 @@ def gather_poses(dist, od, aft, world, dev):
     return allp.cpu().numpy()
 
 
+def dump_outputs(path, od, aft, gathered):
+    """--dump-outputs: the poses the timed path returned after its last timed step, as
+    <path>/odometry.npy and <path>/mapping.npy ([problems, 6], global problem order): this rank's
+    float64 poses at N = 1, the all-gathered float32 ones (gather_poses) with more ranks"""
+    if gathered is not None:
+        od, aft = gathered[:, :6], gathered[:, 6:]
+        dt = np.float32
+    else:
+        dt = np.float64
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "odometry.npy"), np.ascontiguousarray(od, dt))
+    np.save(os.path.join(path, "mapping.npy"), np.ascontiguousarray(aft, dt))
+
+
 def spawn(args_list, n):
     """launch n ranks of this script (torch.distributed.run) as a child; returns its exit code"""
     port = os.environ.get("MASTER_PORT", "29511")
@@ -585,11 +615,16 @@ def spawn(args_list, n):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024, help="problems per GPU (weak split)")
     ap.add_argument("--global-batch", type=int, default=1024, help="problems in total (strong split)")
     ap.add_argument("--split", choices=("weak", "strong"), default="strong", help="which split is `value`")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (other split, fed / unpipelined, per-kernel rooflines, CPU "
+                         "baseline, streaming, latency, dense batch); the switches below choose among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's poses to DIR/odometry.npy and DIR/mapping.npy")
     ap.add_argument("--strong-leg", type=int, default=1, help="also measure the other split (0: skip)")
     ap.add_argument("--cpu-sample", type=int, default=32, help="problems in the CPU baseline sample (0: skip)")
     ap.add_argument("--cpu-reps", type=int, default=5)
@@ -606,7 +641,10 @@ def main(argv=None):
     ap.add_argument("--dense-only", type=int, default=0, help="run only the config-5 batched leg (profiling)")
     argv = sys.argv[1:] if argv is None else argv
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     tune = parse_tune(args.tune)
+    full = args.full
 
     if args.share_only:  # child: the 8-GPU share timed alone in a fresh process, as one rank runs it
         first, B8 = shard(0, 8, args.batch, "strong", args.global_batch)
@@ -646,7 +684,7 @@ def main(argv=None):
         dist = tdist
 
     share8 = None
-    if args.strong_leg and world == 1 and args.global_batch % 8 == 0:
+    if full and args.strong_leg and world == 1 and args.global_batch % 8 == 0:
         # the per-GPU share of config 4 on 8 GPUs (1024 / 8), measured on one GPU in a child process
         # started before this one touches the GPU: a fresh process, as each of the 8 ranks is (timed
         # in this process after the batch-1024 leg it measured ~10 % slower)
@@ -675,11 +713,11 @@ def main(argv=None):
     other = None
     same = shard(rank, world, args.batch, "weak", args.global_batch) == \
         shard(rank, world, args.batch, "strong", args.global_batch)
-    if args.strong_leg and same:  # the other split is this very workload (N = 1, batch = global batch)
+    if full and args.strong_leg and same:  # the other split is this very workload (N = 1, batch = global batch)
         other = {"split": "strong" if args.split == "weak" else "weak", "global_batch": world * main_leg["B"],
                  "problems_per_gpu": main_leg["B"], "value": world * main_leg["B"] * args.steps / main_leg["elapsed"],
                  "ms_per_step": main_leg["elapsed"] / args.steps * 1e3, "note": "same workload as value"}
-    elif args.strong_leg:
+    elif full and args.strong_leg:
         other_split = "strong" if args.split == "weak" else "weak"
         o = leg(other_split)
         o["eng"].close()
@@ -692,20 +730,22 @@ def main(argv=None):
     od, aft = main_leg["od"], main_leg["aft"]
 
     fed = None
-    if args.fed_leg and world == 1 and not os.environ.get("LOAM_BENCH_ENGINE"):
+    if full and args.fed_leg and world == 1 and not os.environ.get("LOAM_BENCH_ENGINE"):
         fed = fed_leg(Engine, sg, main_leg["prevs"], main_leg["curs"], args.steps, args.warmup, local)
 
     # host-buffer rate: the same batch handed over from host memory, upload + one step
-    a = time.perf_counter()
-    eng.batch_upload(main_leg["prevs"], main_leg["curs"])
-    eng.sync()
-    upload_s = time.perf_counter() - a
+    upload_s = None
+    if full:
+        a = time.perf_counter()
+        eng.batch_upload(main_leg["prevs"], main_leg["curs"])
+        eng.sync()
+        upload_s = time.perf_counter() - a
 
     # per-kernel device times of the same workload (HIP events on the engine stream), untimed
     # (the profiling pass also runs the search kernels' counting variants: their work counters, which
     # kernel_bytes needs, come from this pass, st_prof)
     ktimes, st_prof = {}, st
-    if args.profile_steps > 0:
+    if full and args.profile_steps > 0:
         eng.set_profiling(True)
         for _ in range(args.profile_steps):
             eng.batch_run()
@@ -722,22 +762,27 @@ def main(argv=None):
             dist.destroy_process_group()
         return
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, od, aft, gathered)
+
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
     psteps = max(args.profile_steps, 1)
 
-    st["od_moments"] = st_prof["od_moments"] = uses_moments(eng, B)
-    roof, roof_all, pipeline, stage_ms = rooflines(st, st_prof, ktimes, psteps, ms_per_step)
+    roof = roof_all = pipeline = stage_ms = None
+    if full:
+        st["od_moments"] = st_prof["od_moments"] = uses_moments(eng, B)
+        roof, roof_all, pipeline, stage_ms = rooflines(st, st_prof, ktimes, psteps, ms_per_step)
 
     # CPU baseline: the oracle on a bounded sample, N=1 only
     cpu = parity = None
-    if world == 1 and args.cpu_sample > 0 and not os.environ.get("LOAM_BENCH_ENGINE"):
+    if full and world == 1 and args.cpu_sample > 0 and not os.environ.get("LOAM_BENCH_ENGINE"):
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle_ctypes as oc
         cpu, parity = cpu_leg(oc, main_leg["prevs"], main_leg["curs"], od, aft, args.cpu_sample, args.cpu_reps)
 
     stream = latency = None
-    if world == 1 and not os.environ.get("LOAM_BENCH_ENGINE"):
+    if full and world == 1 and not os.environ.get("LOAM_BENCH_ENGINE"):
         loam = importlib.import_module("loam_velodyne-1_amd")
         if args.stream_sweeps > 0:
             stream = stream_leg(loam, sg, args.stream_sweeps, args.stream_cpu_sweeps, tune=tune)
@@ -771,7 +816,7 @@ def main(argv=None):
             dense["points_per_sweep"] = int(len(prob[1]))
             latency["config5"] = with_cpu(dense, *prob, ocfg=lambda oc: oc.default_config(ring_model=1, **dense_cfg))
     dense = None
-    if world == 1 and args.dense_batch > 0 and not os.environ.get("LOAM_BENCH_ENGINE"):
+    if full and world == 1 and args.dense_batch > 0 and not os.environ.get("LOAM_BENCH_ENGINE"):
         loam = importlib.import_module("loam_velodyne-1_amd")
         dense = dense_batch_leg(loam, sg, args.dense_batch, args.dense_steps, 2, min(args.profile_steps, 2),
                                 args.dense_cpu_sample if args.cpu_sample > 0 else 0, 3, device=local, tune=tune)
@@ -799,31 +844,36 @@ def main(argv=None):
                                     "the resident batch — arriving_batches gives fresh batches fed from "
                                     "the host each step and the pipeline-off rate"),
                    **({"tuning": tune} if tune else {})},
-        "roofline": roof,
-        "roofline_kernels": roof_all,
-        "pipeline": pipeline,
-        "cpu_baseline": cpu,
-        "parity": parity,
-        "strong" if args.split == "weak" else "weak": other,
-        "kernel_ms_per_step": stage_ms,
-        "arriving_batches": fed,
-        "single_stream": stream,
-        "latency": latency,
-        "dense_batch": dense,
         "gathered": {"problems": int(gathered.shape[0]),
                      "sha1": hashlib.sha1(np.ascontiguousarray(gathered, np.float32).tobytes()).hexdigest()}
         if gathered is not None else None,
-        "host_upload": {"ms": upload_s * 1e3, "pcie_inclusive_value": B / (upload_s + ms_per_step * 1e-3),
-                        "note": "rank 0; pageable host sweeps packed and copied per sweep; not the metric"},
         "workload_stats": {"od_iters_mean": st["od_iters"] / B, "mp_iters_mean": st["mp_iters"] / B,
                            "mp_stack_mean": st["mp_stack"] / B, "mp_map_points_mean": st["mp_map_points"] / B,
                            "od_queries_mean": st["od_queries"] / B,
-                           "mp_fit_fraction": st["mp_fits"] / max(st["mp_stack_iters"], 1),
-                           "mp_nn_candidates_per_query": st_prof["mp_nn_candidates"] / max(st["mp_stack_iters"], 1),
-                           "mp_nn_cells_per_query": st_prof["mp_nn_cells"] / max(st["mp_stack_iters"], 1),
-                           "od_assoc_points_per_query": st_prof["od_assoc_gathered"] / max(st["od_queries"], 1),
-                           "od_assoc_boxes_per_query": st_prof["od_assoc_boxes"] / max(st["od_queries"], 1)},
+                           "mp_fit_fraction": st["mp_fits"] / max(st["mp_stack_iters"], 1)},
     }
+    if full:  # the secondary legs (each None when its own switch skipped it)
+        out.update({
+            "roofline": roof,
+            "roofline_kernels": roof_all,
+            "pipeline": pipeline,
+            "cpu_baseline": cpu,
+            "parity": parity,
+            "strong" if args.split == "weak" else "weak": other,
+            "kernel_ms_per_step": stage_ms,
+            "arriving_batches": fed,
+            "single_stream": stream,
+            "latency": latency,
+            "dense_batch": dense,
+            "host_upload": {"ms": upload_s * 1e3, "pcie_inclusive_value": B / (upload_s + ms_per_step * 1e-3),
+                            "note": "rank 0; pageable host sweeps packed and copied per sweep; not the metric"},
+        })
+        # the search kernels' work counters come from the profiling pass (st_prof)
+        out["workload_stats"].update({
+            "mp_nn_candidates_per_query": st_prof["mp_nn_candidates"] / max(st["mp_stack_iters"], 1),
+            "mp_nn_cells_per_query": st_prof["mp_nn_cells"] / max(st["mp_stack_iters"], 1),
+            "od_assoc_points_per_query": st_prof["od_assoc_gathered"] / max(st["od_queries"], 1),
+            "od_assoc_boxes_per_query": st_prof["od_assoc_boxes"] / max(st["od_queries"], 1)})
     print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()

@@ -82,7 +82,7 @@ def test_bench_spawns_two_ranks_gloo(sg, split):
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     out = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "3", "--global-batch", "4",
-                      "--split", split, "--profile-steps", "1"], {})
+                      "--split", split, "--profile-steps", "1", "--full"], {})
     assert out["n_gpus"] == 2
     assert out["scaling"] == split
     per, other_per = (3, 2) if split == "weak" else (2, 3)
@@ -101,7 +101,37 @@ def test_bench_single_gpu_share_child(sg):
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     out = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "16", "--global-batch", "16", "--cpu-sample", "0",
-                      "--stream-sweeps", "0", "--latency-runs", "0", "--profile-steps", "1"], {})
+                      "--stream-sweeps", "0", "--latency-runs", "0", "--profile-steps", "1", "--full"], {})
     assert out["n_gpus"] == 1 and out["config"]["global_batch"] == 16
     share = out["weak"]["one_gpu_at_8gpu_share"]
     assert share["problems"] == 2 and share["value"] > 0 and share["ms_per_step"] > 0
+
+
+# what only a --full run measures: absent from a plain run's line
+FULL_ONLY = ("roofline", "roofline_kernels", "pipeline", "cpu_baseline", "parity", "weak", "kernel_ms_per_step",
+             "arriving_batches", "single_stream", "latency", "dense_batch", "host_upload")
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_dumps_outputs(sg, tmp_path, gpus):
+    """A plain run (no --full) times the steps and reports the headline figure alone; with
+    --dump-outputs it writes the poses of the last step, one row per problem in global order
+    (the stand-in engine's poses are a function of each problem's sweeps, so they are known)."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bench_stub
+    d = tmp_path / "out"
+    out = _run_bench(["--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--batch", "4", "--global-batch", "4",
+                      "--dump-outputs", str(d)], {})
+    assert out["n_gpus"] == gpus and out["steps"] == 3 and out["warmup"] == 1
+    assert out["unit"] == "scans/s" and out["higher_is_better"] is True and out["dtype"].startswith("fp32")
+    assert out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(4 / (out["ms_per_step"] * 1e-3), rel=1e-9)
+    assert not [k for k in FULL_ONLY if k in out]
+    assert sorted(p.name for p in d.iterdir()) == ["mapping.npy", "odometry.npy"]
+    prevs, curs = sg.batch_problems(4, base_seed=1000)
+    want = [bench_stub.poses_of(p, c) for p, c in zip(prevs, curs)]
+    for name, k in (("odometry.npy", 0), ("mapping.npy", 1)):
+        got = np.load(d / name)
+        assert got.dtype in (np.float32, np.float64) and got.shape == (4, 6)
+        np.testing.assert_array_equal(got, np.stack([w[k] for w in want]))

@@ -14,7 +14,7 @@ for C in "$@"; do
     for kv in "${KV[@]}"; do T+=("--tune=$kv"); done
   fi
   n=ab_${B}_$(echo "$C" | tr ',=' '_-')
-  timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 3 --cpu-sample 0 --latency-runs 0 \
+  timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup 3 --cpu-sample 0 --latency-runs 0 \
     --batch $B --global-batch $B --strong-leg 0 --stream-sweeps 0 --dense-batch 0 "${T[@]}" \
     > gpurun_out/$n.json 2> gpurun_out/$n.err || exit 1
   python - "$n" <<'EOF'

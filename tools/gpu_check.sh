@@ -18,7 +18,7 @@ if [ -n "$AB" ]; then
   cat $O/ab.txt
 fi
 if [ "${BENCH:-0}" = 1 ]; then
-  timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   python - $O/bench.json <<'EOF'
 import json, sys
 d = json.load(open(sys.argv[1]))

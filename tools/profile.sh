@@ -11,9 +11,9 @@ R=$GRAFT_REPO_ROOT
 TAG=${1:-r06}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
-Q="--cpu-sample 0 --latency-runs 0 --strong-leg 0 --stream-sweeps 0 --dense-batch 0 --fed-leg 0"
+Q="--full --cpu-sample 0 --latency-runs 0 --strong-leg 0 --stream-sweeps 0 --dense-batch 0 --fed-leg 0"
 D="--dense-only 1 --dense-batch 64 --cpu-sample 0"
-cd $R && { [ "${BENCH:-1}" = 0 ] || timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err; } && \
+cd $R && { [ "${BENCH:-1}" = 0 ] || timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err; } && \
 export TMPDIR=/tmp && cd /tmp && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 $R/bench.py --steps 5 --warmup 2 $Q > $O/kt.log 2>&1 && \
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o f -- python3 $R/bench.py --steps 2 --warmup 1 --profile-steps 1 $Q > $O/fetch.log 2>&1 && \
