@@ -211,6 +211,36 @@ int loam_batch_download(loam_ctx *ctx, loam_pose6 *od_sum, loam_pose6 *aft, loam
  * accumulation and TransformToEnd use) */
 int loam_batch_lm_info(loam_ctx *ctx, int32_t *od_iters, int32_t *mp_iters, loam_pose6 *od_transform);
 
+/* ---- the scan-registration clouds of a batch ----
+ * One of the five scanRegistration clouds of every selected sweep, packed back to back in
+ * caller-owned storage.  Problems [first, first + n) select 2n sweeps in the order
+ * sweep j = 2*(i - first) + (0: prev_i, 1: cur_i); sweep j's points are pts[offset[j] .. offset[j+1])
+ * and offset[2n] = count.  Points are the records loam_scan_registration writes: ring-major,
+ * intensity = ring + 0.1*relTime. */
+typedef struct {
+  loam_point *pts;      /* caller-owned, NULL = the points are not wanted (count / offsets still filled) */
+  uint64_t capacity;    /* points pts holds */
+  uint64_t count;       /* points of the selection (written, or required on LOAM_E_CAPACITY) */
+  uint32_t *offset;     /* caller-owned [2*n + 1], NULL = not wanted */
+} loam_batch_cloud;
+typedef struct { loam_batch_cloud full, sharp, less_sharp, flat, less_flat; } loam_batch_clouds;
+
+/* The clouds of the run whose poses loam_batch_download reports (the last loam_batch_run), after
+ * waiting for the context's queued work as loam_batch_download does.  A cloud whose pts and offset
+ * are both NULL is not wanted and its struct is left untouched; for every other cloud count and
+ * (when given) offset are always filled, the points when pts is given.  Passing every pts as NULL
+ * is the sizes-only query.  The pipeline is left as found: a following loam_batch_run behaves as
+ * if this call had not happened.  The points are packed on the device and transferred through a
+ * fixed-size staging (allocated by the first call, released by loam_destroy), chunk by chunk.
+ * Errors: LOAM_E_INVAL for a null argument, no uploaded batch, no loam_batch_run since the last
+ * loam_batch_upload (or since a loam_set_tuning / loam_set_stream_priority, which restart the
+ * pipeline), n == 0, first + n beyond the batch, a wanted cloud of the range exceeding
+ * 2^32 - 1 points (ask for a smaller range), or a max_points too large for the staging; a sweep's
+ * scan-registration error as loam_batch_download reports it; LOAM_E_CAPACITY when a wanted
+ * cloud's points do not fit its capacity: no points are written, every wanted count / offset is
+ * filled, and the call may be repeated with more room. */
+int loam_batch_features(loam_ctx *ctx, uint32_t first, uint32_t n, loam_batch_clouds *out);
+
 /* scheduling (no reference equivalent; the reference's nodes are OS processes): priority of the
  * context's HIP streams.  priority > 0 = the device's highest stream priority, 0 = normal,
  * < 0 = lowest.  Used by a node pipeline to favour its critical node (laserMapping) when several

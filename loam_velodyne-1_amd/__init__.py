@@ -106,10 +106,23 @@ class Stats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BatchCloud(ctypes.Structure):
+    """include/loam/loam.h loam_batch_cloud: one cloud of every selected sweep, packed back to back"""
+    _fields_ = [("pts", ctypes.c_void_p), ("capacity", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                ("offset", ctypes.c_void_p)]
+
+
+BATCH_CLOUDS = ("full", "sharp", "less_sharp", "flat", "less_flat")
+
+
+class BatchClouds(ctypes.Structure):
+    _fields_ = [(n, BatchCloud) for n in BATCH_CLOUDS]
+
+
 EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_error", "loam_imu",
            "loam_scan_registration", "loam_odometry", "loam_mapping", "loam_mapping_surround",
            "loam_maintenance", "loam_chain_sweep",
-           "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_get_stats",
+           "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_get_stats",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -150,6 +163,7 @@ def lib():
         L.loam_get_kernel_times.argtypes = [PP, ctypes.c_char_p, ctypes.c_uint32]
         L.loam_batch_download.argtypes = [PP, P(Pose6), P(Pose6), P(Stats)]
         L.loam_batch_lm_info.argtypes = [PP, P(ctypes.c_int32), P(ctypes.c_int32), P(Pose6)]
+        L.loam_batch_features.argtypes = [PP, ctypes.c_uint32, ctypes.c_uint32, P(BatchClouds)]
         L.loam_get_stats.argtypes = [PP, P(Stats)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
@@ -374,6 +388,29 @@ class Engine:
         P = ctypes.POINTER(ctypes.c_int32)
         _check(lib().loam_batch_lm_info(self.h, od.ctypes.data_as(P), mp.ctypes.data_as(P), tr))
         return od, mp, np.array([p.arr() for p in tr])
+
+    def batch_features(self, first=0, n=None, clouds=BATCH_CLOUDS):
+        """the scan-registration clouds of problems [first, first + n) of the last batch_run
+        (loam_batch_features): {name: (points [N, 4] float32, offsets [2n + 1] uint32)}, sweep
+        j = 2 * (i - first) + (0: prev_i, 1: cur_i) at points[offsets[j]:offsets[j + 1]]"""
+        n = max(getattr(self, "n", 0) - first, 0) if n is None else n
+        for c in clouds:
+            if c not in BATCH_CLOUDS:
+                raise ValueError(f"unknown cloud {c!r}")
+        if n < 0 or first < 0:
+            raise ValueError("first and n must not be negative")
+        bc = BatchClouds()
+        offs = {c: np.zeros(2 * n + 1, np.uint32) for c in clouds}
+        for c in clouds:
+            getattr(bc, c).offset = offs[c].ctypes.data
+        _check(lib().loam_batch_features(self.h, first, n, ctypes.byref(bc)))  # sizes only
+        pts = {c: np.empty((int(getattr(bc, c).count), 4), np.float32) for c in clouds}
+        for c in clouds:
+            b = getattr(bc, c)
+            b.pts, b.capacity = pts[c].ctypes.data, pts[c].shape[0]
+        if clouds:
+            _check(lib().loam_batch_features(self.h, first, n, ctypes.byref(bc)))
+        return {c: (pts[c], offs[c]) for c in clouds}
 
 
 def maintenance(odom_sum, bef, aft):

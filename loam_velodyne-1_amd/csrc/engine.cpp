@@ -197,12 +197,37 @@ struct loam_ctx {
     feed_dev = nullptr;
     feed_doff = nullptr;
   }
+  bool batch_ran = false;  // a loam_batch_run since the last loam_batch_upload (loam_batch_features)
+  // loam_batch_features: the offset table of the selected sweeps (device, and its pinned host copy)
+  // and the bounded staging its packed chunks go through, two device pack buffers and two pinned
+  // host buffers of kPackStagePts points used alternately.  Allocated by the first call for the
+  // uploaded batch size (pack_S sweeps), freed with the batch's other buffers.
+  uint64_t* pack_table = nullptr;
+  uint64_t* pack_table_h = nullptr;
+  float4* pack_dev[2] = {nullptr, nullptr};
+  float4* pack_pin[2] = {nullptr, nullptr};
+  hipEvent_t pack_done[2] = {nullptr, nullptr};
+  int pack_S = 0;
+  void free_pack() {  // (the call that used them has drained its work)
+    if (pack_table) (void)hipFree(pack_table);
+    if (pack_table_h) (void)hipHostFree(pack_table_h);
+    pack_table = pack_table_h = nullptr;
+    for (int i = 0; i < 2; ++i) {
+      if (pack_dev[i]) (void)hipFree(pack_dev[i]);
+      if (pack_pin[i]) (void)hipHostFree(pack_pin[i]);
+      if (pack_done[i]) (void)hipEventDestroy(pack_done[i]);
+      pack_dev[i] = pack_pin[i] = nullptr;
+      pack_done[i] = nullptr;
+    }
+    pack_S = 0;
+  }
   void reset_ahead() {    // (after draining st3 / st4)
     sr_ready = false;
     seed_ready = false;
     for (int i = 0; i < 3; ++i) mp_done_rec[i] = inputs_read_rec[i] = false;
     b_used = false;
     sr_idx = srb_last = pipe_k = 0;
+    batch_ran = false;  // (srb_last no longer names the set of the last run: loam_batch_features waits for the next)
     step_done_rec[0] = step_done_rec[1] = step_done_rec[2] = false;
   }
   OdBuffers odb;
@@ -448,6 +473,7 @@ void loam_destroy(loam_ctx* x) {
   mp_free(x->mpb);
   mp_free(x->mpb2);
   x->free_feed();
+  x->free_pack();
   for (auto& e : x->feed_copied)
     if (e) (void)hipEventDestroy(e);
   if (x->sr_imu_dev) (void)hipFree(x->sr_imu_dev);
@@ -1101,6 +1127,7 @@ int loam_batch_upload(loam_ctx* x, uint32_t n, const loam_cloud_in* prev, const 
     if (x->st2) HIP_TRY(hipStreamSynchronize(x->st2));
     x->drop_graph();  // (its kernels' arguments name the old buffers)
     x->free_feed();   // (sized for the old batch)
+    x->free_pack();
     sr_free(x->srb);
     sr_free(x->srb2);
     sr_free(x->srb3);
@@ -1450,10 +1477,12 @@ int loam_batch_run(loam_ctx* x) {
   }
   if (pipe) {
     HIP_TRY(batch_enqueue_pipe(x));
+    x->batch_ran = true;
     return LOAM_OK;
   }
   if (!x->tune.graph || pf) {
     HIP_TRY(batch_enqueue(x, pf, true));
+    x->batch_ran = true;
     return LOAM_OK;
   }
   // graph replay: captured on the first call for this batch (the kernels' arguments are the
@@ -1477,6 +1506,7 @@ int loam_batch_run(loam_ctx* x) {
   HIP_TRY(hipEventRecord(x->ev[2], x->st));
   HIP_TRY(hipGraphLaunch(x->graph_exec, x->st));
   HIP_TRY(hipEventRecord(x->ev[3], x->st));
+  x->batch_ran = true;
   return LOAM_OK;
 }
 
@@ -1662,6 +1692,192 @@ int loam_batch_download(loam_ctx* x, loam_pose6* od_sum, loam_pose6* aft, loam_s
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ batch feature download
+namespace {
+// points of one staging buffer (32 MiB): a chunk of the packed clouds is at most this large
+constexpr size_t kPackStagePts = (size_t)1 << 21;
+
+// a sweep's clouds at their strides (full and less_flat up to max_points, 12 + 120 + 24 picks per ring)
+size_t pack_sweep_max(const loam_ctx* x) {
+  return (size_t)2 * x->cap + (size_t)(kSharpPerRing + kLessSharpPerRing + kFlatPerRing) * x->R;
+}
+
+int ensure_pack(loam_ctx* x) {
+  const int S = 2 * x->P;
+  if (x->pack_S == S) return LOAM_OK;
+  if (pack_sweep_max(x) > kPackStagePts)
+    return fail(LOAM_E_INVAL, "loam_batch_features: max_points is too large for the download staging (one sweep's "
+                              "clouds must fit " + std::to_string(kPackStagePts) + " points)");
+  x->free_pack();
+  hipError_t he = hipMalloc((void**)&x->pack_table, (size_t)kPackClouds * (S + 1) * sizeof(uint64_t));
+  if (he == hipSuccess)
+    he = hipHostMalloc((void**)&x->pack_table_h, (size_t)kPackClouds * (S + 1) * sizeof(uint64_t), hipHostMallocDefault);
+  for (int i = 0; i < 2; ++i) {
+    if (he == hipSuccess) he = hipMalloc((void**)&x->pack_dev[i], kPackStagePts * sizeof(float4));
+    if (he == hipSuccess) he = hipHostMalloc((void**)&x->pack_pin[i], kPackStagePts * sizeof(float4), hipHostMallocDefault);
+    if (he == hipSuccess) he = hipEventCreateWithFlags(&x->pack_done[i], hipEventDisableTiming);
+  }
+  if (he != hipSuccess) {
+    x->free_pack();
+    return fail(LOAM_E_NOMEM, std::string("feature download staging allocation failed: ") + hipGetErrorString(he));
+  }
+  x->pack_S = S;
+  return LOAM_OK;
+}
+
+// pinned staging -> caller storage, large runs on up to eight threads (as pack_tight)
+void copy_wide(void* dst, const void* src, size_t bytes) {
+  constexpr size_t kMin = (size_t)4 << 20;  // per thread
+  const size_t hw = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+  const size_t nt = std::max<size_t>(1, std::min(hw, bytes / kMin));
+  std::vector<std::thread> th;
+  auto part = [&](size_t t) {
+    const size_t a = bytes * t / nt / 16 * 16, b = t + 1 == nt ? bytes : bytes * (t + 1) / nt / 16 * 16;
+    std::memcpy((char*)dst + a, (const char*)src + a, b - a);
+  };
+  for (size_t t = 1; t < nt; ++t) th.emplace_back(part, t);
+  part(0);
+  for (auto& t : th) t.join();
+}
+}  // namespace
+
+extern "C" int loam_batch_features(loam_ctx* x, uint32_t first, uint32_t n, loam_batch_clouds* out) {
+  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
+  if (x->P == 0) return fail(LOAM_E_INVAL, "no batch uploaded");
+  if (!x->batch_ran) return fail(LOAM_E_INVAL, "loam_batch_features: no loam_batch_run since the last loam_batch_upload");
+  const uint32_t P = (uint32_t)x->P;
+  if (n == 0 || first >= P || n > P - first)
+    return fail(LOAM_E_INVAL, "loam_batch_features: problems [first, first + n) must be a non-empty range of the batch");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipStreamSynchronize(x->st));
+  if (x->st4) HIP_TRY(hipStreamSynchronize(x->st4));
+  if (x->st2) HIP_TRY(hipStreamSynchronize(x->st2));
+  if (x->st3) HIP_TRY(hipStreamSynchronize(x->st3));
+  // the set of the last enqueued step, not the set the next step reads: the work enqueued ahead (or
+  // a feed) has already rewritten that one.  Nothing after k_sr_compact writes a set's clouds (the
+  // odometry and the mapping read them through FeatView's const pointers), so they are as the scan
+  // registration of that step left them.
+  const SrBuffers& sb = x->srbuf(x->srb_last);
+  {
+    std::vector<int> srerr(2 * (size_t)P);
+    HIP_TRY(hipMemcpy(srerr.data(), sb.err, srerr.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int e : srerr) {
+      const int rc = sr_errors(e);
+      if (rc) return rc;
+    }
+  }
+  int rc = ensure_pack(x);
+  if (rc) return rc;
+  loam_batch_cloud* cl[kPackClouds] = {&out->full, &out->sharp, &out->less_sharp, &out->flat, &out->less_flat};
+  const int s0 = 2 * (int)first, ns = 2 * (int)n;
+  // Everything below runs on st and is complete when the call returns: a later run waits behind
+  // none of it.  (One stream: the chunks' pack kernels are ~3 % of their transfers, and alternating
+  // the chunks between st and st2 measured no faster at 1024 VLP-16 problems and slower at 64
+  // HDL-64E ones)
+  hipStream_t st = x->st;
+  x->prof.begin(x->st);
+  HIP_TRY(sr_pack_offsets(sb, s0, ns, x->pack_table, x->st));
+  x->prof.mark("k_sr_pack_offsets");
+  const size_t row = (size_t)ns + 1;
+  HIP_TRY(hipMemcpyAsync(x->pack_table_h, x->pack_table, kPackClouds * row * sizeof(uint64_t), hipMemcpyDeviceToHost, x->st));
+  x->prof.mark("batch_features_table_d2h");
+  HIP_TRY(hipStreamSynchronize(x->st));
+  const uint64_t* T = x->pack_table_h;  // T[c * row + j]
+  unsigned wanted = 0, mask = 0;
+  for (int c = 0; c < kPackClouds; ++c) {
+    if (!cl[c]->pts && !cl[c]->offset) continue;
+    wanted |= 1u << c;
+    if (T[c * row + ns] > 0xffffffffull) {
+      x->prof.collect();
+      return fail(LOAM_E_INVAL, "loam_batch_features: a cloud of this range has more points than a uint32_t offset holds; "
+                                "ask for a smaller range of problems");
+    }
+  }
+  bool fits = true;
+  for (int c = 0; c < kPackClouds; ++c) {
+    if (!(wanted >> c & 1)) continue;
+    const uint64_t total = T[c * row + ns];
+    cl[c]->count = total;
+    if (cl[c]->offset)
+      for (size_t j = 0; j < row; ++j) cl[c]->offset[j] = (uint32_t)T[c * row + j];
+    if (!cl[c]->pts) continue;
+    if (cl[c]->capacity < total) fits = false;
+    else if (total > 0) mask |= 1u << c;
+  }
+  if (!fits) {
+    x->prof.collect();
+    return fail(LOAM_E_CAPACITY, "loam_batch_features: a cloud's capacity is too small (count holds the required size)");
+  }
+  // the sweep range in chunks whose packed size fits one staging buffer (a sweep always does:
+  // ensure_pack), each cloud's run of a chunk contiguous at cbase[c]
+  struct Chunk {
+    int j0, j1;
+    size_t cbase[kPackClouds], pts;
+  };
+  std::vector<Chunk> chunks;
+  auto span = [&](int a, int b) {
+    size_t s = 0;
+    for (int c = 0; c < kPackClouds; ++c)
+      if (mask >> c & 1) s += (size_t)(T[c * row + b] - T[c * row + a]);
+    return s;
+  };
+  for (int j0 = 0; mask && j0 < ns;) {
+    int j1 = j0 + 1;
+    while (j1 < ns && span(j0, j1 + 1) <= kPackStagePts) ++j1;
+    Chunk ch;
+    ch.j0 = j0;
+    ch.j1 = j1;
+    ch.pts = 0;
+    for (int c = 0; c < kPackClouds; ++c) {
+      ch.cbase[c] = ch.pts;
+      if (mask >> c & 1) ch.pts += (size_t)(T[c * row + j1] - T[c * row + j0]);
+    }
+    if (ch.pts > kPackStagePts) {  // (cannot happen: counts are clamped to the strides ensure_pack sized for)
+      x->prof.collect();
+      return fail(LOAM_E_INVAL, "loam_batch_features: a sweep's clouds exceed the download staging");
+    }
+    if (ch.pts) chunks.push_back(ch);
+    j0 = j1;
+  }
+  // chunk k: packed into device buffer k & 1 and DMA'd into pinned buffer k & 1; while the host
+  // copies chunk k into the caller's arrays, chunk k + 1 is packed and transferred
+  auto enqueue = [&](size_t k) -> hipError_t {
+    const Chunk& ch = chunks[k];
+    const int i = (int)(k & 1);
+    long long dbase[kPackClouds];
+    for (int c = 0; c < kPackClouds; ++c) dbase[c] = (long long)ch.cbase[c] - (long long)T[c * row + ch.j0];
+    // (profiling: the time the stream sat empty while the host copied the chunk before, kept out of
+    // the kernel's segment)
+    x->prof.mark("batch_features_host_wait");
+    hipError_t e = sr_pack(sb, x->pack_table, s0, ns, ch.j0, ch.j1 - ch.j0, mask, dbase, x->pack_dev[i], st);
+    x->prof.mark("k_sr_pack");
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(x->pack_pin[i], x->pack_dev[i], ch.pts * sizeof(float4), hipMemcpyDeviceToHost, st);
+    x->prof.mark("batch_features_d2h");
+    if (e == hipSuccess) e = hipEventRecord(x->pack_done[i], st);
+    return e;
+  };
+  hipError_t he = hipSuccess;
+  for (size_t k = 0; k < chunks.size() && k < 2 && he == hipSuccess; ++k) he = enqueue(k);
+  for (size_t k = 0; k < chunks.size() && he == hipSuccess; ++k) {
+    const Chunk& ch = chunks[k];
+    he = hipEventSynchronize(x->pack_done[k & 1]);
+    if (he != hipSuccess) break;
+    for (int c = 0; c < kPackClouds; ++c) {
+      if (!(mask >> c & 1)) continue;
+      const uint64_t a = T[c * row + ch.j0], b = T[c * row + ch.j1];
+      if (b > a) copy_wide(cl[c]->pts + a, x->pack_pin[k & 1] + ch.cbase[c], (size_t)(b - a) * sizeof(float4));
+    }
+    if (k + 2 < chunks.size()) he = enqueue(k + 2);
+  }
+  if (he != hipSuccess) {  // (drain what was enqueued before reporting)
+    (void)hipStreamSynchronize(st);
+    return fail(LOAM_E_HIP, std::string("loam_batch_features: ") + hipGetErrorString(he));
+  }
+  x->prof.collect();
+  return LOAM_OK;
+}
 
 namespace loam {
 __global__ __launch_bounds__(256) void k_xfer(Xfer x) {

@@ -284,6 +284,15 @@ hipError_t sr_alloc(SrBuffers& b, int S, int cap, int R);  // on failure: freed,
 hipError_t sr_scatter_packed(const float4* src, const int* off, const int* n, float4* raw, int cap, int S,
                              hipStream_t st);
 void sr_free(SrBuffers& b);
+// loam_batch_features: the clouds of a set in loam_batch_clouds order (full, sharp, less_sharp,
+// flat, less_flat), packed back to back for a dense download.
+constexpr int kPackClouds = 5;
+// table [kPackClouds][ns + 1] (device): table[c][j] = points of cloud c in sweeps [s0, s0 + j) of b
+hipError_t sr_pack_offsets(const SrBuffers& b, int s0, int ns, uint64_t* table, hipStream_t st);
+// sweeps [j0, j0 + nj) of that table, the clouds in the bit mask `clouds`: point k of cloud c's
+// packed selection (k in [table[c][j0], table[c][j0 + nj])) goes to dst[dbase[c] + k]
+hipError_t sr_pack(const SrBuffers& b, const uint64_t* table, int s0, int ns, int j0, int nj, unsigned clouds,
+                   const long long* dbase, float4* dst, hipStream_t st);
 // runs the whole scan registration for sweeps [0, S) already in b.raw / b.raw_n
 // sorted (optional): recorded once the ring sort has written the full cloud (the later kernels
 // only read it), so that its download can start while the feature kernels run

@@ -17,6 +17,8 @@
 //                   Rings are independent whenever their spans are >5 points apart (always for
 //                   sweeps with no empty ring); otherwise one workgroup walks the rings in order.
 //  k_sr_compact     per sweep: ring-major concatenation of the picks and the downsampled lessFlat.
+//  k_sr_pack_offsets / k_sr_pack   (loam_batch_features only) the clouds of a range of sweeps packed
+//                   back to back for a dense download: prefix sums of the counts, then a streaming copy.
 //
 // HBM traffic per sweep (algorithmic): 16 B/pt raw read, 16 B/pt ring-sorted
 // write + read, 16 B per feature point written.
@@ -1741,6 +1743,115 @@ hipError_t sr_scatter_packed(const float4* src, const int* off, const int* n, fl
   if (S <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_sr_scatter_packed, dim3(std::max(1, std::min(64, (cap + 255) / 256)), S), dim3(256), 0, st, src,
                      off, n, raw, cap);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- feature download (loam_batch_features)
+// The five clouds of a set are strided per sweep (full / lflat [S][cap], sharp [S][12R], lsharp
+// [S][120R], flat [S][24R]) and a sweep fills a fraction of its stride; the download packs the
+// valid prefixes back to back on the device so that the transfer to the host is dense.
+namespace {
+// per-sweep stride of cloud c (loam_batch_clouds order) in points
+__host__ __device__ inline int pack_stride(const SrBuffers& b, int c) {
+  return c == 1 ? kSharpPerRing * b.R : c == 2 ? kLessSharpPerRing * b.R : c == 3 ? kFlatPerRing * b.R : b.cap;
+}
+LOAM_D const float4* pack_src(const SrBuffers& b, int c) {
+  return c == 0 ? b.full : c == 1 ? b.sharp : c == 2 ? b.lsharp : c == 3 ? b.flat : b.lflat;
+}
+
+constexpr int kPackOffThreads = 256;
+// One workgroup: the exclusive prefix sums of the counts of sweeps [s0, s0 + ns) for the five
+// clouds, table[c][j] = points of cloud c in sweeps [s0, s0 + j), j = 0 .. ns.  The sweeps go
+// through the block scan 256 at a time with the running total carried in a register, so ns is
+// unbounded.  A count is clamped to its stride: k_sr_pack's reads stay inside the sweep's slot
+// whatever a failed sweep left in cnt.
+__global__ __launch_bounds__(kPackOffThreads) void k_sr_pack_offsets(SrBuffers b, int s0, int ns, uint64_t* table) {
+  __shared__ int scratch[kPackOffThreads / 64 + 1];
+  const int tid = threadIdx.x;
+  for (int c = 0; c < kPackClouds; ++c) {
+    const int stride = pack_stride(b, c);
+    uint64_t* row = table + (size_t)c * (ns + 1);
+    uint64_t carry = 0;
+    for (int base = 0; base < ns; base += kPackOffThreads) {
+      const int j = base + tid;
+      int n = 0;
+      if (j < ns) {
+        n = c == 0 ? b.n_full[s0 + j] : b.cnt[(size_t)(s0 + j) * 4 + (c - 1)];
+        n = min(max(n, 0), stride);
+      }
+      int total = 0;  // (<= 256 x 2^22 points: an int holds a block's sum)
+      const int excl = block_excl_scan<kPackOffThreads>(n, scratch, total);
+      if (j < ns) row[j] = carry + (uint64_t)excl;
+      carry += (uint64_t)total;
+    }
+    if (tid == 0) row[ns] = carry;
+  }
+}
+
+constexpr int kPackThreads = 256, kPackPerLane = 4, kPackTile = kPackThreads * kPackPerLane;
+constexpr int kPackGridMax = 2048;  // 8 workgroups for each of the 256 CUs; the rest grid-strided
+struct PackJob {
+  int s0, ns;             // the table's first sweep and its sweep count (row length ns + 1)
+  int j0, nj;             // this launch packs sweeps [j0, j0 + nj) of the table
+  int tile0[kPackClouds + 1];  // first tile of each cloud among a sweep's tiles (an unwanted cloud has none)
+  long long dbase[kPackClouds];  // dst index of cloud c's point k of the selection = dbase[c] + k
+};
+// Work item = (sweep, cloud, 1024-point tile of the cloud's stride): the valid points of the tile
+// from the sweep's slot to its packed place, one float4 per lane per access, four in flight.  A
+// tile beyond the sweep's count ends at once.  Source (slot base + t) and destination (packed
+// offset + t) runs advance by one 16-byte point per lane: both sides coalesced and 16-byte aligned.
+__global__ __launch_bounds__(kPackThreads) void k_sr_pack(SrBuffers b, PackJob job, const uint64_t* table, float4* dst) {
+  const int per_sweep = job.tile0[kPackClouds];
+  const uint32_t items = (uint32_t)per_sweep * (uint32_t)job.nj;  // (< 2^31: sr_pack)
+  for (uint32_t w = blockIdx.x; w < items; w += gridDim.x) {
+    const int j = job.j0 + (int)(w / (uint32_t)per_sweep), r = (int)(w % (uint32_t)per_sweep);
+    int c = 0;
+    while (r >= job.tile0[c + 1]) ++c;
+    const int t0 = (r - job.tile0[c]) * kPackTile;
+    const uint64_t* row = table + (size_t)c * (job.ns + 1);
+    const uint64_t o = row[j];
+    const int n = (int)(row[j + 1] - o);
+    if (t0 >= n) continue;
+    const float4* src = pack_src(b, c) + (size_t)(job.s0 + j) * pack_stride(b, c);
+    float4* out = dst + (job.dbase[c] + (long long)o);
+    float4 v[kPackPerLane];
+#pragma unroll
+    for (int k = 0; k < kPackPerLane; ++k) {
+      const int t = t0 + k * kPackThreads + (int)threadIdx.x;
+      v[k] = t < n ? src[t] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+#pragma unroll
+    for (int k = 0; k < kPackPerLane; ++k) {
+      const int t = t0 + k * kPackThreads + (int)threadIdx.x;
+      if (t < n) out[t] = v[k];
+    }
+  }
+}
+}  // namespace
+
+hipError_t sr_pack_offsets(const SrBuffers& b, int s0, int ns, uint64_t* table, hipStream_t st) {
+  if (s0 < 0 || ns <= 0 || s0 + ns > b.S) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_sr_pack_offsets, dim3(1), dim3(kPackOffThreads), 0, st, b, s0, ns, table);
+  return hipGetLastError();
+}
+
+hipError_t sr_pack(const SrBuffers& b, const uint64_t* table, int s0, int ns, int j0, int nj, unsigned clouds,
+                   const long long* dbase, float4* dst, hipStream_t st) {
+  if (s0 < 0 || ns <= 0 || s0 + ns > b.S || j0 < 0 || nj <= 0 || j0 + nj > ns) return hipErrorInvalidValue;
+  PackJob job;
+  job.s0 = s0; job.ns = ns; job.j0 = j0; job.nj = nj;
+  int tiles = 0;
+  for (int c = 0; c < kPackClouds; ++c) {
+    job.tile0[c] = tiles;
+    if (clouds >> c & 1) tiles += (pack_stride(b, c) + kPackTile - 1) / kPackTile;
+    job.dbase[c] = dbase[c];
+  }
+  job.tile0[kPackClouds] = tiles;
+  if (tiles == 0) return hipSuccess;
+  const long long items = (long long)tiles * nj;
+  if (items > 0x7fffffffLL) return hipErrorInvalidValue;  // (the kernel counts its work items in 32 bits)
+  hipLaunchKernelGGL(k_sr_pack, dim3((unsigned)std::min<long long>(items, kPackGridMax)), dim3(kPackThreads), 0, st, b,
+                     job, table, dst);
   return hipGetLastError();
 }
 
