@@ -241,6 +241,59 @@ typedef struct { loam_batch_cloud full, sharp, less_sharp, flat, less_flat; } lo
  * filled, and the call may be repeated with more room. */
 int loam_batch_features(loam_ctx *ctx, uint32_t first, uint32_t n, loam_batch_clouds *out);
 
+/* ---- the map: save it, load it (no reference equivalent: the reference never hands its map over) ----
+ * The streaming context's cube map, laserCloudCornerArray / laserCloudSurfArray
+ * (src/laserMapping.cpp:64-70, :96-99, :980-1036): 21 x 11 x 21 cubes of 50 m.  Each cloud is in
+ * canonical order: cubes in ascending cube index (i + 21*j + 231*k, the reference's cubeInd),
+ * inside a cube the store's own point order (FLANN ties by index and PCL's VoxelGrid sums in input
+ * order, so that order is part of the map).  Points are in the map frame.  Batch maps have no
+ * export. */
+#define LOAM_MAP_CUBES 4851 /* 21 * 11 * 21 */
+
+typedef struct {
+  loam_point *pts;        /* caller-owned; export: NULL = the points are not wanted; import: the points */
+  uint64_t capacity;      /* export: points pts holds; import: ignored */
+  uint64_t count;         /* export: points of the cloud (written, or required on LOAM_E_CAPACITY); import: points given */
+  uint32_t *cube_offset;  /* export: caller-owned [LOAM_MAP_CUBES + 1] or NULL: cube c = pts[cube_offset[c] .. cube_offset[c+1]); import: ignored */
+} loam_map_cloud;
+
+typedef struct {
+  loam_map_cloud corner;   /* laserCloudCornerArray */
+  loam_map_cloud surf;     /* laserCloudSurfArray */
+  int32_t center[3];       /* laserCloudCenWidth / CenHeight / CenDepth (10, 5, 10 at start) */
+  int32_t surround_phase;  /* mapFrameCount, 0..4 (4 = the next mapping frame publishes surround) */
+  loam_pose6 aft;          /* transformAftMapped */
+  loam_pose6 bef;          /* transformBefMapped */
+} loam_map;
+
+/* Writes the context's streaming map and mapping pose state, after waiting for the context's
+ * queued work (a loam_chain_sweep's deferred map update included).  For each cloud count and (when
+ * given) cube_offset are always filled, the points when pts is given; every pts NULL is the
+ * sizes-only query.  LOAM_E_CAPACITY (a cloud's points do not fit its capacity) writes no point
+ * and fills every count and offset, so the call can be repeated with more room.  The call changes
+ * nothing: a mapping frame after it behaves as if it had not happened.  The points are packed on
+ * the device and transferred through loam_batch_features' fixed-size staging, chunk by chunk.
+ * LOAM_E_INVAL for a null argument, or when the last map update overflowed map_capacity. */
+int loam_map_export(loam_ctx *ctx, loam_map *out);
+
+/* Replaces the context's streaming map and mapping pose state: center, bef, aft and
+ * surround_phase are set, a pending surround publication is dropped; odometry, scan registration
+ * and the IMU queues are left alone.  The points need not be sorted: each goes to the cube the
+ * reference's insertion would choose for it with the given center (:983-989) and keeps its input
+ * order inside that cube.  Points outside the grid or with a non-finite coordinate are left out
+ * and counted per cloud in dropped[0] (corner) / dropped[1] (surf) when dropped is given.  Nothing
+ * is downsampled here: as in the reference, a cube is downsampled when it next falls into a
+ * frame's valid set (:1018-1036).  An import of two empty clouds is a map reset that keeps the
+ * given poses.  The two intended uses:
+ *   resume    import exactly what loam_map_export gave; the stream continues bit for bit;
+ *   localize  in a prior map with a fresh odometry: bef = zeros, aft = the initial pose guess
+ *             (the first mapping frame then applies the whole odometry pose on top of aft).
+ * Errors: LOAM_E_INVAL for a null argument (a cloud with count > 0 and pts NULL included),
+ * surround_phase outside 0..4, a |center| component above 2^24, or more than 2^31 - 2^23 points in
+ * all; LOAM_E_CAPACITY when the kept points exceed map_capacity (dropped is filled).  In every
+ * error case the old map and poses are left exactly as they were. */
+int loam_map_import(loam_ctx *ctx, const loam_map *in, uint64_t dropped[2]);
+
 /* scheduling (no reference equivalent; the reference's nodes are OS processes): priority of the
  * context's HIP streams.  priority > 0 = the device's highest stream priority, 0 = normal,
  * < 0 = lowest.  Used by a node pipeline to favour its critical node (laserMapping) when several

@@ -119,10 +119,28 @@ class BatchClouds(ctypes.Structure):
     _fields_ = [(n, BatchCloud) for n in BATCH_CLOUDS]
 
 
+MAP_CUBES = 4851  # LOAM_MAP_CUBES: 21 * 11 * 21 (src/laserMapping.cpp:64-70)
+
+
+class MapCloud(ctypes.Structure):
+    """include/loam/loam.h loam_map_cloud: one cloud of the cube map in canonical order"""
+    _fields_ = [("pts", ctypes.c_void_p), ("capacity", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                ("cube_offset", ctypes.c_void_p)]
+
+
+class Map(ctypes.Structure):
+    """include/loam/loam.h loam_map"""
+    _fields_ = [("corner", MapCloud), ("surf", MapCloud), ("center", ctypes.c_int32 * 3),
+                ("surround_phase", ctypes.c_int32), ("aft", Pose6), ("bef", Pose6)]
+
+
+MAP_KEYS = ("corner", "surf", "corner_offset", "surf_offset", "center", "surround_phase", "aft", "bef")
+
+
 EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_error", "loam_imu",
            "loam_scan_registration", "loam_odometry", "loam_mapping", "loam_mapping_surround",
            "loam_maintenance", "loam_chain_sweep",
-           "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_get_stats",
+           "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_get_stats",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -164,6 +182,8 @@ def lib():
         L.loam_batch_download.argtypes = [PP, P(Pose6), P(Pose6), P(Stats)]
         L.loam_batch_lm_info.argtypes = [PP, P(ctypes.c_int32), P(ctypes.c_int32), P(Pose6)]
         L.loam_batch_features.argtypes = [PP, ctypes.c_uint32, ctypes.c_uint32, P(BatchClouds)]
+        L.loam_map_export.argtypes = [PP, P(Map)]
+        L.loam_map_import.argtypes = [PP, P(Map), P(ctypes.c_uint64)]
         L.loam_get_stats.argtypes = [PP, P(Stats)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
@@ -411,6 +431,57 @@ class Engine:
         if clouds:
             _check(lib().loam_batch_features(self.h, first, n, ctypes.byref(bc)))
         return {c: (pts[c], offs[c]) for c in clouds}
+
+    # --- the map
+    def map_export(self):
+        """the streaming context's cube map and mapping pose state (loam_map_export): a dict of
+        corner / surf ([N, 4] float32, canonical order: cube index ascending, the store's order
+        inside a cube), corner_offset / surf_offset ([MAP_CUBES + 1] uint32: cube c is
+        points[offset[c]:offset[c + 1]]), center ([3] int32), surround_phase, aft, bef"""
+        m = Map()
+        offs = [np.zeros(MAP_CUBES + 1, np.uint32) for _ in range(2)]
+        m.corner.cube_offset, m.surf.cube_offset = offs[0].ctypes.data, offs[1].ctypes.data
+        _check(lib().loam_map_export(self.h, ctypes.byref(m)))  # sizes only
+        pts = [np.empty((int(c.count), 4), np.float32) for c in (m.corner, m.surf)]
+        for c, a in zip((m.corner, m.surf), pts):
+            c.pts, c.capacity = a.ctypes.data, a.shape[0]
+        _check(lib().loam_map_export(self.h, ctypes.byref(m)))
+        return {"corner": pts[0], "surf": pts[1], "corner_offset": offs[0], "surf_offset": offs[1],
+                "center": np.array(m.center[:], np.int32), "surround_phase": int(m.surround_phase),
+                "aft": m.aft.arr(), "bef": m.bef.arr()}
+
+    def map_import(self, corner, surf, center=(10, 5, 10), surround_phase=4, aft=None, bef=None):
+        """replaces the context's map and mapping pose state (loam_map_import): corner / surf [N, 4]
+        map-frame points in any order; returns the (corner, surf) counts of the points left out
+        (outside the grid about `center`, or non-finite).  Resume: pass what map_export gave.
+        Localize in a prior map with a fresh odometry: bef = None (zeros), aft = the pose guess."""
+        m = Map()
+        keep = []
+        for c, a in ((m.corner, corner), (m.surf, surf)):
+            a = np.ascontiguousarray(a, np.float32).reshape(-1, 4)
+            keep.append(a)
+            c.pts, c.count, c.capacity = (a.ctypes.data if a.shape[0] else None), a.shape[0], a.shape[0]
+        m.center[:] = [int(v) for v in center]
+        m.surround_phase = int(surround_phase)
+        m.aft = Pose6.of(np.zeros(6) if aft is None else aft)
+        m.bef = Pose6.of(np.zeros(6) if bef is None else bef)
+        dropped = (ctypes.c_uint64 * 2)(0, 0)
+        _check(lib().loam_map_import(self.h, ctypes.byref(m), dropped))
+        return int(dropped[0]), int(dropped[1])
+
+
+def save_map(path, m):
+    """a map_export dict as an .npz file (numpy only)"""
+    np.savez(path, **{k: np.asarray(m[k]) for k in MAP_KEYS})
+
+
+def load_map(path):
+    """the dict save_map wrote; Engine.map_import(m["corner"], m["surf"], m["center"],
+    m["surround_phase"], m["aft"], m["bef"]) resumes from it"""
+    with np.load(path) as z:
+        m = {k: z[k] for k in MAP_KEYS}
+    m["surround_phase"] = int(m["surround_phase"])
+    return m
 
 
 def maintenance(odom_sum, bef, aft):

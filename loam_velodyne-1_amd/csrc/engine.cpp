@@ -208,10 +208,15 @@ struct loam_ctx {
   float4* pack_pin[2] = {nullptr, nullptr};
   hipEvent_t pack_done[2] = {nullptr, nullptr};
   int pack_S = 0;
-  void free_pack() {  // (the call that used them has drained its work)
+  MapIo mio;  // loam_map_export / loam_map_import: their small tables (the points go through pack_dev / pack_pin)
+  void free_pack_table() {
     if (pack_table) (void)hipFree(pack_table);
     if (pack_table_h) (void)hipHostFree(pack_table_h);
     pack_table = pack_table_h = nullptr;
+    pack_S = 0;
+  }
+  void free_pack() {  // (the call that used them has drained its work)
+    free_pack_table();
     for (int i = 0; i < 2; ++i) {
       if (pack_dev[i]) (void)hipFree(pack_dev[i]);
       if (pack_pin[i]) (void)hipHostFree(pack_pin[i]);
@@ -474,6 +479,7 @@ void loam_destroy(loam_ctx* x) {
   mp_free(x->mpb2);
   x->free_feed();
   x->free_pack();
+  mp_map_free(x->mio);
   for (auto& e : x->feed_copied)
     if (e) (void)hipEventDestroy(e);
   if (x->sr_imu_dev) (void)hipFree(x->sr_imu_dev);
@@ -1703,24 +1709,41 @@ size_t pack_sweep_max(const loam_ctx* x) {
   return (size_t)2 * x->cap + (size_t)(kSharpPerRing + kLessSharpPerRing + kFlatPerRing) * x->R;
 }
 
+// the staging itself: shared by loam_batch_features and the map export / import, kept until loam_destroy
+int ensure_pack_stage(loam_ctx* x, const char* what) {
+  if (x->pack_pin[1] && x->pack_dev[1] && x->pack_done[1]) return LOAM_OK;
+  hipError_t he = hipSuccess;
+  for (int i = 0; i < 2; ++i) {
+    if (he == hipSuccess && !x->pack_dev[i]) he = hipMalloc((void**)&x->pack_dev[i], kPackStagePts * sizeof(float4));
+    if (he == hipSuccess && !x->pack_pin[i])
+      he = hipHostMalloc((void**)&x->pack_pin[i], kPackStagePts * sizeof(float4), hipHostMallocDefault);
+    if (he == hipSuccess && !x->pack_done[i]) he = hipEventCreateWithFlags(&x->pack_done[i], hipEventDisableTiming);
+  }
+  if (he != hipSuccess) {
+    x->free_pack();
+    return fail(LOAM_E_NOMEM, std::string(what) + " staging allocation failed: " + hipGetErrorString(he));
+  }
+  return LOAM_OK;
+}
+
 int ensure_pack(loam_ctx* x) {
   const int S = 2 * x->P;
   if (x->pack_S == S) return LOAM_OK;
   if (pack_sweep_max(x) > kPackStagePts)
     return fail(LOAM_E_INVAL, "loam_batch_features: max_points is too large for the download staging (one sweep's "
                               "clouds must fit " + std::to_string(kPackStagePts) + " points)");
-  x->free_pack();
+  x->free_pack_table();
   hipError_t he = hipMalloc((void**)&x->pack_table, (size_t)kPackClouds * (S + 1) * sizeof(uint64_t));
   if (he == hipSuccess)
     he = hipHostMalloc((void**)&x->pack_table_h, (size_t)kPackClouds * (S + 1) * sizeof(uint64_t), hipHostMallocDefault);
-  for (int i = 0; i < 2; ++i) {
-    if (he == hipSuccess) he = hipMalloc((void**)&x->pack_dev[i], kPackStagePts * sizeof(float4));
-    if (he == hipSuccess) he = hipHostMalloc((void**)&x->pack_pin[i], kPackStagePts * sizeof(float4), hipHostMallocDefault);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&x->pack_done[i], hipEventDisableTiming);
-  }
   if (he != hipSuccess) {
     x->free_pack();
     return fail(LOAM_E_NOMEM, std::string("feature download staging allocation failed: ") + hipGetErrorString(he));
+  }
+  const int rc = ensure_pack_stage(x, "feature download");
+  if (rc) {
+    x->free_pack();
+    return rc;
   }
   x->pack_S = S;
   return LOAM_OK;
@@ -1876,6 +1899,173 @@ extern "C" int loam_batch_features(loam_ctx* x, uint32_t first, uint32_t n, loam
     return fail(LOAM_E_HIP, std::string("loam_batch_features: ") + hipGetErrorString(he));
   }
   x->prof.collect();
+  return LOAM_OK;
+}
+
+// ------------------------------------------------------------------ map export / import
+namespace {
+// a context's queued work: the node calls' stream and the side stream a deferred update runs on
+int map_drain(loam_ctx* x) {
+  HIP_TRY(hipSetDevice(x->device));
+  mp_wait_update(x->mp1, x->st);
+  HIP_TRY(hipStreamSynchronize(x->st));
+  if (x->st2) HIP_TRY(hipStreamSynchronize(x->st2));
+  const hipError_t he = x->mp1.take_error();
+  if (he != hipSuccess) return fail(LOAM_E_HIP, std::string("mapping: ") + hipGetErrorString(he));
+  return LOAM_OK;
+}
+}  // namespace
+
+extern "C" int loam_map_export(loam_ctx* x, loam_map* out) {
+  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
+  int rc = map_drain(x);
+  if (rc) return rc;
+  MpBuffers& b = x->mp1;
+  HIP_TRY(mp_map_ensure(x->mio));
+  hipStream_t st = x->st;
+  x->prof.begin(st);
+  HIP_TRY(mp_map_table(b, x->mio, st, &x->prof));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int* T = x->mio.tab_h;
+  const int nC = T[kMapTabOff + kCubeNum], total = T[kMapTabOff + kMapKeys];
+  if ((T[kMapTabInfo + 3] & ERR_CAP_MAP) || nC < 0 || total < nC || total > b.map_cap) {
+    x->prof.collect();
+    return fail(LOAM_E_INVAL, "loam_map_export: the last map update exceeded map_capacity, the store is not valid");
+  }
+  loam_map_cloud* cl[2] = {&out->corner, &out->surf};
+  const int first[2] = {0, nC}, count[2] = {nC, total - nC};
+  bool fits = true, want = false;
+  for (int k = 0; k < 2; ++k) {
+    cl[k]->count = (uint64_t)count[k];
+    if (cl[k]->cube_offset)
+      for (int c = 0; c <= kCubeNum; ++c) cl[k]->cube_offset[c] = (uint32_t)(T[kMapTabOff + k * kCubeNum + c] - first[k]);
+    if (!cl[k]->pts) continue;
+    if (cl[k]->capacity < (uint64_t)count[k]) fits = false;
+    else if (count[k] > 0) want = true;
+  }
+  for (int k = 0; k < 3; ++k) out->center[k] = T[kMapTabInfo + k];
+  out->surround_phase = x->map_frame_count;
+  std::memcpy(&out->aft, T + kMapTabInfo + 4, sizeof(loam_pose6));
+  std::memcpy(&out->bef, T + kMapTabInfo + 10, sizeof(loam_pose6));
+  if (!fits) {
+    x->prof.collect();
+    return fail(LOAM_E_CAPACITY, "loam_map_export: a cloud's capacity is too small (count holds the required size)");
+  }
+  if (!want) {
+    x->prof.collect();
+    return LOAM_OK;
+  }
+  rc = ensure_pack_stage(x, "map export");
+  if (rc) return rc;
+  HIP_TRY(mp_map_pack(b, x->mio, total, st, &x->prof));
+  // the wanted clouds' runs of vin in chunks of one pinned buffer: chunk k is DMA'd into buffer
+  // k & 1 while the host copies chunk k - 1 into the caller's array
+  struct Chunk {
+    int kind;
+    size_t a, n;  // points [a, a + n) of the cloud
+  };
+  std::vector<Chunk> chunks;
+  for (int k = 0; k < 2; ++k)
+    if (cl[k]->pts)
+      for (size_t a = 0; a < (size_t)count[k]; a += kPackStagePts)
+        chunks.push_back({k, a, std::min(kPackStagePts, (size_t)count[k] - a)});
+  auto enqueue = [&](size_t k) -> hipError_t {
+    const Chunk& ch = chunks[k];
+    x->prof.mark("map_export_host_wait");
+    hipError_t e = hipMemcpyAsync(x->pack_pin[k & 1], b.vin + first[ch.kind] + ch.a, ch.n * sizeof(float4),
+                                  hipMemcpyDeviceToHost, st);
+    x->prof.mark("map_export_d2h");
+    if (e == hipSuccess) e = hipEventRecord(x->pack_done[k & 1], st);
+    return e;
+  };
+  hipError_t he = hipSuccess;
+  for (size_t k = 0; k < chunks.size() && k < 2 && he == hipSuccess; ++k) he = enqueue(k);
+  for (size_t k = 0; k < chunks.size() && he == hipSuccess; ++k) {
+    const Chunk& ch = chunks[k];
+    he = hipEventSynchronize(x->pack_done[k & 1]);
+    if (he != hipSuccess) break;
+    copy_wide(cl[ch.kind]->pts + ch.a, x->pack_pin[k & 1], ch.n * sizeof(float4));
+    if (k + 2 < chunks.size()) he = enqueue(k + 2);
+  }
+  if (he != hipSuccess) {  // (drain what was enqueued before reporting)
+    (void)hipStreamSynchronize(st);
+    return fail(LOAM_E_HIP, std::string("loam_map_export: ") + hipGetErrorString(he));
+  }
+  x->prof.collect();
+  return LOAM_OK;
+}
+
+extern "C" int loam_map_import(loam_ctx* x, const loam_map* in, uint64_t* dropped) {
+  if (!x || !in) return fail(LOAM_E_INVAL, "null argument");
+  const loam_map_cloud* cl[2] = {&in->corner, &in->surf};
+  for (int k = 0; k < 2; ++k)
+    if (cl[k]->count > 0 && !cl[k]->pts) return fail(LOAM_E_INVAL, "loam_map_import: a cloud's pts is null");
+  if (in->surround_phase < 0 || in->surround_phase > 4)
+    return fail(LOAM_E_INVAL, "loam_map_import: surround_phase must be 0..4");
+  for (int k = 0; k < 3; ++k)
+    if (in->center[k] > (1 << 24) || in->center[k] < -(1 << 24))
+      return fail(LOAM_E_INVAL, "loam_map_import: a center component is beyond 2^24");
+  const uint64_t kMaxIn = ((uint64_t)1 << 31) - ((uint64_t)1 << 23);
+  if (cl[0]->count > kMaxIn || cl[1]->count > kMaxIn || cl[0]->count + cl[1]->count > kMaxIn)
+    return fail(LOAM_E_INVAL, "loam_map_import: more than 2^31 - 2^23 points");
+  int rc = map_drain(x);
+  if (rc) return rc;
+  MpBuffers& b = x->mp1;
+  HIP_TRY(mp_map_ensure(x->mio));
+  if (cl[0]->count + cl[1]->count > 0) {
+    rc = ensure_pack_stage(x, "map import");
+    if (rc) return rc;
+  }
+  static_assert(kMapChunkPts <= (int)kPackStagePts, "an import chunk fits one staging buffer");
+  hipStream_t st = x->st;
+  const int cen[3] = {in->center[0], in->center[1], in->center[2]};
+  x->prof.begin(st);
+  hipError_t he = mp_map_bin_begin(b, x->mio, st);
+  // chunk k: copied into pinned buffer k & 1, DMA'd into device buffer k & 1 and binned there, while
+  // the host copies chunk k + 1 into the other pinned buffer
+  size_t k = 0;
+  for (int kind = 0; kind < 2 && he == hipSuccess; ++kind)
+    for (uint64_t a = 0; a < cl[kind]->count && he == hipSuccess; a += kMapChunkPts, ++k) {
+      const size_t n = (size_t)std::min<uint64_t>(kMapChunkPts, cl[kind]->count - a);
+      const int i = (int)(k & 1);
+      if (k >= 2) he = hipEventSynchronize(x->pack_done[i]);  // (the chunk two back has left both buffers)
+      if (he != hipSuccess) break;
+      copy_wide(x->pack_pin[i], cl[kind]->pts + a, n * sizeof(float4));
+      x->prof.mark("map_import_host_wait");
+      he = hipMemcpyAsync(x->pack_dev[i], x->pack_pin[i], n * sizeof(float4), hipMemcpyHostToDevice, st);
+      x->prof.mark("map_import_h2d");
+      if (he == hipSuccess) he = mp_map_bin_chunk(b, x->mio, x->pack_dev[i], (int)n, kind, cen, st, &x->prof);
+      if (he == hipSuccess) he = hipEventRecord(x->pack_done[i], st);
+    }
+  if (he == hipSuccess) he = mp_map_bin_result(x->mio, st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    return fail(LOAM_E_HIP, std::string("loam_map_import: ") + hipGetErrorString(he));
+  }
+  const int* acc = x->mio.tab_h + kMapTabAcc;
+  if (dropped) {
+    dropped[0] = (uint64_t)acc[1];
+    dropped[1] = (uint64_t)acc[2];
+  }
+  if (acc[0] > b.map_cap) {
+    x->prof.collect();
+    return fail(LOAM_E_CAPACITY, "loam_map_import: the points inside the grid exceed map_capacity");
+  }
+  // everything so far wrote scratch only; the sort fills the idle pool and its slot table, and the
+  // store switches to them once they are enqueued without error
+  float pose12[12];
+  std::memcpy(pose12, &in->aft, sizeof(loam_pose6));
+  std::memcpy(pose12 + 6, &in->bef, sizeof(loam_pose6));
+  he = mp_map_install(b, x->mio, acc[0], cen, pose12, st, &x->prof);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) return fail(LOAM_E_HIP, std::string("loam_map_import: ") + hipGetErrorString(he));
+  x->prof.collect();
+  // (statistics only: the valid-point slot a deferred update's next frame reads as "the previous
+  // frame's", mp_stream_run; no frame built this store)
+  *(int*)(x->xb.h + kXferMpUpd + 4 * (1 - b.pool_cur)) = 0;
+  x->map_frame_count = in->surround_phase;
+  x->surround_due = false;
   return LOAM_OK;
 }
 

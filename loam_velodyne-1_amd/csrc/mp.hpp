@@ -231,5 +231,48 @@ void mp_batch_frame2(MpBuffers& b, const OdBuffers& od, int buf, const FeatView&
 int mp_batch_download(MpBuffers& b, hipStream_t st, loam_pose6* aft, loam_stats* stats, std::string& err);
 hipError_t mp_batch_iters(MpBuffers& b, hipStream_t st, int32_t* iters);
 
+// ---- map export / import of a streaming store (instance 0; loam_map_export / loam_map_import) ----
+// Canonical order: key = kind * kCubeNum + cube (kind 0 corner, 1 surf), ascending; inside a key
+// the store's own point order.  The small tables both calls need live in one device block (`tab`,
+// ints) with a pinned host copy of its head; the point scratch is the store's own idle buffers
+// (vin, vg_k / vg_k2 / vg_v / vg_v2, app_cnt: all rewritten by a frame before it reads them).
+constexpr int kMapKeys = 2 * kCubeNum;
+constexpr int kMapTabOff = 0;                     // [kMapKeys + 1] canonical offsets (export)
+constexpr int kMapTabInfo = kMapKeys + 2;         // centre[3], istate error, aft[6], bef[6] (export)
+constexpr int kMapTabAcc = kMapTabInfo + 16;      // kept points so far, dropped corner / surf (import)
+constexpr int kMapTabHead = kMapTabAcc + 8;       // ints of the head (what the host reads)
+constexpr int kMapTabSrc = kMapTabHead;           // [kMapKeys] pool offset of every key (export)
+constexpr int kMapChunkPts = 1 << 21;             // points of one import chunk at most
+constexpr int kMapBinTile = 1024;                 // points per workgroup of the chunk kernels
+constexpr int kMapChunkTiles = kMapChunkPts / kMapBinTile;
+constexpr int kMapTabTile = kMapTabSrc + kMapKeys + 2;  // [kMapChunkTiles] a chunk's kept points per tile, scanned in place
+constexpr int kMapTabInts = kMapTabTile + kMapChunkTiles;
+static_assert(kMapTabHead % 4 == 0 && kMapTabTile % 4 == 0, "table regions");
+struct MapIo {
+  int* tab = nullptr;    // device [kMapTabInts]
+  int* tab_h = nullptr;  // pinned [kMapTabHead]
+};
+hipError_t mp_map_ensure(MapIo& io);  // allocated by the first call
+void mp_map_free(MapIo& io);
+// export: the canonical offsets, the centre and the poses into io.tab (k_mp_map_table), copied to
+// io.tab_h; the caller synchronises st before reading it
+hipError_t mp_map_table(MpBuffers& b, MapIo& io, hipStream_t st, Prof* prof);
+// export: the store's points in canonical order into b.vin[0 .. total) (k_mp_map_pack); total =
+// tab_h[kMapKeys]
+hipError_t mp_map_pack(MpBuffers& b, MapIo& io, int total, hipStream_t st, Prof* prof);
+// import: zeroes the accumulators and the per-key counts
+hipError_t mp_map_bin_begin(MpBuffers& b, MapIo& io, hipStream_t st);
+// import: n <= kMapChunkPts points of one kind (device memory, 16-byte aligned): the kept ones
+// (in the grid about centre cen, finite) appended in input order to b.vin with their keys, at most
+// map_cap of them; the accumulators count on beyond that
+hipError_t mp_map_bin_chunk(MpBuffers& b, MapIo& io, const float4* pts, int n, int kind, const int* cen,
+                            hipStream_t st, Prof* prof);
+// import: the accumulators into io.tab_h + kMapTabAcc (the caller synchronises st)
+hipError_t mp_map_bin_result(MapIo& io, hipStream_t st);
+// import: the kept points (<= map_cap) sorted stably by key into the idle pool, its slot table, the
+// centre and the Bef / Aft poses (pose12: aft then bef); on success the store switches to that pool
+hipError_t mp_map_install(MpBuffers& b, MapIo& io, int kept, const int* cen, const float* pose12, hipStream_t st,
+                          Prof* prof);
+
 }  // namespace loam
 #endif
