@@ -294,6 +294,55 @@ int loam_map_export(loam_ctx *ctx, loam_map *out);
  * error case the old map and poses are left exactly as they were. */
 int loam_map_import(loam_ctx *ctx, const loam_map *in, uint64_t dropped[2]);
 
+/* ---- multi-hypothesis localization in the map (no reference equivalent) ----
+ * One sweep's feature clouds and n candidate poses: laserMapping's sweep-to-map refinement
+ * (src/laserMapping.cpp:411-974 without the map update) for every candidate at once against the
+ * context's streaming map, which is only read. */
+#define LOAM_LOC_SOLVED  0  /* the L-M ran; aft is the refined pose */
+#define LOAM_LOC_NO_LM   1  /* <= 10 corner or <= 100 surf map points in the candidate's valid cubes
+                               (src/laserMapping.cpp:706): no L-M, aft = the candidate's aft as given */
+#define LOAM_LOC_OFFGRID 2  /* a mapping frame at this guess would recentre the cube grid (:454-614);
+                               not evaluated, aft = the candidate's aft as given, the counts are 0 */
+#define LOAM_LOCALIZE_MAX 1024
+
+typedef struct {
+  loam_pose6 aft;            /* transformAftMapped a mapping frame would leave */
+  int32_t status;            /* LOAM_LOC_* */
+  int32_t iters;             /* L-M iterations run */
+  int32_t degenerate_steps;  /* updates projected by the iteration-0 degeneracy analysis */
+  uint32_t rows_last;        /* rows (accepted correspondences) of the last iteration evaluated */
+  uint32_t rows_sum;         /* rows summed over the iterations (loam_stats.mp_rows_sum) */
+  uint32_t stack_corner, stack_surf;  /* the sweep's stacks after their VoxelGrid (0.2 / 0.4) */
+  uint32_t map_corner, map_surf;      /* FromMap points of the candidate's valid cubes */
+} loam_localize_result;
+
+/* out[h], h < n, is what one loam_mapping(ctx', stamp, odom_sum, corner_last, surf_last, ...) would
+ * return in aft and report in its statistics, where ctx' holds this context's map and grid centre
+ * as they are now, transformBefMapped = bef[h] (zeros when bef is NULL), transformAftMapped =
+ * aft[h], and has received no IMU message: odom_sum through the nav_msgs quaternion round trip,
+ * transformAssociateToMap, the candidate's centre cube and FOV-tested 5x5x5 valid set, FromMap in
+ * the reference's order, the stacks' round trip and VoxelGrid, up to mp_max_iter L-M iterations,
+ * transformUpdate without IMU.  Without an L-M (LOAM_LOC_NO_LM) that frame leaves
+ * transformAftMapped alone, so aft = aft[h].  A candidate whose centre cube is within 3 of a grid
+ * edge (the frame would first recentre the grid, which this call never does) is LOAM_LOC_OFFGRID:
+ * import the map with another centre to evaluate it.  No residual score is returned; rank by
+ * status, rows_last / (stack_corner + stack_surf) and iters < mp_max_iter.
+ * The call waits for the context's queued work (a deferred map update included) and changes
+ * nothing in the context: the map, the grid centre, Bef / Aft, the surround phase and a pending
+ * surround publication, odometry, scan registration, the IMU queues and the last frame's statistics
+ * stay as they were, and every later call behaves as if this one had not happened.  Its working
+ * set (sized by n, the sweep's counts and the largest FromMap) is allocated on demand and kept until
+ * loam_destroy.
+ * Errors: LOAM_E_INVAL for a null argument (bef may be NULL), n == 0 or n > LOAM_LOCALIZE_MAX, a
+ * cloud with count > 0 and pts NULL, a cloud larger than max_points (corner_last: than the mapping
+ * stack's 120 points per ring), or a map whose last update overflowed map_capacity; LOAM_E_NOMEM
+ * when the working set cannot be allocated; LOAM_E_HIP for a failed HIP call.  In every error
+ * case out is untouched and the context is as it was. */
+int loam_map_localize(loam_ctx *ctx, const loam_pose6 *odom_sum,
+                      const loam_cloud_out *corner_last, const loam_cloud_out *surf_last,
+                      uint32_t n, const loam_pose6 *aft, const loam_pose6 *bef,
+                      loam_localize_result *out);
+
 /* scheduling (no reference equivalent; the reference's nodes are OS processes): priority of the
  * context's HIP streams.  priority > 0 = the device's highest stream priority, 0 = normal,
  * < 0 = lowest.  Used by a node pipeline to favour its critical node (laserMapping) when several

@@ -136,11 +136,25 @@ class Map(ctypes.Structure):
 
 MAP_KEYS = ("corner", "surf", "corner_offset", "surf_offset", "center", "surround_phase", "aft", "bef")
 
+LOC_SOLVED, LOC_NO_LM, LOC_OFFGRID = 0, 1, 2  # LOAM_LOC_*: a candidate's status
+LOCALIZE_MAX = 1024  # LOAM_LOCALIZE_MAX: candidates of one loam_map_localize call
+
+
+class LocalizeResult(ctypes.Structure):
+    """include/loam/loam.h loam_localize_result: one candidate of loam_map_localize"""
+    _fields_ = [("aft", Pose6), ("status", ctypes.c_int32), ("iters", ctypes.c_int32),
+                ("degenerate_steps", ctypes.c_int32), ("rows_last", ctypes.c_uint32), ("rows_sum", ctypes.c_uint32),
+                ("stack_corner", ctypes.c_uint32), ("stack_surf", ctypes.c_uint32),
+                ("map_corner", ctypes.c_uint32), ("map_surf", ctypes.c_uint32)]
+
+
+LOCALIZE_KEYS = tuple(n for n, _ in LocalizeResult._fields_)
+
 
 EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_error", "loam_imu",
            "loam_scan_registration", "loam_odometry", "loam_mapping", "loam_mapping_surround",
            "loam_maintenance", "loam_chain_sweep",
-           "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_get_stats",
+           "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_map_localize", "loam_get_stats",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -184,6 +198,8 @@ def lib():
         L.loam_batch_features.argtypes = [PP, ctypes.c_uint32, ctypes.c_uint32, P(BatchClouds)]
         L.loam_map_export.argtypes = [PP, P(Map)]
         L.loam_map_import.argtypes = [PP, P(Map), P(ctypes.c_uint64)]
+        L.loam_map_localize.argtypes = [PP, P(Pose6), P(CloudOut), P(CloudOut), ctypes.c_uint32, P(Pose6), P(Pose6),
+                                        P(LocalizeResult)]
         L.loam_get_stats.argtypes = [PP, P(Stats)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
@@ -468,6 +484,31 @@ class Engine:
         dropped = (ctypes.c_uint64 * 2)(0, 0)
         _check(lib().loam_map_import(self.h, ctypes.byref(m), dropped))
         return int(dropped[0]), int(dropped[1])
+
+    def map_localize(self, odom_sum, corner, surf, aft, bef=None):
+        """n candidate poses of one sweep against the context's map, which is left untouched
+        (loam_map_localize): aft / bef (n, 6) float32 (bef None = zeros).  Returns a dict of numpy
+        arrays, one entry per candidate: aft (n, 6), the pose a mapping frame started from
+        (bef[h], aft[h]) would leave, status (LOC_SOLVED / LOC_NO_LM / LOC_OFFGRID), iters,
+        degenerate_steps, rows_last, rows_sum, stack_corner, stack_surf, map_corner, map_surf.
+        Rank by status == LOC_SOLVED, then rows_last / (stack_corner + stack_surf)."""
+        aft = np.ascontiguousarray(aft, np.float32).reshape(-1, 6)
+        n = aft.shape[0]
+        P = ctypes.POINTER(Pose6)
+        pb = None
+        if bef is not None:
+            bef = np.ascontiguousarray(bef, np.float32).reshape(-1, 6)
+            if bef.shape[0] != n:
+                raise ValueError("aft and bef must hold the same number of candidates")
+            pb = bef.ctypes.data_as(P)
+        refs = [_cloud_ref(a) for a in (corner, surf)]
+        out = (LocalizeResult * max(n, 1))()
+        _check(lib().loam_map_localize(self.h, ctypes.byref(Pose6.of(odom_sum)), ctypes.byref(refs[0][0]),
+                                       ctypes.byref(refs[1][0]), n, aft.ctypes.data_as(P), pb, out))
+        rec = np.frombuffer(out, dtype=np.dtype([(k, np.float32, (6,)) if k == "aft" else
+                                                 (k, np.int32 if k in ("status", "iters", "degenerate_steps") else np.uint32)
+                                                 for k in LOCALIZE_KEYS]), count=n)
+        return {k: rec[k].copy() for k in LOCALIZE_KEYS}
 
 
 def save_map(path, m):

@@ -209,6 +209,7 @@ struct loam_ctx {
   hipEvent_t pack_done[2] = {nullptr, nullptr};
   int pack_S = 0;
   MapIo mio;  // loam_map_export / loam_map_import: their small tables (the points go through pack_dev / pack_pin)
+  MpLoc loc;  // loam_map_localize: the candidates' working set, allocated by the first call, kept until loam_destroy
   void free_pack_table() {
     if (pack_table) (void)hipFree(pack_table);
     if (pack_table_h) (void)hipHostFree(pack_table_h);
@@ -480,6 +481,7 @@ void loam_destroy(loam_ctx* x) {
   x->free_feed();
   x->free_pack();
   mp_map_free(x->mio);
+  mp_loc_free(x->loc);
   for (auto& e : x->feed_copied)
     if (e) (void)hipEventDestroy(e);
   if (x->sr_imu_dev) (void)hipFree(x->sr_imu_dev);
@@ -2066,6 +2068,109 @@ extern "C" int loam_map_import(loam_ctx* x, const loam_map* in, uint64_t* droppe
   *(int*)(x->xb.h + kXferMpUpd + 4 * (1 - b.pool_cur)) = 0;
   x->map_frame_count = in->surround_phase;
   x->surround_due = false;
+  return LOAM_OK;
+}
+
+// ------------------------------------------------------------------ multi-hypothesis localization
+// n candidate (Aft, Bef) poses of one sweep against the streaming map, which is only read: every
+// candidate is an instance of the context's second mapping working set (MpLoc, mp.hpp).  The host
+// reads the candidates' FromMap counts once (to size the set), then the results.
+extern "C" int loam_map_localize(loam_ctx* x, const loam_pose6* odom_sum, const loam_cloud_out* corner_last,
+                                 const loam_cloud_out* surf_last, uint32_t n, const loam_pose6* aft,
+                                 const loam_pose6* bef, loam_localize_result* out) {
+  static_assert(LOAM_LOCALIZE_MAX == kLocMax, "loam.h and mp.hpp");
+  static_assert(sizeof(loam_localize_result) == 60, "loam_localize_result layout");
+  if (!x || !odom_sum || !corner_last || !surf_last || !aft || !out) return fail(LOAM_E_INVAL, "null argument");
+  if (n == 0 || n > LOAM_LOCALIZE_MAX)
+    return fail(LOAM_E_INVAL, "loam_map_localize: n must be in [1, LOAM_LOCALIZE_MAX]");
+  if ((corner_last->count && !corner_last->pts) || (surf_last->count && !surf_last->pts))
+    return fail(LOAM_E_INVAL, "loam_map_localize: a cloud's pts is null");
+  const MpBuffers& s = x->mp1;
+  // (corner_last: also the mapping stack's own bound, 120 picks per ring, as loam_mapping has it)
+  if (corner_last->count > (uint32_t)x->cap || surf_last->count > (uint32_t)x->cap ||
+      corner_last->count > (uint32_t)s.capC)
+    return fail(LOAM_E_INVAL, "loam_map_localize: a cloud exceeds max_points (corner_last: 120 points per ring)");
+  int rc = map_drain(x);
+  if (rc) return rc;
+  MpLoc& L = x->loc;
+  hipError_t he = mp_loc_reserve(L, s, (int)n, (int)corner_last->count, (int)surf_last->count);
+  if (he != hipSuccess)
+    return fail(LOAM_E_NOMEM, std::string("loam_map_localize: working set allocation failed: ") + hipGetErrorString(he));
+  hipStream_t st = x->st;
+  Prof* pf = x->prof.on ? &x->prof : nullptr;  // (with profiling the L-M kernels also count their work)
+  MpBuffers& w = L.w;
+  float* ch = L.cand_h();
+  for (uint32_t h = 0; h < n; ++h) {
+    std::memcpy(ch + (size_t)h * 12, &aft[h], sizeof(loam_pose6));
+    if (bef) std::memcpy(ch + (size_t)h * 12 + 6, &bef[h], sizeof(loam_pose6));
+    else std::memset(ch + (size_t)h * 12 + 6, 0, sizeof(loam_pose6));
+  }
+  const int cnt[3] = {(int)corner_last->count, (int)surf_last->count, 0};
+  x->prof.begin(st);
+  x->pin.reset();
+  he = x->pin.reserve((size_t)cnt[0] + cnt[1], st);
+  if (he == hipSuccess) he = x->pin.up(st, w.inC, corner_last->pts, (size_t)cnt[0]);
+  if (he == hipSuccess) he = x->pin.up(st, w.inS, surf_last->pts, (size_t)cnt[1]);
+  if (he == hipSuccess) {
+    Xfer xp;
+    xp.put(w.in_n, cnt, 3 * sizeof(int));
+    xp.put(w.in_pose, odom_sum, 6 * sizeof(float));
+    he = xfer_launch(xp, st);
+  }
+  x->prof.mark("map_localize_h2d");
+  MpInput in;  // the one sweep, read by every candidate
+  in.corner = w.inC; in.surf = w.inS; in.full = nullptr;
+  in.corner_stride = in.surf_stride = in.full_stride = 0;
+  in.ncorner = w.in_n; in.nsurf = w.in_n + 1; in.nfull = w.in_n + 2;
+  in.ncorner_stride = in.nsurf_stride = in.nfull_stride = 0;
+  in.pose = w.in_pose; in.pose_stride = 0;
+  if (he == hipSuccess) he = mp_localize_prepare(L, s, in, (int)n, st, pf);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    x->prof.collect();
+    return fail(LOAM_E_HIP, std::string("loam_map_localize: ") + hipGetErrorString(he));
+  }
+  const int* head = L.head_h();
+  if (head[2 * n] & ERR_CAP_MAP) {
+    x->prof.collect();
+    return fail(LOAM_E_INVAL, "loam_map_localize: the last map update exceeded map_capacity, the store is not valid");
+  }
+  int from_max = 0, cloud_max = 0;
+  for (uint32_t h = 0; h < n; ++h) {
+    from_max = std::max(from_max, head[2 * h] + head[2 * h + 1]);
+    cloud_max = std::max(cloud_max, std::max(head[2 * h], head[2 * h + 1]));
+  }
+  he = mp_loc_reserve_map(L, from_max);
+  if (he != hipSuccess) {
+    x->prof.collect();
+    return fail(LOAM_E_NOMEM, std::string("loam_map_localize: FromMap allocation failed (") + std::to_string(n) + " x " +
+                                  std::to_string(from_max) + " points): " + hipGetErrorString(he));
+  }
+  he = mp_localize_solve(L, s, in, (int)n, from_max, cloud_max, std::max(cnt[0], cnt[1]), st, pf);
+  x->prof.mark("map_localize_d2h");
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    x->prof.collect();
+    return fail(LOAM_E_HIP, std::string("loam_map_localize: ") + hipGetErrorString(he));
+  }
+  x->prof.collect();
+  const int* R = L.res_h();
+  for (uint32_t h = 0; h < n; ++h) {
+    const int* r = R + (size_t)h * kLocResWords;
+    loam_localize_result& o = out[h];
+    std::memcpy(&o.aft, r + kLrAft, sizeof(loam_pose6));
+    o.status = r[kLrStatus];
+    o.iters = r[kLrIters];
+    o.degenerate_steps = r[kLrDegSteps];
+    o.rows_last = (uint32_t)r[kLrRowsLast];
+    o.rows_sum = (uint32_t)r[kLrRowsSum];
+    o.stack_corner = (uint32_t)r[kLrStackC];
+    o.stack_surf = (uint32_t)r[kLrStackS];
+    o.map_corner = (uint32_t)r[kLrMapC];
+    o.map_surf = (uint32_t)r[kLrMapS];
+  }
   return LOAM_OK;
 }
 

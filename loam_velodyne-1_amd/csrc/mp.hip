@@ -22,6 +22,9 @@
 //  k_mp_vcopy      per valid cube: old content ++ appended points -> DS input
 //  k_mp_compact    new cube store (valid cubes downsampled, others appended) into the other pool
 //  k_mp_register   full cloud to the map frame (:1060-1063)
+//  k_mp_loc_prepare / k_mp_loc_gather / k_mp_loc_result   loam_map_localize: n candidate poses of one
+//                  sweep as the instances of a second working set against the streaming store, which
+//                  is only read (prepare without recentring, FromMap per candidate, the L-M as above)
 
 #include <algorithm>
 #include <functional>
@@ -75,6 +78,56 @@ LOAM_D loampose::MapRot rot_load(const MpBuffers& b, int p) {
   return r;
 }
 
+// one thread: the frame's pose prediction for instance p (the odometry pose through the message
+// round trip, transformAssociateToMap with the instance's Bef / Aft, :110-197), its rotation and
+// the point on the Y axis of the FOV test (:616-622)
+LOAM_D void prepare_pose(const MpBuffers& b, const MpInput& in, int p) {
+  float* st = b.state + (size_t)p * kMpStateFloats;
+  float pose[6] = {0, 0, 0, 0, 0, 0};
+  if (in.pose)
+    for (int k = 0; k < 6; ++k) pose[k] = in.pose[(size_t)p * in.pose_stride + k];
+  loampose::pose_through_msg(pose, st + kMpSum);
+  loampose::associate_to_map(st + kMpSum, st + kMpBef, st + kMpAft, st + kMpIncre, st + kMpTobe);
+  const float* T = st + kMpTobe;
+  const loampose::MapRot r = loampose::map_rot(T);
+  rot_store(b, p, T);
+  const float4 onY = loampose::point_to_map(r, make_float4(0.0f, 10.0f, 0.0f, 0.0f));
+  st[kMpOnY] = onY.x; st[kMpOnY + 1] = onY.y; st[kMpOnY + 2] = onY.z;
+}
+
+// thread tid < 125: cube tid of the 5x5x5 neighbourhood of the centre cube (cI, cJ, cK) in the
+// reference's i, j, k loop order: inside the grid and in the field of view (:624-672)?  ind: its index
+LOAM_D bool fov_cube(const float* st, int tid, int cI, int cJ, int cK, int cW, int cH, int cD, int& ind) {
+  const float* T = st + kMpTobe;
+  bool inFOV = false;
+  ind = 0;
+  if (tid < 125) {
+    const int i = cI - 2 + tid / 25, j = cJ - 2 + (tid / 5) % 5, k = cK - 2 + tid % 5;
+    if (i >= 0 && i < kCubeW && j >= 0 && j < kCubeH && k >= 0 && k < kCubeD) {
+      const float ox = st[kMpOnY], oy = st[kMpOnY + 1], oz = st[kMpOnY + 2];
+      const float centerX = (float)(50.0 * (i - cW));
+      const float centerY = (float)(50.0 * (j - cH));
+      const float centerZ = (float)(50.0 * (k - cD));
+      for (int ii = -1; ii <= 1; ii += 2)
+        for (int jj = -1; jj <= 1; jj += 2)
+          for (int kk = -1; kk <= 1; kk += 2) {
+            const float cornerX = (float)(D(centerX) + 25.0 * ii);
+            const float cornerY = (float)(D(centerY) + 25.0 * jj);
+            const float cornerZ = (float)(D(centerZ) + 25.0 * kk);
+            const float sq1 = (T[3] - cornerX) * (T[3] - cornerX) + (T[4] - cornerY) * (T[4] - cornerY) +
+                              (T[5] - cornerZ) * (T[5] - cornerZ);
+            const float sq2 = (ox - cornerX) * (ox - cornerX) + (oy - cornerY) * (oy - cornerY) +
+                              (oz - cornerZ) * (oz - cornerZ);
+            const float check1 = (float)(100.0 + D(sq1) - D(sq2) - 10.0 * sqrt(3.0) * sqrt(D(sq1)));
+            const float check2 = (float)(100.0 + D(sq1) - D(sq2) + 10.0 * sqrt(3.0) * sqrt(D(sq1)));
+            if (check1 < 0 && check2 > 0) inFOV = true;
+          }
+      ind = cube_index(i, j, k);
+    }
+  }
+  return inFOV;
+}
+
 __global__ __launch_bounds__(kMpThreads) void k_mp_prepare(MpBuffers b, MpInput in) {
   const int p = blockIdx.x, tid = threadIdx.x;
   float* st = b.state + (size_t)p * kMpStateFloats;
@@ -83,16 +136,8 @@ __global__ __launch_bounds__(kMpThreads) void k_mp_prepare(MpBuffers b, MpInput 
   __shared__ int sh_shift[3], sh_count[3];
   __shared__ int sh_nshift, sh_c[3], sh_cen[3], sh_scan[16];
   if (tid == 0) {
-    float pose[6] = {0, 0, 0, 0, 0, 0};
-    if (in.pose)
-      for (int k = 0; k < 6; ++k) pose[k] = in.pose[(size_t)p * in.pose_stride + k];
-    loampose::pose_through_msg(pose, st + kMpSum);
-    loampose::associate_to_map(st + kMpSum, st + kMpBef, st + kMpAft, st + kMpIncre, st + kMpTobe);
+    prepare_pose(b, in, p);
     const float* T = st + kMpTobe;
-    const loampose::MapRot r = loampose::map_rot(T);
-    rot_store(b, p, T);
-    const float4 onY = loampose::point_to_map(r, make_float4(0.0f, 10.0f, 0.0f, 0.0f));
-    st[kMpOnY] = onY.x; st[kMpOnY + 1] = onY.y; st[kMpOnY + 2] = onY.z;
     int cW = ist[kMiCenW], cH = ist[kMiCenH], cD = ist[kMiCenD];
     int cI = cube_of(T[3], cW), cJ = cube_of(T[4], cH), cK = cube_of(T[5], cD);
     // :454-614: each `while` moves the grid one slab per pass until the centre cube is >= 3 from
@@ -156,35 +201,8 @@ __global__ __launch_bounds__(kMpThreads) void k_mp_prepare(MpBuffers b, MpInput 
   }
   // FOV selection (:616-672) and FromMap prefix: thread c tests cube c of the 5x5x5
   // neighbourhood (the reference's i, j, k loop order), block scans keep that order
-  const float* T = st + kMpTobe;
-  const int cI = sh_c[0], cJ = sh_c[1], cK = sh_c[2];
-  const int cW = sh_cen[0], cH = sh_cen[1], cD = sh_cen[2];
-  bool inFOV = false;
-  int ind = 0;
-  if (tid < 125) {
-    const int i = cI - 2 + tid / 25, j = cJ - 2 + (tid / 5) % 5, k = cK - 2 + tid % 5;
-    if (i >= 0 && i < kCubeW && j >= 0 && j < kCubeH && k >= 0 && k < kCubeD) {
-      const float ox = st[kMpOnY], oy = st[kMpOnY + 1], oz = st[kMpOnY + 2];
-      const float centerX = (float)(50.0 * (i - cW));
-      const float centerY = (float)(50.0 * (j - cH));
-      const float centerZ = (float)(50.0 * (k - cD));
-      for (int ii = -1; ii <= 1; ii += 2)
-        for (int jj = -1; jj <= 1; jj += 2)
-          for (int kk = -1; kk <= 1; kk += 2) {
-            const float cornerX = (float)(D(centerX) + 25.0 * ii);
-            const float cornerY = (float)(D(centerY) + 25.0 * jj);
-            const float cornerZ = (float)(D(centerZ) + 25.0 * kk);
-            const float sq1 = (T[3] - cornerX) * (T[3] - cornerX) + (T[4] - cornerY) * (T[4] - cornerY) +
-                              (T[5] - cornerZ) * (T[5] - cornerZ);
-            const float sq2 = (ox - cornerX) * (ox - cornerX) + (oy - cornerY) * (oy - cornerY) +
-                              (oz - cornerZ) * (oz - cornerZ);
-            const float check1 = (float)(100.0 + D(sq1) - D(sq2) - 10.0 * sqrt(3.0) * sqrt(D(sq1)));
-            const float check2 = (float)(100.0 + D(sq1) - D(sq2) + 10.0 * sqrt(3.0) * sqrt(D(sq1)));
-            if (check1 < 0 && check2 > 0) inFOV = true;
-          }
-      ind = cube_index(i, j, k);
-    }
-  }
+  int ind;
+  const bool inFOV = fov_cube(st, tid, sh_c[0], sh_c[1], sh_c[2], sh_cen[0], sh_cen[1], sh_cen[2], ind);
   const int nC = inFOV ? slots[ind * 4 + 1] : 0, nS = inFOV ? slots[ind * 4 + 3] : 0;
   int nv, accC, accS;
   const int xv = block_excl_scan<kMpThreads>(inFOV ? 1 : 0, sh_scan, nv);
@@ -207,6 +225,122 @@ __global__ __launch_bounds__(kMpThreads) void k_mp_prepare(MpBuffers b, MpInput 
     }
     b.nfrom[p * 2 + 0] = accC;
     b.nfrom[p * 2 + 1] = accS;
+  }
+}
+
+// ---------------------------------------------------------------- localization (loam_map_localize)
+// what the localization kernels read of the streaming store (instance 0's current pool)
+struct LocStore {
+  const int* slots;     // [kCubeNum][4] (offC, cntC, offS, cntS)
+  const float4* pool;
+  const int* istate;    // the store's instance state (grid centre, error word)
+  int map_cap;
+};
+
+// The read-only half of k_mp_prepare for candidate p = blockIdx.x of the working set w: the
+// candidate's Bef / Aft (cand: aft then bef) instead of a kept state, the grid centre of the shared
+// store, no recentring — a candidate whose centre cube is within 3 of a grid edge (the condition
+// of the reference's `while` loops, :454-614) is marked kMiLocOff and gets an empty valid set —
+// then the FOV cube selection and the FromMap prefix from the shared slot table.  Writes w only;
+// head: every candidate's FromMap counts and the store's error word, for the host.
+__global__ __launch_bounds__(kMpThreads) void k_mp_loc_prepare(MpBuffers w, MpInput in, LocStore s,
+                                                                const float* cand, int* head) {
+  const int p = blockIdx.x, tid = threadIdx.x;
+  float* st = w.state + (size_t)p * kMpStateFloats;
+  int* ist = w.istate + (size_t)p * kMpStateInts;
+  __shared__ int sh_c[3], sh_cen[3], sh_off, sh_scan[16];
+  if (tid == 0) {
+    for (int k = 0; k < 6; ++k) {
+      st[kMpAft + k] = cand[(size_t)p * 12 + k];
+      st[kMpBef + k] = cand[(size_t)p * 12 + 6 + k];
+    }
+    prepare_pose(w, in, p);
+    const float* T = st + kMpTobe;
+    const int cW = s.istate[kMiCenW], cH = s.istate[kMiCenH], cD = s.istate[kMiCenD];
+    const int cI = cube_of(T[3], cW), cJ = cube_of(T[4], cH), cK = cube_of(T[5], cD);
+    sh_off = cI < 3 || cI >= kCubeW - 3 || cJ < 3 || cJ >= kCubeH - 3 || cK < 3 || cK >= kCubeD - 3;
+    sh_c[0] = cI; sh_c[1] = cJ; sh_c[2] = cK;
+    sh_cen[0] = cW; sh_cen[1] = cH; sh_cen[2] = cD;
+    ist[kMiCubeI] = cI; ist[kMiCubeJ] = cJ; ist[kMiCubeK] = cK;
+    ist[kMiCenW] = cW; ist[kMiCenH] = cH; ist[kMiCenD] = cD;
+    ist[kMiShifts] = 0;
+    ist[kMiErr] = 0;
+    ist[kMiImu] = 0;  // (no IMU message: transformUpdate without the blend)
+    ist[kMiDegen] = 0;
+    ist[kMiLocOff] = sh_off;
+    if (p == 0) head[2 * gridDim.x] = s.istate[kMiErr];
+  }
+  __syncthreads();
+  int ind = 0;
+  const bool inFOV = !sh_off && fov_cube(st, tid, sh_c[0], sh_c[1], sh_c[2], sh_cen[0], sh_cen[1], sh_cen[2], ind);
+  const int nC = inFOV ? s.slots[ind * 4 + 1] : 0, nS = inFOV ? s.slots[ind * 4 + 3] : 0;
+  int nv, accC, accS;
+  const int xv = block_excl_scan<kMpThreads>(inFOV ? 1 : 0, sh_scan, nv);
+  const int xc = block_excl_scan<kMpThreads>(nC, sh_scan, accC);
+  const int xs = block_excl_scan<kMpThreads>(nS, sh_scan, accS);
+  int* vp = w.vpre + (size_t)p * (kMaxValid + 1) * 2;
+  if (inFOV) {
+    w.valid[(size_t)p * kMaxValid + xv] = ind;
+    vp[xv * 2 + 0] = xc;
+    vp[xv * 2 + 1] = xs;
+  }
+  if (tid == 0) {
+    if (accC + accS > s.map_cap) {  // (k_mp_prepare's guard; a valid store never holds more)
+      ist[kMiErr] |= ERR_CAP_MAP;
+      accC = accS = 0;
+      nv = 0;
+    }
+    vp[nv * 2 + 0] = accC;
+    vp[nv * 2 + 1] = accS;
+    ist[kMiNValid] = nv;
+    w.nfrom[p * 2 + 0] = accC;
+    w.nfrom[p * 2 + 1] = accS;
+    head[p * 2 + 0] = accC;
+    head[p * 2 + 1] = accS;
+  }
+}
+
+// FromMap of every candidate (blockIdx.y) from the shared pool: its valid cubes' corner points,
+// then their surf points, cubes in valid order and points in store order (k_mp_gather's order).
+// The candidate's runs (2 per valid cube: output offset, pool offset) are held in LDS; output
+// point i finds its run by a fixed-step search (as k_mp_map_pack), four points per lane with all
+// four loads issued before the stores, the stores fully coalesced.  The shared cubes are read by
+// many candidates (L2).
+constexpr int kLocRuns = 256;  // >= 2 * kMaxValid, a power of two (the search's steps)
+static_assert(kLocRuns >= 2 * kMaxValid, "a candidate's runs");
+__global__ __launch_bounds__(256) void k_mp_loc_gather(MpBuffers w, LocStore s) {
+  const int p = blockIdx.y, tid = threadIdx.x;
+  const int nv = w.istate[(size_t)p * kMpStateInts + kMiNValid];
+  const int* vp = w.vpre + (size_t)p * (kMaxValid + 1) * 2;
+  const int totC = vp[nv * 2 + 0], total = totC + vp[nv * 2 + 1];
+  if (total <= 0 || total > w.map_cap || blockIdx.x * 1024 >= total) return;  // (uniform)
+  __shared__ int off[kLocRuns], src[kLocRuns];
+  {  // run tid: kind tid / nv, valid cube tid % nv; beyond 2 nv: never chosen
+    const bool live = tid < 2 * nv;
+    const int kind = live && tid >= nv ? 1 : 0, c = live ? tid - kind * nv : 0;
+    const int ind = live ? w.valid[(size_t)p * kMaxValid + c] : 0;
+    off[tid] = live ? kind * totC + vp[c * 2 + kind] : 0x7fffffff;
+    src[tid] = live ? s.slots[ind * 4 + 2 * kind] : 0;
+  }
+  __syncthreads();
+  float4* dst = w.from + (size_t)p * w.map_cap;
+  for (int base = blockIdx.x * 1024; base < total; base += gridDim.x * 1024) {
+    // the pool index of output point i (clamped: the lanes past the end load a valid point)
+    auto locate = [&](int i) {
+      i = min(i, total - 1);
+      int lo = 0;  // the last run whose offset is <= i (an empty run never is the last such)
+#pragma unroll
+      for (int step = kLocRuns / 2; step > 0; step >>= 1)
+        if (off[lo + step] <= i) lo += step;
+      return src[lo] + (i - off[lo]);
+    };
+    const int i0 = base + tid, i1 = i0 + 256, i2 = i0 + 512, i3 = i0 + 768;
+    const int a0 = locate(i0), a1 = locate(i1), a2 = locate(i2), a3 = locate(i3);
+    const float4 v0 = s.pool[a0], v1 = s.pool[a1], v2 = s.pool[a2], v3 = s.pool[a3];
+    if (i0 < total) dst[i0] = v0;
+    if (i1 < total) dst[i1] = v1;
+    if (i2 < total) dst[i2] = v2;
+    if (i3 < total) dst[i3] = v3;
   }
 }
 
@@ -1342,6 +1476,7 @@ __global__ void k_mp_lm_begin(MpBuffers b) {
   ist[kMiStop] = 0;
   ist[kMiIters] = 0;
   ist[kMiRows] = 0;
+  ist[kMiRowsLast] = 0;
   ist[kMiFits] = 0;
   ist[kMiDegSteps] = 0;
   ist[kMiNnCand] = 0;
@@ -1657,6 +1792,7 @@ LOAM_D void mp_step(const MpBuffers& b, int p, const double* tot, MpStepScratch&
   if (lane != 0) return;
   ist[kMiIters] = iter + 1;
   ist[kMiRows] = c_rows + nrows;
+  ist[kMiRowsLast] = nrows;
   if (solve) {
     ist[kMiDegen] = degen;
     if (degen) ist[kMiDegSteps] = c_deg + 1;
@@ -2846,17 +2982,12 @@ void mp_wait_update(MpBuffers& b, hipStream_t st) {
   b.upd_pending = false;
 }
 
-void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof, bool map_empty,
-              const std::function<void()>& before_register, int stack_max, const SideStream* side,
-              hipStream_t defer) {
-  const int P = b.P;
-  auto mark = [&](const char* n) { if (prof) prof->mark(n); };
-  mp_wait_update(b, st);  // (the previous frame's map update, when it was deferred)
-  hipLaunchKernelGGL(k_mp_prepare, dim3(P), dim3(kMpThreads), 0, st, b, in);
-  mark("k_mp_prepare");
-  hipLaunchKernelGGL(k_mp_stack, dim3(16, P), dim3(256), 0, st, b, in);
-  mark("k_mp_stack");
-  if (side && side->inputs_read) b.note(hipEventRecord(side->inputs_read, st));  // (in.corner / in.surf read)
+namespace {
+// The middle of a mapping frame, shared by mp_frame and the localization (mp_localize_solve), for
+// the P instances of b: the stack VoxelGrid, the FromMap hash builds, the L-M loop.
+
+// the stacks' VoxelGrid (:693-701) on vs (k_mp_stack zeroed the cascade's list counters)
+void mp_stack_vg(MpBuffers& b, int P, hipStream_t vs, int stack_max) {
   VgJob js = vg_job(b);
   js.in = b.stack2; js.out = b.stack; js.begin = b.sseg_b; js.end = b.sseg_e; js.leaf = b.sseg_leaf;
   js.out_count = b.sseg_cnt; js.nseg = 2 * P; js.total = P * b.cap_stack;
@@ -2866,24 +2997,16 @@ void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof, bool 
   js.zeroed = true;
   // (the cascade's first kernel takes 12288 points for a few instances, 2048 for batches)
   const bool fits = stack_max >= 0 && stack_max <= (P <= 4 ? 12288 : 2048);
-  // batches: the corner stacks (<= 120 points per ring) take the 2048-point kernel, the surf
-  // stacks the 12288-point one; a few instances: one 12288-point launch.  With a side stream it
-  // runs there, beside the FromMap gather and the map hash builds (which read only the store)
-  const bool fork = side && side->st && !prof && !map_empty;
-  if (fork) {
-    b.note(hipEventRecord(side->fork[0], st));
-    b.note(hipStreamWaitEvent(side->st, side->fork[0], 0));
-  }
   // (vg_split 1: the split takes the segments beyond the first kernel when a sweep can fill several
   // LDS-tier segments (HDL-64E: 64 problems 0.56 -> 0.49 ms/step), else only those beyond the LDS
   // kernels (VLP-16 at 128 / 1024 problems: splitting beyond the first kernel 0.24 -> 0.32 ms/step))
   const bool split_early = b.tune.vg_split == 3 || (b.tune.vg_split == 1 && b.capS > 4 * 16384);
-  b.note(vg_run<kVgStack>(js, fork ? side->st : st, P <= 4 ? 12288 : 2048, !fits, /*tier2_idx=*/true,
+  b.note(vg_run<kVgStack>(js, vs, P <= 4 ? 12288 : 2048, !fits, /*tier2_idx=*/true,
                           b.tune.vg_split ? &b.vgs : nullptr, split_early));
-  if (fork) b.note(hipEventRecord(side->join[0], side->st));
-  mark("vg_stack");
-  hipLaunchKernelGGL(k_mp_gather, dim3(32, P), dim3(256), 0, st, b);
-  mark("k_mp_gather");
+}
+
+// the 1 m voxel hashes of FromMap's corner and surf parts
+void mp_hash_from(MpBuffers& b, int P, hipStream_t st, bool spread = false) {
   HashJob hc;
   hc.pts = b.from; hc.pts_stride = b.map_cap; hc.pts_off = nullptr; hc.pts_off_stride = 0;
   hc.count = b.nfrom; hc.count_stride_bytes = 2 * sizeof(int);
@@ -2897,16 +3020,20 @@ void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof, bool 
   hs.pts_off = b.nfrom; hs.pts_off_stride = 2;
   hs.count = b.nfrom + 1; hs.start = b.hS_start; hs.out = b.hS_pts; hs.tsize = b.hS_T;
   hs.fill = b.h_fill + (size_t)P * b.tmax;  // (the two indexes are built in one launch / concurrently)
-  hash_build_pair(hc, hs, P, st, false);
-  mark("k_hash_build_map");
-  if (fork) b.note(hipStreamWaitEvent(st, side->join[0], 0));
+  hash_build_pair(hc, hs, P, st, false, spread);
+}
+
+// k_mp_lm_begin, the iterations, k_mp_lm_end; persist: one instance may take the persistent launch
+// (tuning mp_persist)
+void mp_lm_loop(MpBuffers& b, int P, hipStream_t st, Prof* prof, bool map_empty, bool persist) {
+  auto mark = [&](const char* n) { if (prof) prof->mark(n); };
   hipLaunchKernelGGL(k_mp_lm_begin, dim3((P + 255) / 256), dim3(256), 0, st, b);
   // workgroups per instance: all the stack's queries at once for a few instances; for large
   // batches about one pass over a VLP-16 stack (bigger stacks loop), fewer idle workgroups
   const int gq = std::min(P >= 64 ? 24 : 64, (b.cap_stack + kMpQueryThreads - 1) / kMpQueryThreads);
   // an empty map store (the first frame after a reset) cannot run the L-M (:706): no launches
   // one instance (streaming): the whole L-M loop as one persistent launch (tuning mp_persist)
-  const int gls = P == 1 && !map_empty && b.tune.mp_persist ? mp_lm_stream_grid() : 0;
+  const int gls = persist && P == 1 && !map_empty && b.tune.mp_persist ? mp_lm_stream_grid() : 0;
   if (gls > 0) {
     hipLaunchKernelGGL(k_mp_lm_stream, dim3(gls), dim3(kMpQueryThreads), 0, st, b);
     mark("k_mp_lm_stream");
@@ -2935,6 +3062,36 @@ void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof, bool 
     }
   }
   hipLaunchKernelGGL(k_mp_lm_end, dim3((P + 255) / 256), dim3(256), 0, st, b);
+}
+}  // namespace
+
+void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof, bool map_empty,
+              const std::function<void()>& before_register, int stack_max, const SideStream* side,
+              hipStream_t defer) {
+  const int P = b.P;
+  auto mark = [&](const char* n) { if (prof) prof->mark(n); };
+  mp_wait_update(b, st);  // (the previous frame's map update, when it was deferred)
+  hipLaunchKernelGGL(k_mp_prepare, dim3(P), dim3(kMpThreads), 0, st, b, in);
+  mark("k_mp_prepare");
+  hipLaunchKernelGGL(k_mp_stack, dim3(16, P), dim3(256), 0, st, b, in);
+  mark("k_mp_stack");
+  if (side && side->inputs_read) b.note(hipEventRecord(side->inputs_read, st));  // (in.corner / in.surf read)
+  // the stack VoxelGrid: with a side stream it runs there, beside the FromMap gather and the map
+  // hash builds (which read only the store)
+  const bool fork = side && side->st && !prof && !map_empty;
+  if (fork) {
+    b.note(hipEventRecord(side->fork[0], st));
+    b.note(hipStreamWaitEvent(side->st, side->fork[0], 0));
+  }
+  mp_stack_vg(b, P, fork ? side->st : st, stack_max);
+  if (fork) b.note(hipEventRecord(side->join[0], side->st));
+  mark("vg_stack");
+  hipLaunchKernelGGL(k_mp_gather, dim3(32, P), dim3(256), 0, st, b);
+  mark("k_mp_gather");
+  mp_hash_from(b, P, st);
+  mark("k_hash_build_map");
+  if (fork) b.note(hipStreamWaitEvent(st, side->join[0], 0));
+  mp_lm_loop(b, P, st, prof, map_empty, /*persist=*/true);
   // the registration reads only the final pose and the full cloud: beside the insertion with a
   // side stream (the batch: no before_register hook)
   const bool reg_side = fork && !before_register && !defer;
@@ -3685,6 +3842,223 @@ hipError_t mp_map_install(MpBuffers& b, MapIo& io, int kept, const int* cen, con
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess) b.pool_cur = 1 - b.pool_cur;
   return e;
+}
+
+// ---------------------------------------------------------------- localization: host side
+namespace {
+// a candidate's result block (kLr* words): what a mapping frame at this candidate would return in
+// aft (k_mp_lm_end left it in the state; untouched without an L-M) and report in its statistics
+__global__ void k_mp_loc_result(MpBuffers w, int* res) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= w.P) return;
+  const int* ist = w.istate + (size_t)p * kMpStateInts;
+  const float* st = w.state + (size_t)p * kMpStateFloats;
+  int* r = res + (size_t)p * kLocResWords;
+  const bool off = ist[kMiLocOff] != 0, ran = ist[kMiLmRan] != 0;
+  for (int k = 0; k < 6; ++k) r[kLrAft + k] = __float_as_int(st[kMpAft + k]);
+  r[kLrStatus] = off ? 2 : (ran ? 0 : 1);  // LOAM_LOC_OFFGRID / SOLVED / NO_LM
+  r[kLrIters] = ist[kMiIters];
+  r[kLrDegSteps] = ist[kMiDegSteps];
+  r[kLrRowsLast] = ist[kMiRowsLast];
+  r[kLrRowsSum] = ist[kMiRows];
+  r[kLrStackC] = off ? 0 : ist[kMiStackC];
+  r[kLrStackS] = off ? 0 : ist[kMiStackS];
+  r[kLrMapC] = ist[kMiFromC];
+  r[kLrMapS] = ist[kMiFromS];
+}
+
+LocStore loc_store(const MpBuffers& s) {
+  LocStore v;
+  v.slots = s.slots + (size_t)s.pool_cur * s.P * kCubeNum * 4;
+  v.pool = s.pool + (size_t)s.pool_cur * s.P * s.map_cap;
+  v.istate = s.istate;
+  v.map_cap = s.map_cap;
+  return v;
+}
+
+void loc_free_map(MpBuffers& w) {
+  void* ptrs[] = {w.from, w.hC_start, w.hS_start, w.hC_rec, w.hS_rec, w.h_fill, w.hC_pts, w.hS_pts};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  w.from = w.hC_pts = w.hS_pts = nullptr;
+  w.hC_start = w.hS_start = w.h_fill = nullptr;
+  w.hC_rec = w.hS_rec = nullptr;
+  w.map_cap = w.tmax = 0;
+}
+}  // namespace
+
+void mp_loc_free(MpLoc& L) {
+  mp_free(L.w);
+  if (L.cand) (void)hipFree(L.cand);
+  if (L.head) (void)hipFree(L.head);
+  if (L.res) (void)hipFree(L.res);
+  if (L.pin) (void)hipHostFree(L.pin);
+  L = MpLoc();
+}
+
+hipError_t mp_loc_reserve(MpLoc& L, const MpBuffers& s, int n, int ncorner, int nsurf) {
+  if (!L.pin) {
+    DevAlloc A;
+    A(&L.cand, (size_t)kLocMax * 12 * sizeof(float));
+    A(&L.head, (size_t)(2 * kLocMax + 4) * sizeof(int));
+    A(&L.res, (size_t)kLocMax * kLocResWords * sizeof(int));
+    if (A.err == hipSuccess)
+      A.err = hipHostMalloc((void**)&L.pin, (size_t)kLocMax * (12 + 2 + kLocResWords) * 4 + 16, hipHostMallocDefault);
+    if (A.err != hipSuccess) {
+      mp_loc_free(L);
+      return A.err;
+    }
+  }
+  MpBuffers& w = L.w;
+  w.tune = s.tune;
+  w.max_iter = s.max_iter;
+  // the stacks hold the sweep given, not the context's max_points (193 B per stack point and
+  // candidate): its counts rounded up, at most the store's own capacities
+  const int needC = std::min(s.capC, (std::max(ncorner, 1) + 511) / 512 * 512);
+  const int needS = std::min(s.capS, (std::max(nsurf, 1) + 4095) / 4096 * 4096);
+  if (n <= L.cap_n && needC <= w.capC && needS <= w.capS) return hipSuccess;
+  const int capC = std::max(needC, w.capC), capS = std::max(needS, w.capS), cap_stack = capC + capS;
+  // the stacks' segment bases and the VoxelGrid job's size are ints over all the candidates
+  if ((size_t)n * cap_stack > (size_t)0x7fffffff) return hipErrorOutOfMemory;
+  const int P = std::max(L.cap_n, n <= 4 ? 4 : std::min(kLocMax, next_pow2(n)));
+  const int Pc = (size_t)P * cap_stack > (size_t)0x7fffffff ? std::max(n, L.cap_n) : P;
+  mp_free(w);
+  L.cap_n = L.from_cap = 0;
+  DevAlloc A;
+  w.P = Pc;
+  w.capC = capC; w.capS = capS; w.cap_stack = cap_stack;
+  w.max_iter = s.max_iter;
+  w.tune = s.tune;
+  const size_t Ps = (size_t)Pc * w.cap_stack;
+  A(&w.state, (size_t)Pc * kMpStateFloats * sizeof(float));
+  A(&w.istate, (size_t)Pc * kMpStateInts * sizeof(int));
+  A(&w.valid, (size_t)Pc * kMaxValid * sizeof(int));
+  A(&w.vpre, (size_t)Pc * (kMaxValid + 1) * 2 * sizeof(int));
+  A(&w.nfrom, (size_t)Pc * 2 * sizeof(int));
+  A(&w.hC_T, (size_t)Pc * sizeof(int));
+  A(&w.hS_T, (size_t)Pc * sizeof(int));
+  // the sweep's two clouds, once for every candidate
+  A(&w.inC, (size_t)w.capC * sizeof(float4));
+  A(&w.inS, (size_t)w.capS * sizeof(float4));
+  A(&w.in_n, 3 * sizeof(int));
+  A(&w.in_pose, 6 * sizeof(float));
+  A(&w.stack2, Ps * sizeof(float4));
+  A(&w.stack, Ps * sizeof(float4));
+  A(&w.sseg_b, (size_t)Pc * 2 * sizeof(int));
+  A(&w.sseg_e, (size_t)Pc * 2 * sizeof(int));
+  A(&w.sseg_cnt, (size_t)Pc * 2 * sizeof(int));
+  A(&w.sseg_leaf, (size_t)Pc * 2 * sizeof(float));
+  A(&w.vg_k, Ps * sizeof(uint32_t));
+  A(&w.vg_k2, Ps * sizeof(uint32_t));
+  A(&w.vg_v, Ps * sizeof(uint32_t));
+  A(&w.vg_v2, Ps * sizeof(uint32_t));
+  A(&w.vg_l0, (size_t)Pc * 2 * sizeof(int));
+  A(&w.vg_l1, (size_t)Pc * 2 * sizeof(int));
+  A(&w.vg_cnt, 4 * sizeof(int));
+  w.vgs.npar = 2 * Pc;
+  A(&w.vgs.pts, Ps * sizeof(float4));
+  A(&w.vgs.out, Ps * sizeof(float4));
+  A(&w.vgs.begin, (size_t)Pc * 32 * sizeof(int));
+  A(&w.vgs.end, (size_t)Pc * 32 * sizeof(int));
+  A(&w.vgs.out_count, (size_t)Pc * 32 * sizeof(int));
+  A(&w.vgs.leaf, (size_t)Pc * 32 * sizeof(float));
+  A(&w.vgs.frame, (size_t)Pc * 32 * sizeof(VgFrame));
+  A(&w.vgs.lists[0], (size_t)Pc * 32 * sizeof(int));
+  A(&w.vgs.lists[1], (size_t)Pc * 32 * sizeof(int));
+  A(&w.vgs.counts, 4 * sizeof(int));
+  A(&w.vgs.ilist, (size_t)Pc * 32 * sizeof(int));
+  A(&w.q_ok, Ps * sizeof(int8_t));
+  A(&w.q_cf, Ps * sizeof(float4));
+  A(&w.q_nn, Ps * 2 * sizeof(int4));
+  A(&w.q_fit, Ps * 4 * sizeof(float4));
+  A(&w.part, (size_t)Pc * std::max(kMpSmallGrid, kMpFitGridMax) * 28 * sizeof(double));
+  A(&w.rot, (size_t)Pc * 6 * sizeof(double));
+  A(&w.done, (size_t)Pc * sizeof(int));
+  A(&w.ls_epoch, sizeof(unsigned long long));  // (k_mp_lm_begin advances it for one instance)
+  if (A.err == hipSuccess) A.err = hipMemset(w.state, 0, (size_t)Pc * kMpStateFloats * sizeof(float));
+  if (A.err == hipSuccess) A.err = hipMemset(w.istate, 0, (size_t)Pc * kMpStateInts * sizeof(int));
+  if (A.err == hipSuccess) A.err = hipMemset(w.done, 0, (size_t)Pc * sizeof(int));
+  if (A.err == hipSuccess) A.err = hipMemset(w.ls_epoch, 0, sizeof(unsigned long long));
+  if (A.err != hipSuccess) {
+    mp_free(w);
+    return A.err;
+  }
+  L.cap_n = Pc;
+  return hipSuccess;
+}
+
+hipError_t mp_loc_reserve_map(MpLoc& L, int from_max) {
+  MpBuffers& w = L.w;
+  if (from_max <= L.from_cap) return hipSuccess;
+  loc_free_map(w);
+  L.from_cap = 0;
+  // a quarter more than asked, in steps of 4096 points: later calls seldom reallocate
+  const size_t want = ((size_t)from_max + from_max / 4 + 4095) / 4096 * 4096;
+  const int cap = (int)std::min<size_t>(want, (size_t)1 << 28);  // (a FromMap never exceeds map_capacity <= 2^28)
+  DevAlloc A;
+  const int P = L.cap_n;
+  w.map_cap = cap;
+  w.tmax = next_pow2(cap) > (1 << 20) ? (1 << 20) : next_pow2(cap);
+  if (w.tmax < 64) w.tmax = 64;
+  const size_t Pm = (size_t)P * cap;
+  A(&w.from, Pm * sizeof(float4));
+  A(&w.hC_pts, Pm * sizeof(float4));
+  A(&w.hS_pts, Pm * sizeof(float4));
+  A(&w.hC_start, (size_t)P * (w.tmax + 1) * sizeof(int));
+  A(&w.hS_start, (size_t)P * (w.tmax + 1) * sizeof(int));
+  A(&w.hC_rec, (size_t)P * w.tmax * sizeof(uint32_t));
+  A(&w.hS_rec, (size_t)P * w.tmax * sizeof(uint32_t));
+  A(&w.h_fill, (size_t)2 * P * w.tmax * sizeof(int));
+  if (A.err != hipSuccess) {
+    loc_free_map(w);
+    return A.err;
+  }
+  L.from_cap = cap;
+  return hipSuccess;
+}
+
+hipError_t mp_localize_prepare(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, hipStream_t st, Prof* prof) {
+  MpBuffers& w = L.w;
+  w.P = n;
+  hipError_t e = hipMemcpyAsync(L.cand, L.cand_h(), (size_t)n * 12 * sizeof(float), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_mp_loc_prepare, dim3(n), dim3(kMpThreads), 0, st, w, in, loc_store(s), L.cand, L.head);
+  if (prof) prof->mark("k_mp_loc_prepare");
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return hipMemcpyAsync(L.head_h(), L.head, (size_t)(2 * n + 1) * sizeof(int), hipMemcpyDeviceToHost, st);
+}
+
+hipError_t mp_localize_solve(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, int from_max, int cloud_max,
+                             int stack_max, hipStream_t st, Prof* prof) {
+  MpBuffers& w = L.w;
+  w.P = n;
+  auto mark = [&](const char* name) { if (prof) prof->mark(name); };
+  hipLaunchKernelGGL(k_mp_stack, dim3(16, n), dim3(256), 0, st, w, in);
+  mark("k_mp_stack");
+  mp_stack_vg(w, n, st, stack_max);
+  mark("vg_stack");
+  const bool map_empty = from_max == 0;  // no candidate can run the L-M (:706): nothing to gather or hash
+  if (!map_empty) {
+    // about 2048 workgroups over all the candidates, each looping over its candidate's 1024-point tiles
+    const int tiles = (from_max + 1023) / 1024;
+    const int gx = std::max(1, std::min(tiles, (2048 + n - 1) / n));
+    hipLaunchKernelGGL(k_mp_loc_gather, dim3(gx, n), dim3(256), 0, st, w, loc_store(s));
+    mark("k_mp_loc_gather");
+    // a cloud beyond k_hash_build's 8192 LDS counters is a long global-atomic counting sort in its one
+    // workgroup: the grid per cloud instead (1024 candidates of 8.7 k + 25 k points: 9.2 -> 3.9 ms, 64:
+    // 0.47 -> 0.29; clouds inside the LDS counters are slower that way: 0.10 -> 0.68 ms at 1024)
+    mp_hash_from(w, n, st, /*spread=*/cloud_max > 8192);
+    mark("k_hash_build_map");
+  }
+  // (never the persistent one-instance L-M: it spin-waits between its workgroups)
+  mp_lm_loop(w, n, st, prof, map_empty, /*persist=*/false);
+  hipLaunchKernelGGL(k_mp_loc_result, dim3((n + 255) / 256), dim3(256), 0, st, w, L.res);
+  mark("k_mp_loc_result");
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = w.take_error();
+  if (e != hipSuccess) return e;
+  return hipMemcpyAsync(L.res_h(), L.res, (size_t)n * kLocResWords * sizeof(int), hipMemcpyDeviceToHost, st);
 }
 
 // frame 1 of the batch problem: reset, then prev (the seed's Last[buf]) into the empty store at

@@ -28,8 +28,10 @@ enum { kMiCenW = 0, kMiCenH, kMiCenD, kMiDegen, kMiNValid, kMiIters, kMiRows, kM
        kMiShifts,    // cube-grid slab shifts of this frame's recentring (the reference's passes)
        kMiNnCand,    // map points the 5-NN evaluated this frame (seeds included)
        kMiNnCells,   // hash bucket ranges the 5-NN read this frame
+       kMiRowsLast,  // rows of the last L-M iteration evaluated (mp_step; the persistent streaming L-M keeps no such count)
+       kMiLocOff,    // loam_map_localize: the candidate's centre cube is within 3 of a grid edge (not evaluated)
        kMpStateInts = 28 };
-static_assert(kMiNnCells < kMpStateInts, "istate layout");
+static_assert(kMiLocOff < kMpStateInts, "istate layout");
 
 // one mapping frame's inputs for every instance (device pointers)
 struct MpInput {
@@ -273,6 +275,45 @@ hipError_t mp_map_bin_result(MapIo& io, hipStream_t st);
 // centre and the Bef / Aft poses (pose12: aft then bef); on success the store switches to that pool
 hipError_t mp_map_install(MpBuffers& b, MapIo& io, int kept, const int* cen, const float* pose12, hipStream_t st,
                           Prof* prof);
+
+// ---- multi-hypothesis localization in a streaming store (loam_map_localize) ----
+// n candidate (Aft, Bef) poses, one sweep: each candidate's laserMapping L-M against the store of `s`
+// (instance 0), which is only read.  The candidates are the instances of a working set `w` (an
+// MpBuffers whose pools, cube VoxelGrid, insertion and registration buffers stay unallocated: P =
+// the candidates, map_cap = the largest FromMap of a candidate); the sweep's two clouds are held
+// once and read by every candidate.
+constexpr int kLocMax = 1024;      // LOAM_LOCALIZE_MAX
+constexpr int kLocResWords = 16;   // a candidate's result block (k_mp_loc_result)
+enum { kLrAft = 0, kLrStatus = 6, kLrIters, kLrDegSteps, kLrRowsLast, kLrRowsSum, kLrStackC, kLrStackS, kLrMapC,
+       kLrMapS };
+static_assert(kLrMapS < kLocResWords, "result block");
+struct MpLoc {
+  MpBuffers w;            // the working set (w.P: the candidates of the current call)
+  int cap_n = 0;          // candidates it holds
+  int from_cap = 0;       // FromMap points per candidate it holds (w.map_cap)
+  float* cand = nullptr;  // device [kLocMax][12]: aft, bef of every candidate
+  int* head = nullptr;    // device [2 * kLocMax + 4]: every candidate's FromMap counts (corner, surf), then the store's error word
+  int* res = nullptr;     // device [kLocMax][kLocResWords]
+  char* pin = nullptr;    // pinned host copies of cand | head | res
+  float* cand_h() const { return (float*)pin; }
+  int* head_h() const { return (int*)(pin + (size_t)kLocMax * 12 * 4); }
+  int* res_h() const { return head_h() + 2 * kLocMax + 4; }
+};
+void mp_loc_free(MpLoc& L);
+// the candidate tables and, for n candidates and a sweep of ncorner + nsurf points, the working set's
+// per-candidate part (stacks sized by the sweep's counts rounded up, L-M state); grows, never
+// shrinks.  On an allocation failure the working set is freed
+hipError_t mp_loc_reserve(MpLoc& L, const MpBuffers& s, int n, int ncorner, int nsurf);
+// the FromMap part (from, the two hash indexes) for from_max points per candidate
+hipError_t mp_loc_reserve_map(MpLoc& L, int from_max);
+// k_mp_loc_prepare for n candidates (L.cand) on the sweep `in` (strides 0) + the counts into
+// L.head_h(); the caller synchronises st, then reads them
+hipError_t mp_localize_prepare(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, hipStream_t st, Prof* prof);
+// the stacks, the FromMap gather (from_max > 0), the hash builds, the L-M and the result blocks
+// into L.res_h(); the caller synchronises st, then reads them.  from_max: the largest FromMap of a
+// candidate, cloud_max: its largest corner or surf part; stack_max as mp_frame's
+hipError_t mp_localize_solve(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, int from_max, int cloud_max,
+                             int stack_max, hipStream_t st, Prof* prof);
 
 }  // namespace loam
 #endif

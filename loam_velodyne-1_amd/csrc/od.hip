@@ -350,8 +350,8 @@ __global__ __launch_bounds__(256) void k_hash_scatter(HashPair hp) {
   }
 }
 
-void hash_build_pair(const HashJob& a, const HashJob& b, int P, hipStream_t st, bool wide) {
-  if (P > 4) {  // batches: a workgroup per cloud fills the chip
+void hash_build_pair(const HashJob& a, const HashJob& b, int P, hipStream_t st, bool wide, bool spread) {
+  if (P > 4 && !spread) {  // batches: a workgroup per cloud fills the chip
     HashPair hp;
     hp.j[0] = a;
     hp.j[1] = b;

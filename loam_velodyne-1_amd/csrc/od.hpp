@@ -139,7 +139,9 @@ struct OdBuffers {
 // both clouds' indexes: a workgroup per cloud for batches, a grid per cloud for P <= 4
 // wide: 1024-thread workgroups (the odometry Last clouds: 0.28 -> 0.19 ms/step at batch 1024), else
 // 512 (the map clouds: 0.27 -> 0.26; 1024 measured 0.31)
-void hash_build_pair(const HashJob& a, const HashJob& b, int P, hipStream_t st, bool wide);
+// spread: the grid per cloud for any P (many large clouds: loam_map_localize's FromMap beyond the LDS
+// counters, where a cloud's single workgroup is a long global-atomic counting sort)
+void hash_build_pair(const HashJob& a, const HashJob& b, int P, hipStream_t st, bool wide, bool spread = false);
 
 __global__ void k_od_end(OdBuffers b, FeatView f, int dst, int mode, int do_full);
 
