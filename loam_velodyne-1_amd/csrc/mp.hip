@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "dev_common.hpp"
+#include "dev_hooks.h"
 #include "mp.hpp"
 #include "od.hpp"
 #include "pose_math.hpp"
@@ -965,6 +966,11 @@ __global__ __launch_bounds__(NT) void k_vg_join(VgJob j, VgSplit x) {
 // LDS tiers measured faster than the merge on 2k-12k segments)
 // (Tuning::vg_merge_min: 12288 by default, the largest LDS tier)
 constexpr int kVgMergeNew = 8192;
+// a cube segment of n points whose first nold are its previous VoxelGrid output goes on the merge list
+// (k_mp_vseg; the diagnostic hook loam_dev_vg_run)
+LOAM_HD bool vg_merge_eligible(int n, int nold, int merge_min) {
+  return n > merge_min && nold > 0 && n - nold <= kVgMergeNew;
+}
 template <int NT, int NEW>
 __global__ __launch_bounds__(NT) void k_vg_merge(VgJob j) {
   static_assert((NEW & (NEW - 1)) == 0 && NEW % NT == 0 && NEW <= 65536, "bitonic sort / scan layout");
@@ -1202,6 +1208,40 @@ VgJob vg_job(const MpBuffers& b) {
   j.lists[0] = b.vg_l0; j.lists[1] = b.vg_l1; j.counts = b.vg_cnt;
   return j;
 }
+
+// The three VoxelGrid routes: which cascade a job takes, from the decision inputs the product has.
+// The product's call sites and the diagnostic hook (loam_dev_vg_run) both go through these.
+
+// the stacks (:693-701), P instances: two large segments per instance (the fused 12288-point kernel
+// for a few instances, the 2048-point one for batches); when the host knows every segment fits the
+// first kernel (stack_max >= 0: streaming), the cascade's finish is not enqueued
+hipError_t vg_route_stack(const VgJob& js, hipStream_t st, int P, int stack_max, int vg_split, int capS,
+                          const VgSplit* vgs) {
+  const bool fits = stack_max >= 0 && stack_max <= (P <= 4 ? 12288 : 2048);
+  // (vg_split 1: the split takes the segments beyond the first kernel when a sweep can fill several
+  // LDS-tier segments (HDL-64E: 64 problems 0.56 -> 0.49 ms/step), else only those beyond the LDS
+  // kernels (VLP-16 at 128 / 1024 problems: splitting beyond the first kernel 0.24 -> 0.32 ms/step))
+  const bool split_early = vg_split == 3 || (vg_split == 1 && capS > 4 * 16384);
+  return vg_run<kVgStack>(js, st, P <= 4 ? 12288 : 2048, !fits, /*tier2_idx=*/true, vg_split ? vgs : nullptr,
+                          split_early);
+}
+
+// the valid cubes (:1018-1036), P instances: with vg_merge the long segments with a short tail first
+// (k_vg_merge over mlist, which sets skip), the rest by the cascade.  Most of the 2 x 125 cube
+// segments per instance are small: batches start with the 2048-point kernel (many workgroups per
+// CU); a few instances with the 12288-point one (one launch)
+hipError_t vg_route_cubes(VgJob jv, hipStream_t st, int P, int vg_merge, const int* nold, const int* mlist,
+                          const int* mlist_n, int* skip) {
+  if (vg_merge) {
+    jv.nold = nold; jv.mlist = mlist; jv.mlist_n = mlist_n; jv.skip = skip;
+    // (its segments are rare: a small grid whose workgroups leave at once when the list is short)
+    hipLaunchKernelGGL((k_vg_merge<1024, kVgMergeNew>), dim3(std::min(jv.nseg, 32)), dim3(1024), 0, st, jv);
+  }
+  return vg_run<kVgCubes>(jv, st, P <= 4 ? 12288 : 2048);
+}
+
+// the surround map (:1042-1047): one segment
+hipError_t vg_route_surround(const VgJob& j, hipStream_t st) { return vg_run<kVgSurround>(j, st, 12288); }
 
 // ---------------------------------------------------------------- FromMap gather
 __global__ __launch_bounds__(256) void k_mp_gather(MpBuffers b) {
@@ -2648,7 +2688,7 @@ __global__ __launch_bounds__(kMpThreads) void k_mp_vseg(MpBuffers b) {
     } else {
       b.vg_lin[atomicAdd(b.vg_cnt + 2, 1)] = sidx;
       // long segments with a short appended tail: the incremental VoxelGrid may take them
-      if (b.tune.vg_merge && n > b.tune.vg_merge_min && nold > 0 && n - nold <= kVgMergeNew)
+      if (b.tune.vg_merge && vg_merge_eligible(n, nold, b.tune.vg_merge_min))
         b.vg_mlist[atomicAdd(b.vg_cnt + 3, 1)] = sidx;
     }
   }
@@ -2995,14 +3035,7 @@ void mp_stack_vg(MpBuffers& b, int P, hipStream_t vs, int stack_max) {
   // (streaming), the cascade's finish is not enqueued
   // (k_mp_stack zeroed the cascade's list counters)
   js.zeroed = true;
-  // (the cascade's first kernel takes 12288 points for a few instances, 2048 for batches)
-  const bool fits = stack_max >= 0 && stack_max <= (P <= 4 ? 12288 : 2048);
-  // (vg_split 1: the split takes the segments beyond the first kernel when a sweep can fill several
-  // LDS-tier segments (HDL-64E: 64 problems 0.56 -> 0.49 ms/step), else only those beyond the LDS
-  // kernels (VLP-16 at 128 / 1024 problems: splitting beyond the first kernel 0.24 -> 0.32 ms/step))
-  const bool split_early = b.tune.vg_split == 3 || (b.tune.vg_split == 1 && b.capS > 4 * 16384);
-  b.note(vg_run<kVgStack>(js, vs, P <= 4 ? 12288 : 2048, !fits, /*tier2_idx=*/true,
-                          b.tune.vg_split ? &b.vgs : nullptr, split_early));
+  b.note(vg_route_stack(js, vs, P, stack_max, b.tune.vg_split, b.capS, &b.vgs));
 }
 
 // the 1 m voxel hashes of FromMap's corner and surf parts
@@ -3123,14 +3156,7 @@ void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof, bool 
   jv.out_count = b.vseg_cnt; jv.nseg = 2 * kMaxValid * P; jv.total = P * b.map_cap;
   // only the non-empty segments, listed by k_mp_vseg (k_mp_lm_end zeroed the counters)
   jv.list = b.vg_lin; jv.list_n = b.vg_cnt + 2; jv.zeroed = true;
-  if (b.tune.vg_merge) {  // long cube segments with a short tail first (k_vg_merge), the rest by the cascade
-    jv.nold = b.vseg_nold; jv.mlist = b.vg_mlist; jv.mlist_n = b.vg_cnt + 3; jv.skip = b.vseg_skip;
-    // (its segments are rare: a small grid whose workgroups leave at once when the list is short)
-    hipLaunchKernelGGL((k_vg_merge<1024, kVgMergeNew>), dim3(std::min(2 * kMaxValid * P, 32)), dim3(1024), 0, us, jv);
-  }
-  // 2 x 125 cube segments per instance, most of them small: batches start with the 2048-point
-  // kernel (many workgroups per CU); a few instances with the 12288-point one (one launch)
-  b.note(vg_run<kVgCubes>(jv, us, P <= 4 ? 12288 : 2048));
+  b.note(vg_route_cubes(jv, us, P, b.tune.vg_merge, b.vseg_nold, b.vg_mlist, b.vg_cnt + 3, b.vseg_skip));
   mark("vg_cubes");
   hipLaunchKernelGGL(k_mp_compact_table<1024>, dim3(P), dim3(1024), 0, us, b);
   hipLaunchKernelGGL(k_mp_compact_copy, dim3(64, P), dim3(256), 0, us, b);
@@ -3381,7 +3407,7 @@ int mp_stream_surround(MpBuffers& b, hipStream_t st, loam_cloud_out* out, std::s
   j.in = b.vin; j.out = b.vout; j.begin = b.vseg_b; j.end = b.vseg_e; j.leaf = b.vseg_leaf;
   j.out_count = b.vseg_cnt; j.nseg = 1; j.total = b.P * b.map_cap;
   j.zeroed = true;  // (by k_mp_surround)
-  b.note(vg_run<kVgSurround>(j, st, 12288));
+  b.note(vg_route_surround(j, st));
   int cnt = 0;
   hipError_t he = hipMemcpyAsync(&cnt, b.vseg_cnt, sizeof(int), hipMemcpyDeviceToHost, st);
   if (he == hipSuccess) he = hipStreamSynchronize(st);
@@ -4153,3 +4179,170 @@ extern "C" int loam_debug_phases_mp(unsigned long long* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(loam::g_ph_mp), sizeof(PhaseAcc)) == hipSuccess ? 0 : -1;
 }
 #endif
+
+// ---------------------------------------------------------------- diagnostic hook (dev_hooks.h)
+// The VoxelGrid routes on caller-supplied segments (tests/test_gpu_voxelgrid.py): host code only,
+// the launches are vg_route_stack / vg_route_cubes / vg_route_surround's, the merge list is
+// vg_merge_eligible's.
+struct loam_dev_vg {
+  int device = 0, max_total = 0, max_seg = 0;
+  hipStream_t st = nullptr;
+  float4 *in = nullptr, *out = nullptr;
+  int *begin = nullptr, *end = nullptr, *out_count = nullptr;
+  float* leaf = nullptr;
+  uint32_t *k = nullptr, *k2 = nullptr, *v = nullptr, *v2 = nullptr;  // the four sort arrays
+  int *l0 = nullptr, *l1 = nullptr, *lin = nullptr, *mlist = nullptr;  // cascade, input and merge lists
+  int* cnt = nullptr;                                                  // [4] their lengths
+  int *nold = nullptr, *skip = nullptr;
+  loam::VgSplit vgs;
+};
+
+namespace {
+void dev_vg_free(loam_dev_vg* h) {
+  void* ptrs[] = {h->in, h->out, h->begin, h->end, h->out_count, h->leaf, h->k, h->k2, h->v, h->v2, h->l0, h->l1,
+                  h->lin, h->mlist, h->cnt, h->nold, h->skip, h->vgs.pts, h->vgs.out, h->vgs.begin, h->vgs.end,
+                  h->vgs.out_count, h->vgs.leaf, h->vgs.frame, h->vgs.lists[0], h->vgs.lists[1], h->vgs.counts,
+                  h->vgs.ilist};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  if (h->st) (void)hipStreamDestroy(h->st);
+  delete h;
+}
+}  // namespace
+
+extern "C" int loam_dev_vg_create(int device, int32_t max_total_points, int32_t max_segments, loam_dev_vg** out) {
+  if (!out) return LOAM_E_INVAL;
+  *out = nullptr;
+  if (max_total_points < 1 || max_segments < 1 || max_segments > (1 << 24)) return LOAM_E_INVAL;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return LOAM_E_HIP;  // (no CPU path, as loam_create)
+  if (device < 0 || device >= ndev) return LOAM_E_INVAL;
+  if (hipSetDevice(device) != hipSuccess) return LOAM_E_HIP;
+  loam_dev_vg* h = new loam_dev_vg();
+  h->device = device; h->max_total = max_total_points; h->max_seg = max_segments;
+  const size_t T = (size_t)max_total_points, S = (size_t)max_segments;
+  loam::DevAlloc A;
+  A(&h->in, T * sizeof(float4));
+  A(&h->out, T * sizeof(float4));
+  A(&h->begin, S * sizeof(int));
+  A(&h->end, S * sizeof(int));
+  A(&h->out_count, S * sizeof(int));
+  A(&h->leaf, S * sizeof(float));
+  A(&h->k, T * sizeof(uint32_t));
+  A(&h->k2, T * sizeof(uint32_t));
+  A(&h->v, T * sizeof(uint32_t));
+  A(&h->v2, T * sizeof(uint32_t));
+  A(&h->l0, S * sizeof(int));
+  A(&h->l1, S * sizeof(int));
+  A(&h->lin, S * sizeof(int));
+  A(&h->mlist, S * sizeof(int));
+  A(&h->cnt, 4 * sizeof(int));
+  A(&h->nold, S * sizeof(int));
+  A(&h->skip, S * sizeof(int));
+  // the split: every segment a parent, 16 sub-segments each (as mp_alloc's for the 2P stacks)
+  A(&h->vgs.pts, T * sizeof(float4));
+  A(&h->vgs.out, T * sizeof(float4));
+  A(&h->vgs.begin, S * 16 * sizeof(int));
+  A(&h->vgs.end, S * 16 * sizeof(int));
+  A(&h->vgs.out_count, S * 16 * sizeof(int));
+  A(&h->vgs.leaf, S * 16 * sizeof(float));
+  A(&h->vgs.frame, S * 16 * sizeof(loam::VgFrame));
+  A(&h->vgs.lists[0], S * 16 * sizeof(int));
+  A(&h->vgs.lists[1], S * 16 * sizeof(int));
+  A(&h->vgs.counts, 4 * sizeof(int));
+  A(&h->vgs.ilist, S * 16 * sizeof(int));
+  hipError_t e = A.err;
+  if (e == hipSuccess) e = hipStreamCreate(&h->st);
+  if (e != hipSuccess) {
+    dev_vg_free(h);
+    return e == hipErrorOutOfMemory ? LOAM_E_NOMEM : LOAM_E_HIP;
+  }
+  *out = h;
+  return LOAM_OK;
+}
+
+extern "C" int loam_dev_vg_run(loam_dev_vg* h, const loam_dev_vg_job* job, float* out_pts, int32_t* out_count,
+                               int32_t* merged) {
+  if (!h || !job || !out_pts || !out_count || !merged) return LOAM_E_INVAL;
+  const int n = job->nseg, total = job->total;
+  if (n < 1 || n > h->max_seg || total < 1 || total > h->max_total) return LOAM_E_INVAL;
+  if (!job->pts || !job->begin || !job->end || !job->leaf || job->P < 1) return LOAM_E_INVAL;
+  if (job->route < LOAM_DEV_VG_STACK || job->route > LOAM_DEV_VG_SURROUND) return LOAM_E_INVAL;
+  if (job->route == LOAM_DEV_VG_SURROUND && n != 1) return LOAM_E_INVAL;
+  if (job->vg_split < 0 || job->vg_split > 3 || job->vg_merge < 0 || job->vg_merge > 1 || job->vg_merge_min < 0)
+    return LOAM_E_INVAL;
+  int prev_end = 0;
+  for (int s = 0; s < n; ++s) {  // every segment inside [0, total), in ascending order, none overlapping
+    const int b0 = job->begin[s], b1 = job->end[s];
+    if (b0 < prev_end || b1 < b0 || b1 > total) return LOAM_E_INVAL;
+    if (!(job->leaf[s] > 0.0f) || !(job->leaf[s] < 3.0e38f)) return LOAM_E_INVAL;
+    if (job->nold && (job->nold[s] < 0 || job->nold[s] > b1 - b0)) return LOAM_E_INVAL;
+    prev_end = b1;
+  }
+  const bool cubes = job->route == LOAM_DEV_VG_CUBES, merge = cubes && job->vg_merge != 0;
+  // what k_mp_vseg leaves on the cube route: the non-empty segments listed, the merge candidates
+  // listed, count 0 for the empty ones, skip 0; elsewhere every count starts at -1
+  std::vector<int> lin, ml, cnt0((size_t)n, -1), nold((size_t)n, 0), zero((size_t)n, 0);
+  for (int s = 0; s < n; ++s) {
+    const int len = job->end[s] - job->begin[s];
+    if (job->nold) nold[s] = job->nold[s];
+    if (!cubes) continue;
+    if (len == 0) {
+      cnt0[s] = 0;
+      continue;
+    }
+    lin.push_back(s);
+    if (merge && loam::vg_merge_eligible(len, nold[s], job->vg_merge_min)) ml.push_back(s);
+  }
+  const int cnt4[4] = {0, 0, (int)lin.size(), (int)ml.size()};
+  hipStream_t st = h->st;
+  auto up = [&](void* d, const void* s, size_t bytes) {
+    return bytes ? hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+  };
+  hipError_t e = hipSetDevice(h->device);
+  if (e == hipSuccess) e = up(h->in, job->pts, (size_t)total * sizeof(float4));
+  if (e == hipSuccess) e = up(h->begin, job->begin, (size_t)n * sizeof(int));
+  if (e == hipSuccess) e = up(h->end, job->end, (size_t)n * sizeof(int));
+  if (e == hipSuccess) e = up(h->leaf, job->leaf, (size_t)n * sizeof(float));
+  if (e == hipSuccess) e = up(h->out_count, cnt0.data(), (size_t)n * sizeof(int));
+  if (e == hipSuccess) e = up(h->nold, nold.data(), (size_t)n * sizeof(int));
+  if (e == hipSuccess) e = up(h->skip, zero.data(), (size_t)n * sizeof(int));
+  if (e == hipSuccess) e = up(h->lin, lin.data(), lin.size() * sizeof(int));
+  if (e == hipSuccess) e = up(h->mlist, ml.data(), ml.size() * sizeof(int));
+  if (e == hipSuccess) e = up(h->cnt, cnt4, sizeof(cnt4));  // (the product's earlier kernels zero the first two)
+  if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)h->out, (int)LOAM_DEV_VG_SENTINEL, (size_t)total * 4, st);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    return LOAM_E_HIP;
+  }
+  loam::VgJob j;
+  j.keys = h->k; j.keys_alt = h->k2; j.vals = h->v; j.vals_alt = h->v2;
+  j.lists[0] = h->l0; j.lists[1] = h->l1; j.counts = h->cnt;
+  j.in = h->in; j.out = h->out; j.begin = h->begin; j.end = h->end; j.leaf = h->leaf;
+  j.out_count = h->out_count; j.nseg = n; j.total = total;
+  j.zeroed = true;
+  if (job->route == LOAM_DEV_VG_STACK) {
+    h->vgs.npar = n;
+    e = loam::vg_route_stack(j, st, job->P, job->stack_max, job->vg_split, job->capS, &h->vgs);
+  } else if (cubes) {
+    j.list = h->lin; j.list_n = h->cnt + 2;
+    e = loam::vg_route_cubes(j, st, job->P, job->vg_merge, h->nold, h->mlist, h->cnt + 3, h->skip);
+  } else {
+    e = loam::vg_route_surround(j, st);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out_pts, h->out, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_count, h->out_count, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && merge) e = hipMemcpyAsync(merged, h->skip, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);  // (the host arrays above live until here)
+  if (e == hipSuccess) e = es;
+  if (!merge) std::fill(merged, merged + n, -1);
+  return e == hipSuccess ? LOAM_OK : LOAM_E_HIP;
+}
+
+extern "C" int loam_dev_vg_destroy(loam_dev_vg* h) {
+  if (!h) return LOAM_E_INVAL;
+  (void)hipSetDevice(h->device);
+  if (h->st) (void)hipStreamSynchronize(h->st);
+  dev_vg_free(h);
+  return LOAM_OK;
+}
