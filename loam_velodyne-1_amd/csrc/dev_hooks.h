@@ -10,7 +10,7 @@
 extern "C" {
 #endif
 
-/* The segmented VoxelGrid (mp.hip vg_run) through the product's three routes.  A handle owns the
+/* The segmented VoxelGrid (vg.hip vg_run) through the product's three routes.  A handle owns the
  * device scratch a mapping instance would (sort arrays, cascade lists and counters, input / merge
  * lists, nold / skip, the split's buffers); consecutive jobs reuse it as consecutive frames do. */
 typedef struct loam_dev_vg loam_dev_vg;

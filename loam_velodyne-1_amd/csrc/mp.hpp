@@ -10,6 +10,7 @@
 #include "engine.hpp"
 #include "xfer.hpp"
 #include "od.hpp"
+#include "vg.hpp"
 
 namespace loam {
 
@@ -46,64 +47,6 @@ struct MpInput {
   // state layout), so the full cloud is neither written to nor read back from fullEnd
   const float* end_state = nullptr;
   int end_mode = 0;
-};
-
-// the voxel frame of a segment (PCL VoxelGrid's min_b and divb multipliers), for sub-segments that
-// take their parent's (vg_run's big-segment split)
-struct VgFrame {
-  int m0, m1, m2, divx, divy, pad;
-};
-
-// segmented PCL VoxelGrid job (segment s: input in[begin[s] .. end[s]), output out[begin[s] ..))
-struct VgJob {
-  const float4* in;
-  float4* out;
-  const int* begin;
-  const int* end;
-  const float* leaf;     // per segment
-  int* out_count;        // per segment
-  uint32_t *keys, *keys_alt, *vals, *vals_alt;  // k_vg_big's global sort arrays (indexed like in)
-  int nseg;
-  int total;             // size of in / out / keys arrays
-  // vg_run's cascade: lists[0] / lists[1] ([nseg] segment ids) and their lengths counts[0] / [1]
-  // (device); a kernel processes every segment, or the ids of list / *list_n, and appends the
-  // segments beyond its capacity to big / *big_n
-  int* lists[2] = {nullptr, nullptr};
-  int* counts = nullptr;   // [3]: the two lists' lengths, and the length of the caller's input list
-  // set by the caller: counts[0] / counts[1] already zeroed by an earlier kernel on the stream
-  bool zeroed = false;
-  const int* list = nullptr;
-  const int* list_n = nullptr;
-  int* big = nullptr;
-  int* big_n = nullptr;
-  // incremental cube VoxelGrid (k_vg_merge): per segment the count of its leading points that are the
-  // cube's previous VoxelGrid output, the candidate list, and the per-segment "done" flags the
-  // cascade's first kernel skips
-  const int* nold = nullptr;
-  const int* mlist = nullptr;
-  const int* mlist_n = nullptr;
-  int* skip = nullptr;
-  // per segment: the voxel frame to use instead of the segment's own bounding box (sub-segments of a
-  // split parent); nullptr: every segment computes its own
-  const VgFrame* frame = nullptr;
-  int grid_max = 1 << 30;  // the first kernel's grid at most (the split's sub-job)
-};
-
-// vg_run's split of the segments beyond the LDS tiers (the HDL-64E surf stacks): each parent's
-// points re-ordered stably into 16 buckets by the top bits of their voxel key (k_vg_split), the
-// buckets VoxelGridded as sub-segments in the parent's frame by the LDS cascade, their outputs
-// concatenated in bucket order (k_vg_join).  Sub-segment li * 16 + d; pts / out indexed like the
-// job's input
-struct VgSplit {
-  float4* pts = nullptr;
-  float4* out = nullptr;
-  int *begin = nullptr, *end = nullptr, *out_count = nullptr;
-  float* leaf = nullptr;
-  VgFrame* frame = nullptr;
-  int* lists[2] = {nullptr, nullptr};
-  int* ilist = nullptr;   // the non-empty sub-segments (the cascade's input list)
-  int* counts = nullptr;  // [3]: the cascade's two lists, ilist
-  int npar = 0;           // parents it holds (list entries beyond go to k_vg_big)
 };
 
 struct MpBuffers {
@@ -147,14 +90,14 @@ struct MpBuffers {
   float* vseg_leaf = nullptr;
   int *sseg_b = nullptr, *sseg_e = nullptr, *sseg_cnt = nullptr;  // [P][2] stack segments
   float* sseg_leaf = nullptr;
-  uint32_t *vg_k = nullptr, *vg_k2 = nullptr, *vg_v = nullptr, *vg_v2 = nullptr;
-  int *vg_l0 = nullptr, *vg_l1 = nullptr;  // [P][2][kMaxValid] vg_run's segment lists
+  // the VoxelGrid scratch: sort arrays [max(P map_cap, P cap_stack)], vg_run's segment lists
+  // [P][2][kMaxValid], counts [4] (the lengths of its two lists, of vg_lin, of vg_mlist), the stack
+  // job's big-segment split (2P parents)
+  VgScratch vg;
   int* vg_lin = nullptr;                   // [P][2][kMaxValid] the non-empty cube segments (k_mp_vseg)
-  int* vg_cnt = nullptr;                   // [4] the lists' lengths (vg_l0, vg_l1, vg_lin, vg_mlist)
   int* vg_mlist = nullptr;                 // [P][2][kMaxValid] cube segments k_vg_merge may take
   int* vseg_nold = nullptr;                // [P][2][kMaxValid] leading points from the cube's last DS
   int* vseg_skip = nullptr;                // [P][2][kMaxValid] 1: k_vg_merge wrote the segment
-  VgSplit vgs;                             // the stack job's big-segment split (2P parents)
   float4* reg = nullptr;      // [P][capS] registered full cloud
   double* part = nullptr;     // [P][kMpSmallGrid][28] k_mp_lm_small's per-workgroup JᵀJ | Jᵀb | rows
   int* done = nullptr;        // [P] its workgroups finished (the last one runs the step)
@@ -237,7 +180,7 @@ hipError_t mp_batch_iters(MpBuffers& b, hipStream_t st, int32_t* iters);
 // Canonical order: key = kind * kCubeNum + cube (kind 0 corner, 1 surf), ascending; inside a key
 // the store's own point order.  The small tables both calls need live in one device block (`tab`,
 // ints) with a pinned host copy of its head; the point scratch is the store's own idle buffers
-// (vin, vg_k / vg_k2 / vg_v / vg_v2, app_cnt: all rewritten by a frame before it reads them).
+// (vin, the VoxelGrid sort arrays vg.keys .. vg.vals_alt, app_cnt: all rewritten by a frame before it reads them).
 constexpr int kMapKeys = 2 * kCubeNum;
 constexpr int kMapTabOff = 0;                     // [kMapKeys + 1] canonical offsets (export)
 constexpr int kMapTabInfo = kMapKeys + 2;         // centre[3], istate error, aft[6], bef[6] (export)

@@ -1,4 +1,4 @@
-"""The segmented VoxelGrid cascade (csrc/mp.hip vg_run and its seven kernels) tier by tier, through
+"""The segmented VoxelGrid cascade (csrc/vg.hip vg_run and its seven kernels) tier by tier, through
 the product's own three routes (the diagnostic hook loam_dev_vg_run, csrc/dev_hooks.h), against
 oracle_voxel_grid per segment: the counts and every output float bit for bit, the sentinel intact
 between the segments.  The sizes are the kernels' capacity edges; tests/test_vg_cases.py shows that

@@ -1,6 +1,6 @@
 """Input segments for the VoxelGrid cascade's edges (tests/test_vg_cases.py checks that the drawn
 inputs have the properties they are meant to have; tests/test_gpu_voxelgrid.py runs them), and a
-numpy restatement of the voxel key computation (csrc/mp.hip vg_frame_of and the kernels' key
+numpy restatement of the voxel key computation (csrc/vg.hip vg_frame_of and the kernels' key
 lines, as pcl_voxel_grid in tests/test_oracle_components.py) that tells, per segment, how many bits
 its largest key needs, how k_vg_split would bucket it and whether k_vg_merge may take it.
 
@@ -80,7 +80,7 @@ def merge_precondition(pts, leaf, nold):
 
 
 def merge_eligible(n, nold, merge_min, new_max=8192):
-    """vg_merge_eligible (csrc/mp.hip), restated"""
+    """vg_merge_eligible (csrc/vg.hpp), restated"""
     return n > merge_min and nold > 0 and n - nold <= new_max
 
 

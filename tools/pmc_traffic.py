@@ -12,7 +12,7 @@ import json
 import sys
 
 
-# the VoxelGrid cascade's kernels carry their job as the last template argument (mp.hip vg_run's
+# the VoxelGrid cascade's kernels carry their job as the last template argument (vg.hip vg_run's
 # TAG): they are reported per job, under bench.py's names for the two jobs of a step
 VG_JOBS = {"0": "vg_stack", "1": "vg_cubes", "2": "vg_surround"}
 
