@@ -343,6 +343,44 @@ int loam_map_localize(loam_ctx *ctx, const loam_pose6 *odom_sum,
                       uint32_t n, const loam_pose6 *aft, const loam_pose6 *bef,
                       loam_localize_result *out);
 
+/* ---- scoring pose guesses against the map (no reference equivalent) ----
+ * loam_map_localize's missing score (score its refined aft) and its pre-filter (score a grid of
+ * tens of thousands of guesses, refine the best few hundred): no L-M, no per-candidate working set. */
+#define LOAM_SCORE_MAX 65536
+
+typedef struct {
+  uint32_t corner_scored, surf_scored; /* points of each cloud with three finite coordinates (same for every candidate) */
+  uint32_t corner_in, surf_in;         /* of them: nearest map point of the same kind at d2 < max_dist^2 */
+  double corner_cost, surf_cost;       /* sum over the scored points of (inlier ? d2 : max_dist^2) */
+} loam_score_result;                   /* 32 bytes */
+
+/* out[h], h < n: every scored point p of the two clouds is put into the map frame by
+ * pointAssociateToMap (src/laserMapping.cpp:234-252) with transformTobeMapped = pose[h]; d2 is the
+ * smallest float squared distance (dx*dx + dy*dy + dz*dz, no contraction) to any point of the same
+ * kind in the context's streaming map: the whole map, not a candidate's valid cubes, so the grid
+ * centre plays no part.  With r2 = max_dist * max_dist (float) the point is an inlier iff d2 < r2
+ * (false for a NaN and for an empty map) and contributes d2, else r2, to its cloud's cost, a
+ * double sum of these float terms.  A transformed coordinate that is non-finite or beyond 2^24 has
+ * no neighbour.  Nothing is downsampled.  pose[h] is a map pose of the sweep (what aft is after a
+ * mapping frame): loam_map_localize's returned aft, or a grid of guesses, with the sweep's
+ * corner_last / surf_last.  Rank by corner_in + surf_in (more is better), then by corner_cost +
+ * surf_cost (less is better).
+ * out[h] depends on the map, the clouds, max_dist and pose[h] only: bit for bit the same whatever
+ * n is, wherever h sits in the call, and from run to run (partial sums are combined in a fixed
+ * order given by the clouds' sizes; no floating-point atomics).
+ * The call waits for the context's queued work (a deferred map update included) and changes
+ * nothing in the context.  The map's index (a 1 m cell hash of every map point: 16 bytes per point
+ * and 16 per bucket) is rebuilt by every call and shared by all candidates; the working set is allocated on
+ * demand and kept until loam_destroy.  An empty map is no error: every count is 0 and every cost
+ * is scored * r2.
+ * Errors: LOAM_E_INVAL for a null argument, n == 0 or n > LOAM_SCORE_MAX, max_dist not in (0, 1]
+ * (the index has 1 m cells: the 27 cells around a point hold every neighbour closer than 1 m), a
+ * cloud with count > 0 and pts NULL, a cloud larger than max_points, or a map whose last update
+ * overflowed map_capacity; LOAM_E_NOMEM when the working set cannot be allocated; LOAM_E_HIP for
+ * a failed HIP call.  In every error case out is untouched and the context is as it was. */
+int loam_map_score(loam_ctx *ctx, const loam_cloud_out *corner, const loam_cloud_out *surf,
+                   float max_dist, uint32_t n, const loam_pose6 *pose, loam_score_result *out);
+
 /* scheduling (no reference equivalent; the reference's nodes are OS processes): priority of the
  * context's HIP streams.  priority > 0 = the device's highest stream priority, 0 = normal,
  * < 0 = lowest.  Used by a node pipeline to favour its critical node (laserMapping) when several

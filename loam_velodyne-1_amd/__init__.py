@@ -150,11 +150,24 @@ class LocalizeResult(ctypes.Structure):
 
 LOCALIZE_KEYS = tuple(n for n, _ in LocalizeResult._fields_)
 
+SCORE_MAX = 65536  # LOAM_SCORE_MAX: poses of one loam_map_score call
+
+
+class ScoreResult(ctypes.Structure):
+    """include/loam/loam.h loam_score_result: one pose of loam_map_score"""
+    _fields_ = [("corner_scored", ctypes.c_uint32), ("surf_scored", ctypes.c_uint32),
+                ("corner_in", ctypes.c_uint32), ("surf_in", ctypes.c_uint32),
+                ("corner_cost", ctypes.c_double), ("surf_cost", ctypes.c_double)]
+
+
+SCORE_KEYS = tuple(n for n, _ in ScoreResult._fields_)
+_SCORE_DTYPE = np.dtype([(n, np.float64 if t is ctypes.c_double else np.uint32) for n, t in ScoreResult._fields_])
+
 
 EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_error", "loam_imu",
            "loam_scan_registration", "loam_odometry", "loam_mapping", "loam_mapping_surround",
            "loam_maintenance", "loam_chain_sweep",
-           "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_map_localize", "loam_get_stats",
+           "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_map_localize", "loam_map_score", "loam_get_stats",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -200,6 +213,8 @@ def lib():
         L.loam_map_import.argtypes = [PP, P(Map), P(ctypes.c_uint64)]
         L.loam_map_localize.argtypes = [PP, P(Pose6), P(CloudOut), P(CloudOut), ctypes.c_uint32, P(Pose6), P(Pose6),
                                         P(LocalizeResult)]
+        L.loam_map_score.argtypes = [PP, P(CloudOut), P(CloudOut), ctypes.c_float, ctypes.c_uint32, P(Pose6),
+                                     P(ScoreResult)]
         L.loam_get_stats.argtypes = [PP, P(Stats)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
@@ -509,6 +524,59 @@ class Engine:
                                                  (k, np.int32 if k in ("status", "iters", "degenerate_steps") else np.uint32)
                                                  for k in LOCALIZE_KEYS]), count=n)
         return {k: rec[k].copy() for k in LOCALIZE_KEYS}
+
+    def map_score(self, corner, surf, poses, max_dist=1.0):
+        """poses (n, 6) float32 of one sweep scored against the context's whole map, which is left
+        untouched (loam_map_score): a dict of numpy arrays, one entry per pose: corner_scored /
+        surf_scored (the clouds' finite points), corner_in / surf_in (those whose nearest map point
+        of the same kind is closer than max_dist <= 1 m), corner_cost / surf_cost (float64: the sum
+        of the squared nearest distances, max_dist^2 for a point without such a neighbour).  A pose's
+        entries do not depend on the other poses of the call.  Any number of poses: more than
+        SCORE_MAX go in several calls."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        n = poses.shape[0]
+        refs = [_cloud_ref(a) for a in (corner, surf)]
+        rec = np.empty(n, _SCORE_DTYPE)
+        for a in range(0, n, SCORE_MAX):
+            m = min(SCORE_MAX, n - a)
+            _check(lib().loam_map_score(self.h, ctypes.byref(refs[0][0]), ctypes.byref(refs[1][0]), float(max_dist), m,
+                                        poses[a:a + m].ctypes.data_as(ctypes.POINTER(Pose6)),
+                                        rec[a:a + m].ctypes.data_as(ctypes.POINTER(ScoreResult))))
+        return {k: rec[k].copy() for k in SCORE_KEYS}
+
+    def relocalize(self, corner, surf, poses, keep=64, max_dist=1.0):
+        """where in the loaded map is this sweep: scores every pose guess (map_score), refines the
+        best `keep` (<= LOCALIZE_MAX) with map_localize (odom_sum = zeros, bef = None, aft = the
+        guess) and scores the refined poses of the LOC_SOLVED ones.  Returns a dict: index (the kept
+        guesses' rows of `poses`), localize (map_localize's result for them), coarse (their first
+        scores), fine (the scores of their refined aft; a guess that was not LOC_SOLVED keeps its
+        coarse score), all ordered best first by the fine score: most corner_in + surf_in, then
+        least corner_cost + surf_cost, then lowest index.  The kept guesses are chosen by the same key
+        on the coarse scores."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        if not 1 <= keep <= LOCALIZE_MAX:
+            raise ValueError("keep must be in [1, LOCALIZE_MAX]")
+        coarse = self.map_score(corner, surf, poses, max_dist)
+        idx = score_order(coarse)[:keep]
+        loc = self.map_localize(np.zeros(6, np.float32), corner, surf, poses[idx])
+        fine = {k: coarse[k][idx].copy() for k in SCORE_KEYS}
+        ok = np.flatnonzero(loc["status"] == LOC_SOLVED)
+        if ok.size:
+            s = self.map_score(corner, surf, loc["aft"][ok], max_dist)
+            for k in SCORE_KEYS:
+                fine[k][ok] = s[k]
+        o = score_order(fine, idx)
+        return {"index": idx[o], "localize": {k: v[o] for k, v in loc.items()},
+                "coarse": {k: coarse[k][idx][o] for k in SCORE_KEYS}, "fine": {k: v[o] for k, v in fine.items()}}
+
+
+def score_order(score, index=None):
+    """the rows of a map_score result best first: most corner_in + surf_in, then least corner_cost +
+    surf_cost, then lowest index (the row number, or the given one)"""
+    n_in = score["corner_in"].astype(np.int64) + score["surf_in"]
+    cost = score["corner_cost"] + score["surf_cost"]
+    index = np.arange(n_in.shape[0]) if index is None else np.asarray(index)
+    return np.lexsort((index, cost, -n_in))
 
 
 def save_map(path, m):

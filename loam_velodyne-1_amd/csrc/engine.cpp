@@ -21,6 +21,7 @@
 #include "mp.hpp"
 #include "od.hpp"
 #include "pose_math.hpp"
+#include "score.hpp"
 
 #ifdef LOAM_PIPE_TRACE
 // Diagnostic builds only (tools/build_variant.sh NAME -DLOAM_PIPE_TRACE): device timestamps of the
@@ -210,6 +211,7 @@ struct loam_ctx {
   int pack_S = 0;
   MapIo mio;  // loam_map_export / loam_map_import: their small tables (the points go through pack_dev / pack_pin)
   MpLoc loc;  // loam_map_localize: the candidates' working set, allocated by the first call, kept until loam_destroy
+  MpScore score;  // loam_map_score: the query clouds, the pose / result tables and the map index, likewise
   void free_pack_table() {
     if (pack_table) (void)hipFree(pack_table);
     if (pack_table_h) (void)hipHostFree(pack_table_h);
@@ -482,6 +484,7 @@ void loam_destroy(loam_ctx* x) {
   x->free_pack();
   mp_map_free(x->mio);
   mp_loc_free(x->loc);
+  mp_score_free(x->score);
   for (auto& e : x->feed_copied)
     if (e) (void)hipEventDestroy(e);
   if (x->sr_imu_dev) (void)hipFree(x->sr_imu_dev);
@@ -2171,6 +2174,81 @@ extern "C" int loam_map_localize(loam_ctx* x, const loam_pose6* odom_sum, const 
     o.map_corner = (uint32_t)r[kLrMapC];
     o.map_surf = (uint32_t)r[kLrMapS];
   }
+  return LOAM_OK;
+}
+
+// ------------------------------------------------------------------ scoring pose guesses
+// n poses of one sweep against the whole streaming map, which is only read (score.hpp).  The host
+// reads the map's sizes once (to size the index), then the results.
+extern "C" int loam_map_score(loam_ctx* x, const loam_cloud_out* corner, const loam_cloud_out* surf, float max_dist,
+                              uint32_t n, const loam_pose6* pose, loam_score_result* out) {
+  static_assert(LOAM_SCORE_MAX == kScoreMax, "loam.h and score.hpp");
+  static_assert(sizeof(loam_score_result) == 32, "loam_score_result layout");
+  if (!x || !corner || !surf || !pose || !out) return fail(LOAM_E_INVAL, "null argument");
+  if (n == 0 || n > LOAM_SCORE_MAX) return fail(LOAM_E_INVAL, "loam_map_score: n must be in [1, LOAM_SCORE_MAX]");
+  if (!(max_dist > 0.0f && max_dist <= 1.0f))
+    return fail(LOAM_E_INVAL, "loam_map_score: max_dist must be in (0, 1] (the map index has 1 m cells)");
+  if ((corner->count && !corner->pts) || (surf->count && !surf->pts))
+    return fail(LOAM_E_INVAL, "loam_map_score: a cloud's pts is null");
+  if (corner->count > (uint32_t)x->cap || surf->count > (uint32_t)x->cap)
+    return fail(LOAM_E_INVAL, "loam_map_score: a cloud exceeds max_points");
+  int rc = map_drain(x);
+  if (rc) return rc;
+  MpBuffers& b = x->mp1;
+  MpScore& S = x->score;
+  const int cnt[2] = {(int)corner->count, (int)surf->count};
+  hipError_t he = mp_map_ensure(x->mio);
+  if (he == hipSuccess) he = mp_score_reserve(S, std::max(cnt[0], cnt[1]));
+  if (he != hipSuccess)
+    return fail(LOAM_E_NOMEM, std::string("loam_map_score: working set allocation failed: ") + hipGetErrorString(he));
+  hipStream_t st = x->st;
+  std::memcpy(S.pose_h(), pose, (size_t)n * sizeof(loam_pose6));
+  x->prof.begin(st);
+  he = mp_map_table(b, x->mio, st, &x->prof);
+  x->pin.reset();
+  if (he == hipSuccess) he = x->pin.reserve((size_t)cnt[0] + cnt[1], st);
+  if (he == hipSuccess) he = x->pin.up(st, S.q, corner->pts, (size_t)cnt[0]);
+  if (he == hipSuccess) he = x->pin.up(st, S.q + S.cloud_cap, surf->pts, (size_t)cnt[1]);
+  if (he == hipSuccess) he = hipMemcpyAsync(S.pose, S.pose_h(), (size_t)n * sizeof(loam_pose6), hipMemcpyHostToDevice, st);
+  x->prof.mark("map_score_h2d");
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    x->prof.collect();
+    return fail(LOAM_E_HIP, std::string("loam_map_score: ") + hipGetErrorString(he));
+  }
+  const int* T = x->mio.tab_h;
+  const int nC = T[kMapTabOff + kCubeNum], total = T[kMapTabOff + kMapKeys];
+  if ((T[kMapTabInfo + 3] & ERR_CAP_MAP) || nC < 0 || total < nC || total > b.map_cap) {
+    x->prof.collect();
+    return fail(LOAM_E_INVAL, "loam_map_score: the last map update exceeded map_capacity, the store is not valid");
+  }
+  he = mp_score_reserve_map(S, nC, total - nC, cnt[0], cnt[1], (int)n);
+  if (he != hipSuccess) {
+    x->prof.collect();
+    return fail(LOAM_E_NOMEM, std::string("loam_map_score: index allocation failed (") + std::to_string(total) +
+                                  " map points): " + hipGetErrorString(he));
+  }
+  const bool count = x->prof.on;  // (with profiling the reduction also adds up the points and buckets the searches read)
+  he = mp_score_run(S, b, x->mio, nC, total, cnt[0], cnt[1], max_dist * max_dist, (int)n, count, st, &x->prof);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    x->prof.collect();
+    return fail(LOAM_E_HIP, std::string("loam_map_score: ") + hipGetErrorString(he));
+  }
+  x->prof.collect();
+  if (count) {  // work counters beside the kernel times: (count, calls)
+    const char* names[3] = {"score_nn_candidates", "score_nn_cells", "score_queries"};
+    const double v[3] = {(double)S.work_h()[0], (double)S.work_h()[1],
+                         (double)n * ((double)S.res_h()[0].corner_scored + (double)S.res_h()[0].surf_scored)};
+    for (int k = 0; k < 3; ++k) {
+      auto& a = x->prof.acc[names[k]];
+      a.first += v[k];
+      a.second += 1;
+    }
+  }
+  std::memcpy(out, S.res_h(), (size_t)n * sizeof(loam_score_result));
   return LOAM_OK;
 }
 
