@@ -381,6 +381,69 @@ typedef struct {
 int loam_map_score(loam_ctx *ctx, const loam_cloud_out *corner, const loam_cloud_out *surf,
                    float max_dist, uint32_t n, const loam_pose6 *pose, loam_score_result *out);
 
+/* ---- lanes: many independent sequences in lockstep (no reference equivalent) ----
+ * n_lanes sequences in one context, each advanced by one sweep per step.  Lane l behaves exactly as
+ * a fresh context that is fed lane l's sweeps through loam_chain_sweep, with no IMU message: the
+ * same poses, registered clouds and map, bit for bit, whatever the other lanes do.  A step runs the
+ * batch's kernels on all lanes at once (one launch sequence per step, not per sequence) and keeps
+ * what the streaming path keeps from sweep to sweep: the Last clouds, transformSum, the cube maps,
+ * Bef / Aft.  system_delay, the odometry's init frame, skip_frame_num and the surround phase advance
+ * identically in every lane, so published and mapped are the same for every live lane of a step.
+ * The lanes never take the two launch forms loam_set_tuning's od_persist / mp_persist and
+ * od_moments_min select, at any n_lanes (1 included), and no tuning turns them on:
+ *   - the per-query moments are not bit-identical to the other forms, and a sequence compounds a
+ *     difference that was validated for one two-sweep problem only;
+ *   - the persistent L-M kernels' workgroups wait on each other, and more than two of them running
+ *     at once on one GPU can hang: a lanes step is safe beside any other context's work.
+ * The streaming nodes, the batch and the IMU queues of the context are separate state and untouched;
+ * their entry points may be called whenever no lanes step is in flight. */
+#define LOAM_LANES_MAX 1024
+
+typedef struct {
+  int32_t status;     /* LOAM_OK, LOAM_E_NOT_READY inside system_delay, or the lane's sticky failure */
+  int32_t published;  /* loam_odometry's LOAM_PUB_* flags of this lane's frame */
+  int32_t mapped;     /* 1 when laserMapping ran on this sweep */
+  int32_t od_iters, mp_iters;   /* L-M iterations of this frame's odometry / mapping (0 when none ran) */
+  loam_pose6 od_sum;  /* transformSum, when LOAM_PUB_POSE */
+  loam_pose6 aft, bef;/* transformAftMapped / transformBefMapped, when mapped */
+  uint32_t n_registered; /* points of /velodyne_cloud_registered of this frame, when mapped */
+} loam_lane_out;
+
+/* Allocates the lanes' working set (scan registration for n_lanes sweeps, odometry and mapping for
+ * n_lanes problems, lane_map_capacity points of map store per lane, pinned staging for one step's
+ * sweeps; DESIGN.md §21 has the bytes per lane).  Every lane starts as a fresh context: empty map,
+ * centre (10, 5, 10), zero poses, odometry not initialised, system_delay not yet consumed.
+ * LOAM_E_INVAL: null context, lanes already open (close first), n_lanes == 0 or > LOAM_LANES_MAX,
+ * lane_map_capacity outside loam_create's [1024, 2^28], or n_lanes x lane_map_capacity or n_lanes x
+ * (max_points + 120 n_rings) reaching 2^31 (the message names the product).  LOAM_E_NOMEM when an
+ * allocation fails: everything is freed and the context is as it was.  loam_destroy closes. */
+int loam_lanes_open(loam_ctx *ctx, uint32_t n_lanes, uint32_t lane_map_capacity);
+/* One step: raw[l] is lane l's next sweep.  Packs the sweeps on the calling thread, enqueues the
+ * whole step and returns; the caller's buffers are free on return.  One step may be in flight: a
+ * second push before a pull is LOAM_E_INVAL.  Returns LOAM_OK when the step was enqueued, whatever
+ * the individual lanes will report.
+ * A lane fails when its sweep fails scan registration as the node call would (count == 0 or no
+ * finite point: LOAM_E_INVAL; more than max_points: LOAM_E_CAPACITY; null data or a bad stride:
+ * LOAM_E_INVAL) or when its map store or stack overflows (LOAM_E_CAPACITY).  The failure is sticky:
+ * the lane reports that code in status on this step and every later one, its other fields are not
+ * meaningful and its map cannot be exported; no other lane is affected, bit for bit.  Feeding
+ * count = 0 is therefore how a lane that has run out of sweeps is retired.  Inside system_delay the
+ * sweeps are not looked at, as in the node. */
+int loam_lanes_push(loam_ctx *ctx, double stamp, const loam_cloud_in *raw /* [n_lanes] */);
+/* Waits for the pushed step (its only synchronisation) and fills out[l] for every lane.  LOAM_OK
+ * when the step ran, whatever the lanes report; LOAM_E_INVAL with nothing pushed. */
+int loam_lanes_pull(loam_ctx *ctx, loam_lane_out *out /* [n_lanes] */);
+/* /velodyne_cloud_registered of one lane from the last pulled step: valid while that step's mapped
+ * is set and until the next push (LOAM_E_INVAL otherwise, for a failed lane and for lane >=
+ * n_lanes).  LOAM_E_CAPACITY writes the required size into out->count. */
+int loam_lanes_registered(loam_ctx *ctx, uint32_t lane, loam_cloud_out *out);
+/* loam_map_export for one lane's map: canonical cube order, centre, Aft / Bef; surround_phase is
+ * the lanes' shared mapping frame counter.  LOAM_E_INVAL while a step is in flight, for a failed
+ * lane and for lane >= n_lanes. */
+int loam_lanes_map_export(loam_ctx *ctx, uint32_t lane, loam_map *out);
+/* Frees the lanes' working set (waits for a step in flight).  LOAM_E_INVAL when not open. */
+int loam_lanes_close(loam_ctx *ctx);
+
 /* scheduling (no reference equivalent; the reference's nodes are OS processes): priority of the
  * context's HIP streams.  priority > 0 = the device's highest stream priority, 0 = normal,
  * < 0 = lowest.  Used by a node pipeline to favour its critical node (laserMapping) when several

@@ -7,6 +7,7 @@ on one GPU:
     mapping(pose, corner, surf, full) laserMapping body  src/laserMapping.cpp:411-1097
     maintenance(sum, bef, aft)      transformMaintenance src/transformMaintenance.cpp:147-203
     batch_*                         config 4 (independent problems)
+    lanes_*                         many sequences in lockstep
 
 There is no CPU path: without a GPU (or without the built library) every call raises.
 The package directory name contains '-', so import it with
@@ -164,10 +165,27 @@ SCORE_KEYS = tuple(n for n, _ in ScoreResult._fields_)
 _SCORE_DTYPE = np.dtype([(n, np.float64 if t is ctypes.c_double else np.uint32) for n, t in ScoreResult._fields_])
 
 
+LANES_MAX = 1024  # LOAM_LANES_MAX: lanes of one context
+
+
+class LaneOut(ctypes.Structure):
+    """include/loam/loam.h loam_lane_out: one lane of a lanes step"""
+    _fields_ = [("status", ctypes.c_int32), ("published", ctypes.c_int32), ("mapped", ctypes.c_int32),
+                ("od_iters", ctypes.c_int32), ("mp_iters", ctypes.c_int32), ("od_sum", Pose6), ("aft", Pose6),
+                ("bef", Pose6), ("n_registered", ctypes.c_uint32)]
+
+
+LANE_KEYS = tuple(n for n, _ in LaneOut._fields_)
+_LANE_DTYPE = np.dtype([(n, np.float32, (6,)) if t is Pose6 else (n, np.uint32 if t is ctypes.c_uint32 else np.int32)
+                        for n, t in LaneOut._fields_])
+
+
 EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_error", "loam_imu",
            "loam_scan_registration", "loam_odometry", "loam_mapping", "loam_mapping_surround",
            "loam_maintenance", "loam_chain_sweep",
            "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_map_localize", "loam_map_score", "loam_get_stats",
+           "loam_lanes_open", "loam_lanes_push", "loam_lanes_pull", "loam_lanes_registered", "loam_lanes_map_export",
+           "loam_lanes_close",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -216,6 +234,12 @@ def lib():
         L.loam_map_score.argtypes = [PP, P(CloudOut), P(CloudOut), ctypes.c_float, ctypes.c_uint32, P(Pose6),
                                      P(ScoreResult)]
         L.loam_get_stats.argtypes = [PP, P(Stats)]
+        L.loam_lanes_open.argtypes = [PP, ctypes.c_uint32, ctypes.c_uint32]
+        L.loam_lanes_push.argtypes = [PP, ctypes.c_double, P(CloudIn)]
+        L.loam_lanes_pull.argtypes = [PP, P(LaneOut)]
+        L.loam_lanes_registered.argtypes = [PP, ctypes.c_uint32, P(CloudOut)]
+        L.loam_lanes_map_export.argtypes = [PP, ctypes.c_uint32, P(Map)]
+        L.loam_lanes_close.argtypes = [PP]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -469,14 +493,18 @@ class Engine:
         corner / surf ([N, 4] float32, canonical order: cube index ascending, the store's order
         inside a cube), corner_offset / surf_offset ([MAP_CUBES + 1] uint32: cube c is
         points[offset[c]:offset[c + 1]]), center ([3] int32), surround_phase, aft, bef"""
+        return self._map_export(lambda m: lib().loam_map_export(self.h, ctypes.byref(m)))
+
+    @staticmethod
+    def _map_export(call):
         m = Map()
         offs = [np.zeros(MAP_CUBES + 1, np.uint32) for _ in range(2)]
         m.corner.cube_offset, m.surf.cube_offset = offs[0].ctypes.data, offs[1].ctypes.data
-        _check(lib().loam_map_export(self.h, ctypes.byref(m)))  # sizes only
+        _check(call(m))  # sizes only
         pts = [np.empty((int(c.count), 4), np.float32) for c in (m.corner, m.surf)]
         for c, a in zip((m.corner, m.surf), pts):
             c.pts, c.capacity = a.ctypes.data, a.shape[0]
-        _check(lib().loam_map_export(self.h, ctypes.byref(m)))
+        _check(call(m))
         return {"corner": pts[0], "surf": pts[1], "corner_offset": offs[0], "surf_offset": offs[1],
                 "center": np.array(m.center[:], np.int32), "surround_phase": int(m.surround_phase),
                 "aft": m.aft.arr(), "bef": m.bef.arr()}
@@ -499,6 +527,58 @@ class Engine:
         dropped = (ctypes.c_uint64 * 2)(0, 0)
         _check(lib().loam_map_import(self.h, ctypes.byref(m), dropped))
         return int(dropped[0]), int(dropped[1])
+
+    # --- lanes: many sequences in lockstep
+    def lanes_open(self, n, map_capacity):
+        """n independent sequences in this context, map_capacity points of map store each
+        (loam_lanes_open); every lane starts as a fresh Engine does"""
+        _check(lib().loam_lanes_open(self.h, int(n), int(map_capacity)))
+        self.n_lanes = int(n)
+
+    def lanes_push(self, raws, stamp=0.0):
+        """one step: raws[l] is lane l's next sweep ((n, >= 3) float array or a loam_cloud_in; an
+        empty array retires the lane).  Enqueues the step and returns (loam_lanes_push)."""
+        if len(raws) != self.n_lanes:
+            raise ValueError("one sweep per lane")
+        a = (CloudIn * self.n_lanes)()
+        keep = []
+        for l, r in enumerate(raws):
+            a[l], k = _cloud_in(r)
+            keep.append(k)
+        _check(lib().loam_lanes_push(self.h, stamp, a))
+
+    def lanes_pull(self):
+        """waits for the pushed step (loam_lanes_pull): a dict of numpy arrays, one row per lane:
+        status (LOAM_OK, LOAM_E_NOT_READY inside system_delay, or the lane's sticky failure code),
+        published, mapped, od_iters, mp_iters, od_sum / aft / bef (n, 6), n_registered"""
+        rec = np.zeros(self.n_lanes, _LANE_DTYPE)
+        _check(lib().loam_lanes_pull(self.h, rec.ctypes.data_as(ctypes.POINTER(LaneOut))))
+        return {k: rec[k].copy() for k in LANE_KEYS}
+
+    def lanes_step(self, raws, stamp=0.0):
+        """lanes_push followed by lanes_pull"""
+        self.lanes_push(raws, stamp)
+        return self.lanes_pull()
+
+    def lanes_registered(self, lane):
+        """/velodyne_cloud_registered of one lane from the last pulled step, which mapped
+        (loam_lanes_registered): an (n, 4) array"""
+        out = _Out(0)
+        rc = lib().loam_lanes_registered(self.h, int(lane), ctypes.byref(out.c))
+        if rc == LOAM_E_CAPACITY:
+            out = _Out(int(out.c.count))
+            rc = lib().loam_lanes_registered(self.h, int(lane), ctypes.byref(out.c))
+        _check(rc)
+        return out.get()
+
+    def lanes_map_export(self, lane):
+        """one lane's cube map and mapping pose state (loam_lanes_map_export): the dict map_export
+        returns, so save_map takes it"""
+        return self._map_export(lambda m: lib().loam_lanes_map_export(self.h, int(lane), ctypes.byref(m)))
+
+    def lanes_close(self):
+        _check(lib().loam_lanes_close(self.h))
+        self.n_lanes = 0
 
     def map_localize(self, odom_sum, corner, surf, aft, bef=None):
         """n candidate poses of one sweep against the context's map, which is left untouched

@@ -18,6 +18,7 @@
 
 #include "../../include/loam/loam.h"
 #include "engine.hpp"
+#include "lanes.hpp"
 #include "mp.hpp"
 #include "od.hpp"
 #include "pose_math.hpp"
@@ -212,6 +213,7 @@ struct loam_ctx {
   MapIo mio;  // loam_map_export / loam_map_import: their small tables (the points go through pack_dev / pack_pin)
   MpLoc loc;  // loam_map_localize: the candidates' working set, allocated by the first call, kept until loam_destroy
   MpScore score;  // loam_map_score: the query clouds, the pose / result tables and the map index, likewise
+  Lanes lanes;    // loam_lanes_*: S sequences in lockstep, their own working set (lanes.hpp); S = 0 until loam_lanes_open
   void free_pack_table() {
     if (pack_table) (void)hipFree(pack_table);
     if (pack_table_h) (void)hipHostFree(pack_table_h);
@@ -305,6 +307,24 @@ void pack(const loam_cloud_in& c, float4* dst, size_t i0, size_t i1) {
     std::memcpy(q, base + i * c.stride_bytes, sizeof(q));
     dst[i] = make_float4(q[0], q[1], q[2], 0.0f);
   }
+}
+
+// sweeps [s0, s1) (sweep s = sweep(s)) packed back to back (sweep s at off[s]) into dst, on up to eight threads
+template <class Sweep>
+void pack_tight_of(Sweep sweep, size_t s0, size_t s1, const int* off, float4* dst) {
+  auto run = [&](size_t a, size_t b) {
+    for (size_t s = a; s < b; ++s) {
+      const loam_cloud_in& c = sweep(s);
+      pack(c, dst + off[s], 0, c.count);
+    }
+  };
+  const size_t S = s1 - s0;
+  const unsigned hw = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+  const size_t nt = S >= 64 ? hw : 1;
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < nt; ++t) th.emplace_back(run, s0 + S * t / nt, s0 + S * (t + 1) / nt);
+  run(s0, s0 + S / nt);
+  for (auto& t : th) t.join();
 }
 
 // device cloud -> caller storage through the pinned arena (completed by pin.finish() after a sync)
@@ -485,6 +505,7 @@ void loam_destroy(loam_ctx* x) {
   mp_map_free(x->mio);
   mp_loc_free(x->loc);
   mp_score_free(x->score);
+  lanes_free(x->lanes);
   for (auto& e : x->feed_copied)
     if (e) (void)hipEventDestroy(e);
   if (x->sr_imu_dev) (void)hipFree(x->sr_imu_dev);
@@ -592,6 +613,7 @@ int loam_set_tuning(loam_ctx* x, const char* key, long long value) {
   x->drop_graph();  // (captured with the old choices)
   x->od1.tune = x->odb.tune = t;
   x->mp1.tune = x->mpb.tune = x->mpb2.tune = t;
+  x->lanes.od.tune = x->lanes.mp.tune = lanes_tuning(t);
   return LOAM_OK;
 }
 
@@ -1184,21 +1206,9 @@ int loam_batch_upload(loam_ctx* x, uint32_t n, const loam_cloud_in* prev, const 
 }
 
 namespace {
-// sweeps [s0, s1) of a batch (sweep 2i = prev[i], 2i + 1 = cur[i]) packed back to back (sweep s at off[s]) into dst, on up to eight threads
+// sweeps [s0, s1) of a batch (sweep 2i = prev[i], 2i + 1 = cur[i]) packed back to back (pack_tight_of)
 void pack_tight(const loam_cloud_in* prev, const loam_cloud_in* cur, size_t s0, size_t s1, const int* off, float4* dst) {
-  auto run = [&](size_t a, size_t b) {
-    for (size_t s = a; s < b; ++s) {
-      const loam_cloud_in& c = (s & 1) ? cur[s / 2] : prev[s / 2];
-      pack(c, dst + off[s], 0, c.count);
-    }
-  };
-  const size_t S = s1 - s0;
-  const unsigned hw = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
-  const size_t nt = S >= 64 ? hw : 1;
-  std::vector<std::thread> th;
-  for (size_t t = 1; t < nt; ++t) th.emplace_back(run, s0 + S * t / nt, s0 + S * (t + 1) / nt);
-  run(s0, s0 + S / nt);
-  for (auto& t : th) t.join();
+  pack_tight_of([&](size_t s) -> const loam_cloud_in& { return (s & 1) ? cur[s / 2] : prev[s / 2]; }, s0, s1, off, dst);
 }
 
 // The second scan-registration set and the second mapping set, which only the modes that alternate
@@ -1921,15 +1931,15 @@ int map_drain(loam_ctx* x) {
 }
 }  // namespace
 
-extern "C" int loam_map_export(loam_ctx* x, loam_map* out) {
-  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
-  int rc = map_drain(x);
-  if (rc) return rc;
-  MpBuffers& b = x->mp1;
+namespace {
+// loam_map_export's body for instance `inst` of the store b, whose queued work has been drained
+// (loam_map_export: the streaming store; loam_lanes_map_export: a lane); phase: its mapFrameCount
+int map_export_of(loam_ctx* x, MpBuffers& b, int inst, int phase, loam_map* out) {
+  int rc = LOAM_OK;
   HIP_TRY(mp_map_ensure(x->mio));
   hipStream_t st = x->st;
   x->prof.begin(st);
-  HIP_TRY(mp_map_table(b, x->mio, st, &x->prof));
+  HIP_TRY(mp_map_table(b, x->mio, st, &x->prof, inst));
   HIP_TRY(hipStreamSynchronize(st));
   const int* T = x->mio.tab_h;
   const int nC = T[kMapTabOff + kCubeNum], total = T[kMapTabOff + kMapKeys];
@@ -1949,7 +1959,7 @@ extern "C" int loam_map_export(loam_ctx* x, loam_map* out) {
     else if (count[k] > 0) want = true;
   }
   for (int k = 0; k < 3; ++k) out->center[k] = T[kMapTabInfo + k];
-  out->surround_phase = x->map_frame_count;
+  out->surround_phase = phase;
   std::memcpy(&out->aft, T + kMapTabInfo + 4, sizeof(loam_pose6));
   std::memcpy(&out->bef, T + kMapTabInfo + 10, sizeof(loam_pose6));
   if (!fits) {
@@ -1962,7 +1972,8 @@ extern "C" int loam_map_export(loam_ctx* x, loam_map* out) {
   }
   rc = ensure_pack_stage(x, "map export");
   if (rc) return rc;
-  HIP_TRY(mp_map_pack(b, x->mio, total, st, &x->prof));
+  HIP_TRY(mp_map_pack(b, x->mio, total, st, &x->prof, inst));
+  const float4* packed = b.vin + (size_t)inst * b.map_cap;
   // the wanted clouds' runs of vin in chunks of one pinned buffer: chunk k is DMA'd into buffer
   // k & 1 while the host copies chunk k - 1 into the caller's array
   struct Chunk {
@@ -1977,7 +1988,7 @@ extern "C" int loam_map_export(loam_ctx* x, loam_map* out) {
   auto enqueue = [&](size_t k) -> hipError_t {
     const Chunk& ch = chunks[k];
     x->prof.mark("map_export_host_wait");
-    hipError_t e = hipMemcpyAsync(x->pack_pin[k & 1], b.vin + first[ch.kind] + ch.a, ch.n * sizeof(float4),
+    hipError_t e = hipMemcpyAsync(x->pack_pin[k & 1], packed + first[ch.kind] + ch.a, ch.n * sizeof(float4),
                                   hipMemcpyDeviceToHost, st);
     x->prof.mark("map_export_d2h");
     if (e == hipSuccess) e = hipEventRecord(x->pack_done[k & 1], st);
@@ -1998,6 +2009,14 @@ extern "C" int loam_map_export(loam_ctx* x, loam_map* out) {
   }
   x->prof.collect();
   return LOAM_OK;
+}
+}  // namespace
+
+extern "C" int loam_map_export(loam_ctx* x, loam_map* out) {
+  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
+  const int rc = map_drain(x);
+  if (rc) return rc;
+  return map_export_of(x, x->mp1, 0, x->map_frame_count, out);
 }
 
 extern "C" int loam_map_import(loam_ctx* x, const loam_map* in, uint64_t* dropped) {
@@ -2250,6 +2269,255 @@ extern "C" int loam_map_score(loam_ctx* x, const loam_cloud_out* corner, const l
   }
   std::memcpy(out, S.res_h(), (size_t)n * sizeof(loam_score_result));
   return LOAM_OK;
+}
+
+// ------------------------------------------------------------------ lanes
+// S sequences in lockstep (loam.h): a step is the batch's launch sequences on the
+// lanes' own working set, with the streaming path's life cycle.  What loam_chain_sweep keeps in the
+// context per sequence (system_delay, the odometry's init frame and frame counter, the surround
+// phase) is kept once for all lanes; what it keeps on the device (the odometry state, the Last
+// clouds, the map store) is the batch buffers' per-problem state, never cleared between steps.
+namespace {
+// what is wrong with a lane's pushed sweep before any kernel sees it (LOAM_OK: nothing)
+int lane_sweep_code(const loam_cloud_in& c, int cap) {
+  if (c.count == 0) return LOAM_E_INVAL;
+  if (c.data == nullptr || c.stride_bytes < 12 || c.stride_bytes % 4 != 0) return LOAM_E_INVAL;
+  if (c.count > (uint32_t)cap) return LOAM_E_CAPACITY;
+  return LOAM_OK;
+}
+
+// one step's device work on x->st, behind the sweeps' upload; sets L.step_pub / L.step_mapped
+hipError_t lanes_enqueue(loam_ctx* x, Prof* pf) {
+  Lanes& L = x->lanes;
+  const int S = L.S;
+  hipStream_t st = x->st;
+  OdBuffers& o = L.od;
+  hipError_t e = hipSuccess;
+  auto T = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+  sr_launch(L.sr, sr_params(x), st, pf);
+  const FeatView f = feat_view(L.sr, 0, 1);
+  L.step_pub = 0;
+  L.step_mapped = 0;
+  if (!L.od_inited) {  // src/laserOdometry.cpp:427-456: Last = raw lessSharp / lessFlat, no L-M (od_frame's init frame)
+    hipLaunchKernelGGL(k_od_end, dim3(kOdEndWg, S), dim3(256), 0, st, o, f, 0, 0, 0);
+    x->prof.mark("k_od_end");
+    od_build_hashes(o, 0, st);
+    x->prof.mark("k_hash_build_last");
+    L.od_last = 0;
+    L.od_inited = true;
+    L.step_pub = LOAM_PUB_CLOUDS;
+  } else {
+    const int cur = L.od_last, nxt = 1 - cur;
+    od_solve(o, f, cur, st, pf, /*device_fini=*/true);
+    x->prof.mark("k_od_fini");
+    L.od_frame_count++;
+    const bool pub = L.od_frame_count >= (int)x->cfg.skip_frame_num + 1;
+    hipLaunchKernelGGL(k_od_end, dim3(kOdEndWg, S), dim3(256), 0, st, o, f, nxt, 2, pub ? 1 : 0);
+    x->prof.mark("k_od_end");
+    od_build_hashes(o, nxt, st);
+    x->prof.mark("k_hash_build_last");
+    L.od_last = nxt;
+    L.step_pub = LOAM_PUB_POSE;
+    if (pub) {
+      L.od_frame_count = 0;
+      L.step_pub |= LOAM_PUB_CLOUDS | LOAM_PUB_FULL;
+      // laserMapping on the published clouds in place, as the device chain reads them: fullEnd is
+      // already at the sweep's end, the pose is the transformSum the odometry left on the device
+      MpInput in;
+      in.corner = o.lastC + (size_t)nxt * o.P * o.capC;
+      in.surf = o.lastS + (size_t)nxt * o.P * o.capS;
+      in.full = o.fullEnd + (size_t)nxt * o.P * o.capS;
+      in.corner_stride = o.capC; in.surf_stride = o.capS; in.full_stride = o.capS;
+      in.ncorner = o.nlast + nxt * 2; in.nsurf = o.nlast + nxt * 2 + 1; in.nfull = o.nfullEnd + nxt;
+      in.ncorner_stride = in.nsurf_stride = 2 * kOdBufs; in.nfull_stride = kOdBufs;
+      in.pose = o.state + kOdSum; in.pose_stride = kOdStateFloats;
+      mp_frame(L.mp, in, st, pf);
+      L.step_mapped = 1;
+      if (++L.map_frame_count >= 5) L.map_frame_count = 0;  // :1038-1040
+    }
+  }
+  T(lanes_out(L, st));
+  x->prof.mark("k_lanes_out");
+  T(hipGetLastError());
+  return e;
+}
+}  // namespace
+
+extern "C" int loam_lanes_open(loam_ctx* x, uint32_t n_lanes, uint32_t lane_map_capacity) {
+  if (!x) return fail(LOAM_E_INVAL, "null argument");
+  if (x->lanes.S) return fail(LOAM_E_INVAL, "loam_lanes_open: lanes are open (loam_lanes_close first)");
+  if (n_lanes == 0 || n_lanes > LOAM_LANES_MAX)
+    return fail(LOAM_E_INVAL, "loam_lanes_open: n_lanes must be in [1, LOAM_LANES_MAX]");
+  if (lane_map_capacity < 1024 || lane_map_capacity > (1u << 28))
+    return fail(LOAM_E_INVAL, "loam_lanes_open: lane_map_capacity must be in [1024, 2^28] points");
+  // (the stores' and stacks' segment bases and VgJob::total are ints)
+  const uint64_t cap_stack = (uint64_t)x->cap + (uint64_t)kLessSharpPerRing * x->R;
+  if ((uint64_t)n_lanes * lane_map_capacity >= ((uint64_t)1 << 31))
+    return fail(LOAM_E_INVAL, "loam_lanes_open: n_lanes x lane_map_capacity reaches 2^31 points");
+  if ((uint64_t)n_lanes * cap_stack >= ((uint64_t)1 << 31))
+    return fail(LOAM_E_INVAL, "loam_lanes_open: n_lanes x stack capacity (max_points + 120 n_rings) reaches 2^31 points");
+  HIP_TRY(hipSetDevice(x->device));
+  const hipError_t he = lanes_alloc(x->lanes, (int)n_lanes, x->cap, x->R, (int)lane_map_capacity,
+                                    (int)x->cfg.od_max_iter, (int)x->cfg.mp_max_iter);
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LOAM_E_NOMEM, std::string("loam_lanes_open: allocation failed: ") + hipGetErrorString(he));
+  }
+  Lanes& L = x->lanes;
+  L.od.tune = L.mp.tune = lanes_tuning(x->tune);
+  L.od_frame_count = (int)x->cfg.skip_frame_num;  // frameCount = skipFrameNum (src/laserOdometry.cpp:407)
+  return LOAM_OK;
+}
+
+extern "C" int loam_lanes_close(loam_ctx* x) {
+  if (!x) return fail(LOAM_E_INVAL, "null argument");
+  if (!x->lanes.S) return fail(LOAM_E_INVAL, "loam_lanes_close: lanes are not open");
+  HIP_TRY(hipSetDevice(x->device));
+  (void)hipStreamSynchronize(x->st);
+  (void)x->lanes.mp.take_error();
+  lanes_free(x->lanes);
+  return LOAM_OK;
+}
+
+extern "C" int loam_lanes_push(loam_ctx* x, double stamp, const loam_cloud_in* raw) {
+  (void)stamp;  // (no IMU in lanes: nothing is looked up by time)
+  if (!x || !raw) return fail(LOAM_E_INVAL, "null argument");
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_push: lanes are not open");
+  if (L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_push: a step is in flight (loam_lanes_pull first)");
+  const int S = L.S;
+  L.have_reg = false;
+  if (!L.sr_inited) {  // src/scanRegistration.cpp:213-219 (Q1): the sweeps are not looked at
+    L.sr_init_count++;
+    if (L.sr_init_count >= (int)x->cfg.system_delay) L.sr_inited = true;
+    L.in_flight = true;
+    L.step_ran = false;
+    return LOAM_OK;
+  }
+  HIP_TRY(hipSetDevice(x->device));
+  // a lane whose sweep cannot be uploaded, and a lane that failed before, is an empty sweep on the
+  // device: its slot goes through the kernels as an empty problem of a batch does
+  std::vector<loam_cloud_in> eff((size_t)S);
+  int* nn = L.tab_h;
+  int* off = nn + S;
+  size_t run = 0;
+  for (int l = 0; l < S; ++l) {
+    L.fail_new[l] = lane_sweep_code(raw[l], x->cap);
+    eff[l] = raw[l];
+    if (L.fail_new[l] != LOAM_OK || L.fail[l] != LOAM_OK) eff[l].count = 0;
+    nn[l] = (int)eff[l].count;
+    off[l] = (int)run;
+    run += eff[l].count;
+  }
+  hipStream_t st = x->st;
+  Prof* pf = x->prof.on ? &x->prof : nullptr;
+  x->prof.begin(st);
+  // packed in chunks of sweeps, each chunk's copy enqueued before the next is packed
+  constexpr int kPushChunk = 128;  // sweeps
+  for (int s0 = 0; s0 < S; s0 += kPushChunk) {
+    const int s1 = std::min(S, s0 + kPushChunk);
+    pack_tight_of([&](size_t s) -> const loam_cloud_in& { return eff[s]; }, (size_t)s0, (size_t)s1, off, L.stage_h);
+    const size_t a = (size_t)off[s0], b = (size_t)off[s1 - 1] + (size_t)nn[s1 - 1];
+    if (b > a)
+      HIP_TRY(hipMemcpyAsync(L.stage_d + a, L.stage_h + a, (b - a) * sizeof(float4), hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipMemcpyAsync(L.tab_d, nn, (size_t)2 * S * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(sr_scatter_packed(L.stage_d, L.tab_d + S, L.tab_d, L.sr.raw, x->cap, S, st));
+  HIP_TRY(hipMemcpyAsync(L.sr.raw_n, L.tab_d, (size_t)S * sizeof(int), hipMemcpyDeviceToDevice, st));
+  x->prof.mark("lanes_h2d");
+  const hipError_t he = lanes_enqueue(x, pf);
+  L.in_flight = true;
+  L.step_ran = true;
+  if (he != hipSuccess) return fail(LOAM_E_HIP, std::string("loam_lanes_push: ") + hipGetErrorString(he));
+  return LOAM_OK;
+}
+
+extern "C" int loam_lanes_pull(loam_ctx* x, loam_lane_out* out) {
+  static_assert(sizeof(loam_lane_out) == 96, "loam_lane_out layout");
+  static_assert(LOAM_LANES_MAX == 1024, "loam.h");
+  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_pull: lanes are not open");
+  if (!L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_pull: no step was pushed");
+  const int S = L.S;
+  if (!L.step_ran) {  // inside system_delay: nothing was enqueued
+    L.in_flight = false;
+    std::memset(out, 0, (size_t)S * sizeof(loam_lane_out));
+    for (int l = 0; l < S; ++l) out[l].status = LOAM_E_NOT_READY;
+    return LOAM_OK;
+  }
+  HIP_TRY(hipSetDevice(x->device));
+  hipError_t he = hipStreamSynchronize(x->st);
+  L.in_flight = false;
+  if (he == hipSuccess) he = L.mp.take_error();
+  x->prof.collect();
+  if (he != hipSuccess) return fail(LOAM_E_HIP, std::string("loam_lanes_pull: ") + hipGetErrorString(he));
+  std::memset(out, 0, (size_t)S * sizeof(loam_lane_out));
+  for (int l = 0; l < S; ++l) {
+    const int* w = L.out_h + (size_t)l * kLaneOutWords;
+    loam_lane_out& q = out[l];
+    if (L.fail[l] == LOAM_OK) {  // this step's failure, the host's finding first
+      int code = L.fail_new[l];
+      if (code == LOAM_OK && (w[kLoSrErr] & ERR_EMPTY)) code = LOAM_E_INVAL;
+      if (code == LOAM_OK && (w[kLoSrErr] & ERR_CAP_RING)) code = LOAM_E_CAPACITY;
+      if (code == LOAM_OK && w[kLoOdErr]) code = LOAM_E_CAPACITY;
+      if (code == LOAM_OK && L.step_mapped && w[kLoMpErr]) code = LOAM_E_CAPACITY;
+      L.fail[l] = code;
+    }
+    L.nreg[l] = 0;
+    if (L.fail[l] != LOAM_OK) {
+      q.status = L.fail[l];
+      continue;
+    }
+    q.status = LOAM_OK;
+    q.published = L.step_pub;
+    q.mapped = L.step_mapped;
+    if (L.step_pub & LOAM_PUB_POSE) {
+      q.od_iters = w[kLoOdIters];
+      std::memcpy(&q.od_sum, w + kLoOdSum, sizeof(loam_pose6));
+    }
+    if (L.step_mapped) {
+      q.mp_iters = w[kLoMpIters];
+      std::memcpy(&q.aft, w + kLoAft, sizeof(loam_pose6));
+      std::memcpy(&q.bef, w + kLoBef, sizeof(loam_pose6));
+      q.n_registered = (uint32_t)w[kLoNReg];
+      L.nreg[l] = q.n_registered;
+    }
+  }
+  L.have_reg = L.step_mapped != 0;
+  return LOAM_OK;
+}
+
+extern "C" int loam_lanes_registered(loam_ctx* x, uint32_t lane, loam_cloud_out* out) {
+  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_registered: lanes are not open");
+  if (lane >= (uint32_t)L.S) return fail(LOAM_E_INVAL, "loam_lanes_registered: lane index out of range");
+  if (L.in_flight || !L.have_reg)
+    return fail(LOAM_E_INVAL, "loam_lanes_registered: the last pulled step did not map (or a step is in flight)");
+  if (L.fail[lane] != LOAM_OK) return fail(LOAM_E_INVAL, "loam_lanes_registered: the lane has failed");
+  const int n = (int)L.nreg[lane];
+  if (n > 0 && (uint32_t)n <= out->capacity && !out->pts)
+    return fail(LOAM_E_INVAL, "loam_lanes_registered: out->pts is null");
+  HIP_TRY(hipSetDevice(x->device));
+  x->pin.reset();
+  const int rc = copy_out(x->st, x->pin, L.mp.reg + (size_t)lane * L.mp.capS, n, out);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(x->st));
+  x->pin.finish();
+  return LOAM_OK;
+}
+
+extern "C" int loam_lanes_map_export(loam_ctx* x, uint32_t lane, loam_map* out) {
+  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_map_export: lanes are not open");
+  if (lane >= (uint32_t)L.S) return fail(LOAM_E_INVAL, "loam_lanes_map_export: lane index out of range");
+  if (L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_map_export: a step is in flight (loam_lanes_pull first)");
+  if (L.fail[lane] != LOAM_OK) return fail(LOAM_E_INVAL, "loam_lanes_map_export: the lane has failed");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipStreamSynchronize(x->st));
+  return map_export_of(x, L.mp, (int)lane, L.map_frame_count, out);
 }
 
 namespace loam {

@@ -2556,10 +2556,12 @@ struct MapPose {
 };
 
 template <int NT>
-__global__ __launch_bounds__(NT) void k_mp_map_table(MpBuffers b, int* tab) {
+__global__ __launch_bounds__(NT) void k_mp_map_table(MpBuffers b, int* tab, int inst) {
   constexpr int N = kMapKeys, E = (N + NT - 1) / NT;
   const int tid = threadIdx.x;
-  const int* slots = slot_table(b, b.pool_cur, 0);
+  const int* slots = slot_table(b, b.pool_cur, inst);
+  const int* ist = b.istate + (size_t)inst * kMpStateInts;
+  const float* fst = b.state + (size_t)inst * kMpStateFloats;
   __shared__ int nn[N];
   __shared__ int scratch[NT / 64 + 1];
   for (int x = tid; x < N; x += NT) {
@@ -2582,25 +2584,26 @@ __global__ __launch_bounds__(NT) void k_mp_map_table(MpBuffers b, int* tab) {
   __syncthreads();
   for (int x = tid; x < N; x += NT) tab[kMapTabOff + x] = nn[x];
   if (tid == 0) tab[kMapTabOff + N] = run;
-  if (tid < 3) tab[kMapTabInfo + tid] = b.istate[kMiCenW + tid];
-  if (tid == 3) tab[kMapTabInfo + 3] = b.istate[kMiErr];
+  if (tid < 3) tab[kMapTabInfo + tid] = ist[kMiCenW + tid];
+  if (tid == 3) tab[kMapTabInfo + 3] = ist[kMiErr];
   if (tid >= 64 && tid < 76) {
     const int k = tid - 64;
-    tab[kMapTabInfo + 4 + k] = __float_as_int(b.state[(k < 6 ? kMpAft : kMpBef - 6) + k]);
+    tab[kMapTabInfo + 4 + k] = __float_as_int(fst[(k < 6 ? kMpAft : kMpBef - 6) + k]);
   }
 }
 
 // output point i of the canonical order: its key by binary search over the offsets (LDS), its
 // source pool[src[key] + i - off[key]].  Four points per lane, all four loads before the stores.
-__global__ __launch_bounds__(256) void k_mp_map_pack(MpBuffers b, const int* tab, int total) {
+// inst: the instance whose store is packed, into its own map_cap points of vin
+__global__ __launch_bounds__(256) void k_mp_map_pack(MpBuffers b, const int* tab, int total, int inst) {
   constexpr int N = kMapKeys;
   __shared__ int off[N + 1];
   const int tid = threadIdx.x;
   for (int x = tid; x <= N; x += 256) off[x] = tab[kMapTabOff + x];
   __syncthreads();
-  const float4* pool = b.pool + (size_t)b.pool_cur * b.P * b.map_cap;
+  const float4* pool = b.pool + ((size_t)b.pool_cur * b.P + inst) * b.map_cap;
   const int* src = tab + kMapTabSrc;
-  float4* dst = b.vin;
+  float4* dst = b.vin + (size_t)inst * b.map_cap;
   for (int base = blockIdx.x * 1024; base < total; base += gridDim.x * 1024) {
     // the source index of output point i (clamped: the lanes past the end load a valid point)
     auto locate = [&](int i) {
@@ -2890,8 +2893,9 @@ void mp_map_free(MapIo& io) {
   io.tab = io.tab_h = nullptr;
 }
 
-hipError_t mp_map_table(MpBuffers& b, MapIo& io, hipStream_t st, Prof* prof) {
-  hipLaunchKernelGGL(k_mp_map_table<1024>, dim3(1), dim3(1024), 0, st, b, io.tab);
+hipError_t mp_map_table(MpBuffers& b, MapIo& io, hipStream_t st, Prof* prof, int inst) {
+  if (inst < 0 || inst >= b.P) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_mp_map_table<1024>, dim3(1), dim3(1024), 0, st, b, io.tab, inst);
   if (prof) prof->mark("k_mp_map_table");
   hipError_t e = hipGetLastError();
   if (e == hipSuccess)
@@ -2900,11 +2904,11 @@ hipError_t mp_map_table(MpBuffers& b, MapIo& io, hipStream_t st, Prof* prof) {
   return e;
 }
 
-hipError_t mp_map_pack(MpBuffers& b, MapIo& io, int total, hipStream_t st, Prof* prof) {
+hipError_t mp_map_pack(MpBuffers& b, MapIo& io, int total, hipStream_t st, Prof* prof, int inst) {
   if (total <= 0) return hipSuccess;
-  if (total > b.map_cap) return hipErrorInvalidValue;  // (vin holds map_cap points)
+  if (total > b.map_cap || inst < 0 || inst >= b.P) return hipErrorInvalidValue;  // (vin holds map_cap points per instance)
   const int grid = std::min((total + 1023) / 1024, 2048);
-  hipLaunchKernelGGL(k_mp_map_pack, dim3(grid), dim3(256), 0, st, b, io.tab, total);
+  hipLaunchKernelGGL(k_mp_map_pack, dim3(grid), dim3(256), 0, st, b, io.tab, total, inst);
   if (prof) prof->mark("k_mp_map_pack");
   return hipGetLastError();
 }

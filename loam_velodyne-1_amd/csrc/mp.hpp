@@ -176,7 +176,8 @@ void mp_batch_frame2(MpBuffers& b, const OdBuffers& od, int buf, const FeatView&
 int mp_batch_download(MpBuffers& b, hipStream_t st, loam_pose6* aft, loam_stats* stats, std::string& err);
 hipError_t mp_batch_iters(MpBuffers& b, hipStream_t st, int32_t* iters);
 
-// ---- map export / import of a streaming store (instance 0; loam_map_export / loam_map_import) ----
+// ---- map export / import of a streaming store (loam_map_export / loam_map_import: instance 0;
+// loam_lanes_map_export: the export of instance `inst` of the lanes' store) ----
 // Canonical order: key = kind * kCubeNum + cube (kind 0 corner, 1 surf), ascending; inside a key
 // the store's own point order.  The small tables both calls need live in one device block (`tab`,
 // ints) with a pinned host copy of its head; the point scratch is the store's own idle buffers
@@ -201,10 +202,10 @@ hipError_t mp_map_ensure(MapIo& io);  // allocated by the first call
 void mp_map_free(MapIo& io);
 // export: the canonical offsets, the centre and the poses into io.tab (k_mp_map_table), copied to
 // io.tab_h; the caller synchronises st before reading it
-hipError_t mp_map_table(MpBuffers& b, MapIo& io, hipStream_t st, Prof* prof);
-// export: the store's points in canonical order into b.vin[0 .. total) (k_mp_map_pack); total =
-// tab_h[kMapKeys]
-hipError_t mp_map_pack(MpBuffers& b, MapIo& io, int total, hipStream_t st, Prof* prof);
+hipError_t mp_map_table(MpBuffers& b, MapIo& io, hipStream_t st, Prof* prof, int inst = 0);
+// export: the store's points in canonical order into the instance's part of vin,
+// b.vin[inst * map_cap ..) (k_mp_map_pack); total = tab_h[kMapKeys]
+hipError_t mp_map_pack(MpBuffers& b, MapIo& io, int total, hipStream_t st, Prof* prof, int inst = 0);
 // import: zeroes the accumulators and the per-key counts
 hipError_t mp_map_bin_begin(MpBuffers& b, MapIo& io, hipStream_t st);
 // import: n <= kMapChunkPts points of one kind (device memory, 16-byte aligned): the kept ones
