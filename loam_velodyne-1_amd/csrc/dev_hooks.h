@@ -48,6 +48,40 @@ int loam_dev_vg_run(loam_dev_vg* h, const loam_dev_vg_job* job, float* out_pts, 
 
 int loam_dev_vg_destroy(loam_dev_vg* h);
 
+/* The mapping 5-NN search (mp.hip: mp_nn_seed_from + knn5_flat, and the plain knn5) on a caller's
+ * map points and queries: the map's 1 m voxel hash is built by the product's hash build, then one
+ * kernel runs both searches on every query from the same start. */
+typedef struct loam_dev_nn5 loam_dev_nn5;
+
+#define LOAM_DEV_NN5_MAX_MAP 16384
+#define LOAM_DEV_NN5_MAX_QUERIES 4096
+#define LOAM_DEV_NN5_BATCH 0  /* a lane per query, one-wave workgroups (k_mp_nnfit's form) */
+#define LOAM_DEV_NN5_STREAM 1 /* a lane group per query, lists merged (k_mp_lm_small / k_mp_lm_stream's form) */
+#define LOAM_DEV_NN5_OVERFLOW 1 /* flags: a lane of the query filled its pending list and inserted directly */
+#define LOAM_DEV_NN5_PLAIN 2    /* flags: the flat search fell back to the plain one */
+
+typedef struct {
+  const float* map;        /* [n_map][4] x, y, z, - */
+  int32_t n_map;           /* 1 .. LOAM_DEV_NN5_MAX_MAP */
+  const float* queries;    /* [n_queries][4] x, y, z, - (map frame) */
+  int32_t n_queries;       /* 1 .. LOAM_DEV_NN5_MAX_QUERIES */
+  const int32_t* seeds;    /* NULL: unseeded (a first iteration); else [n_queries][5] map indices */
+  const int32_t* distinct; /* NULL (every query's seeds count) or [n_queries]: 0 = that query starts unseeded */
+  int32_t form;            /* LOAM_DEV_NN5_* */
+} loam_dev_nn5_job;
+
+/* LOAM_E_HIP without a GPU, LOAM_E_NOMEM */
+int loam_dev_nn5_create(int device, loam_dev_nn5** out);
+
+/* flat_idx / flat_dist, plain_idx / plain_dist [n_queries][5]: the list of knn5_flat and of knn5,
+ * ascending: the map index (0x7fffffff: none) and the bits of the float squared distance.
+ * flags [n_queries] or NULL: LOAM_DEV_NN5_OVERFLOW | LOAM_DEV_NN5_PLAIN; counts [2]: the queries
+ * with each flag.  LOAM_E_INVAL for sizes out of range, a seed outside the map, an unknown form. */
+int loam_dev_nn5_run(loam_dev_nn5* h, const loam_dev_nn5_job* job, int32_t* flat_idx, uint32_t* flat_dist,
+                     int32_t* plain_idx, uint32_t* plain_dist, int32_t* flags, int32_t* counts);
+
+int loam_dev_nn5_destroy(loam_dev_nn5* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "dev_common.hpp"
+#include "dev_hooks.h"
 #include "mp.hpp"
 #include "od.hpp"
 #include "pose_math.hpp"
@@ -392,41 +393,37 @@ __global__ __launch_bounds__(256) void k_mp_gather(MpBuffers b) {
 }
 
 // ---------------------------------------------------------------- L-M
-struct Top5 {
-  float d[5];
-  int i[5];
-};
 // (distance, index) as one ordered 64-bit key: distances are >= +0, so their bits order as they do
 LOAM_D uint64_t top5_key(float d, int idx) { return ((uint64_t)__float_as_uint(d) << 32) | (uint32_t)idx; }
+// the five smallest keys so far, ascending; kept as keys, so no offer takes one apart or rebuilds it
+struct Top5 {
+  uint64_t K[5];
+  LOAM_D float d(int k) const { return __uint_as_float((uint32_t)(K[k] >> 32)); }
+  LOAM_D int i(int k) const { return (int)(uint32_t)K[k]; }
+};
+LOAM_D uint64_t top5_none() { return top5_key(3.4e38f, 0x7fffffff); }  // the sentinel: no point
 // sorted insertion of a key below K_4 (branch-free: lt_k = key < K_k is monotone in k, so slot k
 // takes K_{k-1} where lt_{k-1}, the key where lt_k alone, else keeps K_k)
-LOAM_D void top5_insert(Top5& t, const uint64_t (&K)[5], uint64_t key) {
+LOAM_D void top5_insert(Top5& t, uint64_t key) {
+  uint64_t(&K)[5] = t.K;
   const bool l0 = key < K[0], l1 = key < K[1], l2 = key < K[2], l3 = key < K[3];
-  const uint64_t N[5] = {l0 ? key : K[0], l0 ? K[0] : (l1 ? key : K[1]), l1 ? K[1] : (l2 ? key : K[2]),
-                         l2 ? K[2] : (l3 ? key : K[3]), l3 ? K[3] : key};
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    t.d[k] = __uint_as_float((uint32_t)(N[k] >> 32));
-    t.i[k] = (int)(uint32_t)N[k];
-  }
+  // (from the last slot down: each slot reads its lower neighbour before that one changes)
+  K[4] = l3 ? K[3] : key;
+  K[3] = l2 ? K[2] : (l3 ? key : K[3]);
+  K[2] = l1 ? K[1] : (l2 ? key : K[2]);
+  K[1] = l0 ? K[0] : (l1 ? key : K[1]);
+  K[0] = l0 ? key : K[0];
 }
 // an offer that cannot repeat a held point (the 5-NN candidate walk: every map point is listed
 // once, and a list seeded with copies of the bound B takes only keys below B)
-LOAM_D void top5_offer_new(Top5& t, float d, int idx) {
-  const uint64_t key = top5_key(d, idx);
-  uint64_t K[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) K[k] = top5_key(t.d[k], t.i[k]);
-  if (key < K[4]) top5_insert(t, K, key);
+LOAM_D void top5_offer_key(Top5& t, uint64_t key) {
+  if (key < t.K[4]) top5_insert(t, key);
 }
-LOAM_D void top5_offer(Top5& t, float d, int idx) {
+LOAM_D void top5_offer(Top5& t, uint64_t key) {
   // ascending (distance, index); a point already held is skipped (the merge of lists)
-  const uint64_t key = top5_key(d, idx);
-  uint64_t K[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) K[k] = top5_key(t.d[k], t.i[k]);
-  if (key < K[4] && key != K[0] && key != K[1] && key != K[2] && key != K[3]) top5_insert(t, K, key);
+  if (key < t.K[4] && key != t.K[0] && key != t.K[1] && key != t.K[2] && key != t.K[3]) top5_insert(t, key);
 }
+LOAM_D void top5_offer(Top5& t, float d, int idx) { top5_offer(t, top5_key(d, idx)); }
 
 // the 27 neighbour cells (index (dx+1) + 3(dy+1) + 9(dz+1)): centre, faces, edges, corners
 __constant__ int kCellOrder[27] = {13, 4, 10, 12, 14, 16, 22, 1, 3, 5, 7, 9, 11, 15, 17, 19, 21, 23, 25,
@@ -454,7 +451,7 @@ LOAM_D void knn5(const int* start, const float4* hp, int T, float4 q, Top5& t, i
     const float gy = dy < 0 ? gyl : (dy > 0 ? gyh : 0.0f);
     const float gz = dz < 0 ? gzl : (dz > 0 ? gzh : 0.0f);
     const float bd = sqdist(gx, gy, gz, 0.0f, 0.0f, 0.0f);
-    if (bd >= 1.0f || bd > t.d[4]) continue;
+    if (bd >= 1.0f || bd > t.d(4)) continue;
     const uint32_t h = cell_hash(cx + dx, cy + dy, cz + dz) & (uint32_t)(T - 1);
     const int b0 = start[h], b1 = start[h + 1];
     work += (b1 - b0) + (1 << kWorkCellShift);
@@ -504,14 +501,21 @@ constexpr int kNnRangeGroup = LOAM_NN_RANGE_GROUP;
 // L > 1: one of L lanes searching the same query: every lane lists the same cells, lane `sub`
 // takes the candidates sub, sub + L, ... of the concatenated list (a crowded cell is shared too);
 // the caller merges the L partial top-5 lists (knn5_merge)
+// pending keys per lane of a deferred walk (a seeded search has 4 to 5 keys below B on average, p99
+// 5 to 9, the oracle's clouds with the query moved 5 to 150 mm; more than 8 in under 2 % of queries)
+constexpr int kNnPending = 8;
+template <bool V>
+struct NnDefer { static constexpr bool value = V; };
+// diag (the test hook): which exceptional paths the lane took
+constexpr int kNnDiagOverflow = 1, kNnDiagPlain = 2;
 template <int S = kMpQueryThreads, int L = 1, int CAPL = 27>
 LOAM_D void knn5_flat(const int* start, const uint32_t* rec, const float4* hp, int T, float4 q, Top5& t,
-                      uint32_t* lst, int& work, int sub = 0) {
+                      uint32_t* lst, int& work, int sub = 0, int* diag = nullptr) {
   if (T <= 0) return;
   const int cx = cell_of(q.x, 1.0f), cy = cell_of(q.y, 1.0f), cz = cell_of(q.z, 1.0f);
   const float gxl = q.x - (float)cx, gyl = q.y - (float)cy, gzl = q.z - (float)cz;
   const float gxh = (float)(cx + 1) - q.x, gyh = (float)(cy + 1) - q.y, gzh = (float)(cz + 1) - q.z;
-  const float bound = t.d[4];
+  const float bound = t.d(4);
   int n = 0, total = 0;
   bool fits = true;
   // the range loads of a group of cells are all issued before any is used (a load whose count is
@@ -552,6 +556,7 @@ LOAM_D void knn5_flat(const int* start, const uint32_t* rec, const float4* hp, i
     }
   }
   if (!fits) {
+    if (diag) *diag |= kNnDiagPlain;
     knn5(start, hp, T, q, t, work);
     return;
   }
@@ -582,26 +587,69 @@ LOAM_D void knn5_flat(const int* start, const uint32_t* rec, const float4* hp, i
   };
   const int mine = L == 1 ? total : (total > sub ? (total - sub + L - 1) / L : 0);
   if (L > 1 && mine > 0) skip(sub);  // (mine > 0: the list holds more than sub candidates)
-  for (int k = 0; k < mine; k += kNnInFlight) {  // independent gathers in flight per step
-    int idx[kNnInFlight];
+  // Deferred insertion.  A seeded list is five copies of the bound B and ends as the five smallest
+  // of {keys below B} and copies of B, whatever the order of the offers.  So the walk only tests
+  // key < B and appends a passing key to the lane's pending list; the sorted insertions follow the
+  // walk and run to the wave's largest pending count (a handful) instead of on nearly every
+  // candidate step (some lane of 64 inserts at almost each).  Pending key j lies in the entries
+  // CAPL - 2 - 2j (low word) and CAPL - 1 - 2j (high word) of the lane's own column, above the n
+  // ranges listed; a lane whose pending list is full inserts its further keys directly, which
+  // is as exact.  The wave defers when any of its lanes is seeded: an unseeded lane among them has
+  // B = the sentinel, appends its first keys and inserts the rest.  A wave of unseeded lanes
+  // (the first iteration) inserts directly: every candidate would pass the test there.
+#ifdef LOAM_NN_NO_DEFER  // (experiment build: every walk inserts directly)
+  const bool deferred = false;
+#else
+  const bool deferred = __builtin_amdgcn_ballot_w64(t.K[4] != top5_none()) != 0;
+#endif
+  constexpr int kPend0 = (CAPL - 2) * S;                                        // pending key 0 (offsets into lst)
+  const int pend_full = kPend0 - 2 * S * min(kNnPending, (CAPL - n) >> 1);  // the first key that does not fit
+  int pend = kPend0;
+  auto walk = [&](auto defer) {
+    for (int k = 0; k < mine; k += kNnInFlight) {  // independent gathers in flight per step
+      int idx[kNnInFlight];
 #pragma unroll
-    for (int u = 0; u < kNnInFlight; ++u) {
-      if (k + u < mine) {
-        idx[u] = next();
-        if (L > 1 && k + u + 1 < mine) skip(L - 1);
-      } else {
-        idx[u] = idx[0];
+      for (int u = 0; u < kNnInFlight; ++u) {
+        if (k + u < mine) {
+          idx[u] = next();
+          if (L > 1 && k + u + 1 < mine) skip(L - 1);
+        } else {
+          idx[u] = idx[0];
+        }
+      }
+#ifdef LOAM_BOUNDS_CHECK
+      for (int u = 0; u < kNnInFlight; ++u) LOAM_CHECK(idx[u] >= 0 && idx[u] < (1 << 19) + (1 << 13), idx[u], total);
+#endif
+      float4 a[kNnInFlight];
+#pragma unroll
+      for (int u = 0; u < kNnInFlight; ++u) a[u] = hp[(uint32_t)idx[u]];
+#pragma unroll
+      for (int u = 0; u < kNnInFlight; ++u) {
+        if (k + u >= mine) continue;
+        const uint64_t key = top5_key(sqdist(a[u].x, a[u].y, a[u].z, q.x, q.y, q.z), __builtin_bit_cast(int, a[u].w));
+        if constexpr (decltype(defer)::value) {
+          if (key < t.K[4]) {  // (= B until the lane inserts directly)
+            if (pend != pend_full) {
+              lst[pend] = (uint32_t)key;
+              lst[pend + S] = (uint32_t)(key >> 32);
+              pend -= 2 * S;
+            } else {
+              if (diag) *diag |= kNnDiagOverflow;
+              top5_offer_key(t, key);
+            }
+          }
+        } else {
+          top5_offer_key(t, key);
+        }
       }
     }
-#ifdef LOAM_BOUNDS_CHECK
-    for (int u = 0; u < kNnInFlight; ++u) LOAM_CHECK(idx[u] >= 0 && idx[u] < (1 << 19) + (1 << 13), idx[u], total);
-#endif
-    float4 a[kNnInFlight];
-#pragma unroll
-    for (int u = 0; u < kNnInFlight; ++u) a[u] = hp[idx[u]];
-#pragma unroll
-    for (int u = 0; u < kNnInFlight; ++u)
-      if (k + u < mine) top5_offer_new(t, sqdist(a[u].x, a[u].y, a[u].z, q.x, q.y, q.z), __builtin_bit_cast(int, a[u].w));
+  };
+  if (deferred) {
+    walk(NnDefer<true>{});
+    for (int pj = kPend0; pj != pend; pj -= 2 * S)  // (the wave's largest pending count)
+      top5_offer_key(t, ((uint64_t)lst[pj + S] << 32) | lst[pj]);
+  } else {
+    walk(NnDefer<false>{});
   }
 }
 
@@ -617,8 +665,8 @@ LOAM_D void knn5_merge(Top5& t) {
     int oi[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-      od[k] = __shfl_xor(t.d[k], m, 64);
-      oi[k] = __shfl_xor(t.i[k], m, 64);
+      od[k] = __shfl_xor(t.d(k), m, 64);
+      oi[k] = __shfl_xor(t.i(k), m, 64);
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k)
@@ -701,8 +749,7 @@ LOAM_D MpNnCtx mp_nn_ctx(const MpBuffers& b, int p) {
 // previous iteration's ordered 5-NN (i0..i3 | i4, -, distinct) when !first
 LOAM_D void mp_nn_seed_from(const MpNnCtx& c, int q, bool corner, bool first, int4 n0, int4 n1, float4 sel, Top5& t,
                             int& work) {
-  float bd = 3.4e38f;
-  int bi = 0x7fffffff;
+  uint64_t start = top5_none();
   if (!first) {
     // The previous iteration's five neighbours (when they were five distinct points, n1.z) bound the
     // search: B = the largest of their (distance, index) keys at the moved query.  The list starts
@@ -722,12 +769,11 @@ LOAM_D void mp_nn_seed_from(const MpNnCtx& c, int q, bool corner, bool first, in
         B = key > B ? key : B;
       }
       work += 5;
-      bd = __uint_as_float((uint32_t)(B >> 32));
-      bi = (int)(uint32_t)B;
+      start = B;
     }
   }
 #pragma unroll
-  for (int k = 0; k < 5; ++k) { t.d[k] = bd; t.i[k] = bi; }
+  for (int k = 0; k < 5; ++k) t.K[k] = start;
 }
 
 LOAM_D void mp_nn_seed(const MpNnCtx& c, int q, bool corner, bool first, float4 sel, Top5& t, int& work) {
@@ -739,12 +785,12 @@ LOAM_D void mp_nn_seed(const MpNnCtx& c, int q, bool corner, bool first, float4 
 // the seeds for the next iteration only when the list holds five distinct map points (a rejected
 // search can end with copies of B or sentinels; the list is sorted, so copies are adjacent)
 LOAM_D int top5_distinct(const Top5& t) {
-  return t.i[4] != 0x7fffffff && t.i[0] != t.i[1] && t.i[1] != t.i[2] && t.i[2] != t.i[3] && t.i[3] != t.i[4];
+  return t.i(4) != 0x7fffffff && t.i(0) != t.i(1) && t.i(1) != t.i(2) && t.i(2) != t.i(3) && t.i(3) != t.i(4);
 }
 
 LOAM_D void mp_nn_store(const MpNnCtx& c, int q, const Top5& t) {
-  c.qnn[2 * q] = make_int4(t.i[0], t.i[1], t.i[2], t.i[3]);
-  c.qnn[2 * q + 1] = make_int4(t.i[4], __float_as_int(t.d[4]), top5_distinct(t), 0);
+  c.qnn[2 * q] = make_int4(t.i(0), t.i(1), t.i(2), t.i(3));
+  c.qnn[2 * q + 1] = make_int4(t.i(4), __float_as_int(t.d(4)), top5_distinct(t), 0);
 }
 
 template <int S = kMpQueryThreads, int L = 1, int CAPL = 27>
@@ -756,7 +802,7 @@ LOAM_D void mp_nn_query(const MpBuffers& b, const MpNnCtx& c, int q, int nsc, bo
   if (corner) knn5_flat<S, L, CAPL>(c.hcs, c.hcr, c.hcp, c.TC, sel, t, lst, work, sub);
   else knn5_flat<S, L, CAPL>(c.hss, c.hsr, c.hsp, c.TS, sel, t, lst, work, sub);
   if constexpr (L > 1) knn5_merge<L>(t);
-  LOAM_CHECK(q < b.cap_stack && (t.i[4] == 0x7fffffff || t.i[4] < (corner ? c.nfc : c.nfs)), q, t.i[4]);
+  LOAM_CHECK(q < b.cap_stack && (t.i(4) == 0x7fffffff || t.i(4) < (corner ? c.nfc : c.nfs)), q, t.i(4));
   if (sub == 0) mp_nn_store(c, q, t);
 }
 
@@ -872,6 +918,15 @@ LOAM_D MpTrig mp_trig_of(const float* trig) { return {trig[0], trig[1], trig[2],
 // without the serial double sin / cos in the kernel prologue
 LOAM_D MpTrig mp_trig_of(const loampose::MapRot& r) {
   return {(float)r.s0, (float)r.c0, (float)r.s1, (float)r.c1, (float)r.s2, (float)r.c2};
+}
+
+// The six values as one place in a loop sees them: the products of them that mp_row_jac forms
+// are the same for every query, and the compiler would otherwise keep each in a vector register
+// across the whole loop over the queries (k_mp_nnfit has none to spare); so they are formed
+// where they are used
+LOAM_D MpTrig mp_trig_here(MpTrig t) {
+  asm volatile("" : "+v"(t.srx), "+v"(t.crx), "+v"(t.sry), "+v"(t.cry), "+v"(t.srz), "+v"(t.crz));
+  return t;
 }
 
 // the accepted row's J (:897-921): a[0..5] and b = -coefficient.w
@@ -1045,7 +1100,7 @@ __global__ __launch_bounds__(kMpFitThreads) __attribute__((amdgpu_waves_per_eu(L
   float4* qcf = b.q_cf + (size_t)p * b.cap_stack;
   const loampose::MapRot r = rot_load(b, p);
   const MpNnCtx c = mp_nn_ctx(b, p);
-  const MpTrig tg = mp_trig_of(r);
+  const MpTrig tg0 = mp_trig_of(r);
   float* jw = (float*)lds + tid * 27;
   int nfits = 0, work = 0;
   // FUSED: the rows of each pass over the queries are reduce-scattered over the wave at once (no
@@ -1085,8 +1140,17 @@ __global__ __launch_bounds__(kMpFitThreads) __attribute__((amdgpu_waves_per_eu(L
       if (!first) { r0 = qrec[q].n0; r1 = qrec[q].n1; }
       sel = loampose::point_to_map(r, o);
       mp_nn_seed_from(c, q, corner, first, r0, r1, sel, t, work);
-      if (corner) knn5_flat<NT, 1, kNnListCap>(c.hcs, c.hcr, c.hcp, c.TC, sel, t, lds + tid, work, 0);
-      else knn5_flat<NT, 1, kNnListCap>(c.hss, c.hsr, c.hsp, c.TS, sel, t, lds + tid, work, 0);
+#ifdef LOAM_DIAG_OVERFLOW  // (diagnostic build: the queries that overflowed their pending list, in mp_fits >> 20)
+      int dg = 0;
+      int* const diag = &dg;
+#else
+      int* const diag = nullptr;
+#endif
+      if (corner) knn5_flat<NT, 1, kNnListCap>(c.hcs, c.hcr, c.hcp, c.TC, sel, t, lds + tid, work, 0, diag);
+      else knn5_flat<NT, 1, kNnListCap>(c.hss, c.hsr, c.hsp, c.TS, sel, t, lds + tid, work, 0, diag);
+#ifdef LOAM_DIAG_OVERFLOW
+      if (dg & kNnDiagOverflow) nfits += 1 << 20;
+#endif
 #ifdef LOAM_DIAG_SEARCH2  // (diagnostic build: the search twice, its cost measured by the difference)
       {
         Top5 t2;
@@ -1095,22 +1159,22 @@ __global__ __launch_bounds__(kMpFitThreads) __attribute__((amdgpu_waves_per_eu(L
         mp_nn_seed_from(c, q, corner, first, r0, r1, sel, t2, w2);
         if (corner) knn5_flat<NT, 1, kNnListCap>(c.hcs, c.hcr, c.hcp, c.TC, sel, t2, lds + tid, w2, 0);
         else knn5_flat<NT, 1, kNnListCap>(c.hss, c.hsr, c.hsp, c.TS, sel, t2, lds + tid, w2, 0);
-        if (t2.i[0] != t.i[0]) nfits += 1 << 20;
+        if (t2.i(0) != t.i(0)) nfits += 1 << 20;
       }
 #endif
-      LOAM_CHECK(q < b.cap_stack && (t.i[4] == 0x7fffffff || t.i[4] < (corner ? c.nfc : c.nfs)), q, t.i[4]);
+      LOAM_CHECK(q < b.cap_stack && (t.i(4) == 0x7fffffff || t.i(4) < (corner ? c.nfc : c.nfs)), q, t.i(4));
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();  // every lane's list reads are done before the scratch reuse
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     if (q < nq) {
-      const int4 n0 = make_int4(t.i[0], t.i[1], t.i[2], t.i[3]);
+      const int4 n0 = make_int4(t.i(0), t.i(1), t.i(2), t.i(3));
       // the stored fit is this list's when the list is unchanged and the fit was made (a fit is
       // a function of the five map points alone: reusing it is bit-identical to refitting)
       bool valid = !first && r1.w && r0.x == n0.x && r0.y == n0.y && r0.z == n0.z && r0.w == n0.w &&
-                   r1.x == t.i[4];
+                   r1.x == t.i(4);
       int ok = 0;
-      if (t.i[4] != 0x7fffffff && D(t.d[4]) < 1.0) {  // :719, :826
+      if (t.i(4) != 0x7fffffff && D(t.d(4)) < 1.0) {  // :719, :826
         float4 g0, g1;
         if (valid) {
           g0 = qrec[q].g0;
@@ -1121,8 +1185,8 @@ __global__ __launch_bounds__(kMpFitThreads) __attribute__((amdgpu_waves_per_eu(L
           float4 nb[5];
 #pragma unroll
           for (int k = 0; k < 5; ++k) {
-            LOAM_CHECK(t.i[k] >= 0 && t.i[k] < (corner ? c.nfc : c.nfs), t.i[k], q);
-            nb[k] = from[t.i[k]];
+            LOAM_CHECK(t.i(k) >= 0 && t.i(k) < (corner ? c.nfc : c.nfs), t.i(k), q);
+            nb[k] = from[t.i(k)];
           }
           mp_fit_compute(corner, nb, jw, g0, g1);
 #ifdef LOAM_DIAG_FIT2  // (diagnostic build: every fit twice)
@@ -1141,7 +1205,7 @@ __global__ __launch_bounds__(kMpFitThreads) __attribute__((amdgpu_waves_per_eu(L
       }
       // the record is written only when it changes: a reused fit's list is the stored one (the
       // next iteration's seeds and reuse test read indices and flags only)
-      const int4 n1 = make_int4(t.i[4], 0, top5_distinct(t), valid ? 1 : 0);
+      const int4 n1 = make_int4(t.i(4), 0, top5_distinct(t), valid ? 1 : 0);
       if (first || r0.x != n0.x || r0.y != n0.y || r0.z != n0.z || r0.w != n0.w || r1.x != n1.x || r1.z != n1.z ||
           r1.w != n1.w) {
         qrec[q].n0 = n0;
@@ -1157,6 +1221,7 @@ __global__ __launch_bounds__(kMpFitThreads) __attribute__((amdgpu_waves_per_eu(L
       // the pass's rows through LDS (8 floats per lane: J, b, 1 when accepted, else zeros), then
       // lane 2t sums term t over the wave's rows in query order: no 28 fp64 sums per lane
       float a6[6] = {0, 0, 0, 0, 0, 0}, bb = 0.0f;
+      const MpTrig tg = mp_trig_here(tg0);
       if (row_ok) mp_row_jac(tg, o, cf, a6, bb);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __builtin_amdgcn_wave_barrier();  // the fits' scratch reads are done
@@ -1311,8 +1376,8 @@ __global__ __launch_bounds__(kMpQueryThreads) void k_mp_lm_small(MpBuffers b) {
     float4 cf = make_float4(0, 0, 0, 0);
     int ok = 0;
     if (sub == 0) {
-      mp_fit_query(b, p, q, nsc, first, make_int4(t.i[0], t.i[1], t.i[2], t.i[3]),
-                   make_int4(t.i[4], __float_as_int(t.d[4]), 0, 0), sel, jac[tid], nfits, cf, ok);
+      mp_fit_query(b, p, q, nsc, first, make_int4(t.i(0), t.i(1), t.i(2), t.i(3)),
+                   make_int4(t.i(4), __float_as_int(t.d(4)), 0, 0), sel, jac[tid], nfits, cf, ok);
       qok[q] = (int8_t)ok;
       qcf[q] = cf;
       if (ok) mp_row_accum(tg, stack[q < nsc ? q : b.capC + (q - nsc)], cf, acc);
@@ -1480,8 +1545,8 @@ __global__ __launch_bounds__(kMpQueryThreads) void k_mp_lm_stream(MpBuffers b) {
       float4 cf = make_float4(0, 0, 0, 0);
       int ok = 0;
       if (sub == 0) {
-        mp_fit_query(b, p, q, nsc, first, make_int4(t.i[0], t.i[1], t.i[2], t.i[3]),
-                     make_int4(t.i[4], __float_as_int(t.d[4]), 0, 0), sel, jac[tid], nfits, cf, ok);
+        mp_fit_query(b, p, q, nsc, first, make_int4(t.i(0), t.i(1), t.i(2), t.i(3)),
+                     make_int4(t.i(4), __float_as_int(t.d(4)), 0, 0), sel, jac[tid], nfits, cf, ok);
         qok[q] = (int8_t)ok;
         qcf[q] = cf;
         if (ok) mp_row_accum(tg, stack[q < nsc ? q : b.capC + (q - nsc)], cf, acc);
@@ -3263,7 +3328,231 @@ int mp_batch_download(MpBuffers& b, hipStream_t st, loam_pose6* aft, loam_stats*
   return LOAM_OK;
 }
 
+// ---------------------------------------------------------------- the 5-NN search's diagnostic hook
+namespace {
+struct DevNn5 {
+  MpNnCtx c;           // the map as the corner cloud (fromC, hcs / hcr / hcp, TC), nfc = its size
+  const float4* qs;    // [nq] queries
+  const int* seeds;    // [nq][5] or nullptr
+  const int* distinct; // [nq] or nullptr
+  int nq;
+  int4* flat;          // [nq][3]: (i0..i3), (i4, d0, d1, d2), (d3, d4, -, -)
+  int4* plain;
+  int* flags;          // [nq], zeroed
+};
+LOAM_D void dev_nn5_store(int4* out, int q, const Top5& t) {
+  out[3 * q + 0] = make_int4(t.i(0), t.i(1), t.i(2), t.i(3));
+  out[3 * q + 1] = make_int4(t.i(4), __float_as_int(t.d(0)), __float_as_int(t.d(1)), __float_as_int(t.d(2)));
+  out[3 * q + 2] = make_int4(__float_as_int(t.d(3)), __float_as_int(t.d(4)), 0, 0);
+}
+// the query's start as an L-M iteration makes it: the stored previous 5-NN and their distinct flag
+LOAM_D void dev_nn5_seed(const DevNn5& d, int q, float4 sel, Top5& t, int& work) {
+  const bool first = d.seeds == nullptr;
+  int4 n0 = make_int4(0, 0, 0, 0), n1 = n0;
+  if (!first) {
+    const int* s = d.seeds + 5 * q;
+    n0 = make_int4(s[0], s[1], s[2], s[3]);
+    n1 = make_int4(s[4], 0, d.distinct ? d.distinct[q] : 1, 0);
+  }
+  mp_nn_seed_from(d.c, q, true, first, n0, n1, sel, t, work);
+}
+// k_mp_nnfit's form: a lane per query, one-wave workgroups, the lists in the workgroup's LDS array
+__global__ __launch_bounds__(kMpFitThreads) void k_dev_nn5_batch(DevNn5 d) {
+  constexpr int NT = kMpFitThreads;
+  __shared__ uint32_t lds[kNnListCap * NT];
+  const int tid = threadIdx.x, q = blockIdx.x * NT + tid;
+  if (q >= d.nq) return;
+  const float4 sel = d.qs[q];
+  int work = 0, diag = 0;
+  Top5 t;
+  dev_nn5_seed(d, q, sel, t, work);
+  knn5_flat<NT, 1, kNnListCap>(d.c.hcs, d.c.hcr, d.c.hcp, d.c.TC, sel, t, lds + tid, work, 0, &diag);
+  dev_nn5_store(d.flat, q, t);
+  if (diag) atomicOr(&d.flags[q], diag);
+  dev_nn5_seed(d, q, sel, t, work);
+  knn5(d.c.hcs, d.c.hcp, d.c.TC, sel, t, work);
+  dev_nn5_store(d.plain, q, t);
+}
+// k_mp_lm_small's form (mp_nn_query): kMpNnLanes lanes per query, their lists merged
+__global__ __launch_bounds__(kMpQueryThreads) void k_dev_nn5_stream(DevNn5 d) {
+  constexpr int L = kMpNnLanes, QPB = kMpQueryThreads / L;
+  __shared__ uint32_t lists[27 * kMpQueryThreads];
+  const int tid = threadIdx.x, sub = tid % L;
+  // (whole lane groups: a group's lanes exchange their lists, so none may leave early)
+  for (int q = blockIdx.x * QPB + tid / L; q < d.nq; q += gridDim.x * QPB) {
+    const float4 sel = d.qs[q];
+    int work = 0, diag = 0;
+    Top5 t;
+    dev_nn5_seed(d, q, sel, t, work);
+    knn5_flat<kMpQueryThreads, L>(d.c.hcs, d.c.hcr, d.c.hcp, d.c.TC, sel, t, lists + tid, work, sub, &diag);
+    if constexpr (L > 1) knn5_merge<L>(t);
+    if (diag) atomicOr(&d.flags[q], diag);
+    if (sub == 0) {
+      dev_nn5_store(d.flat, q, t);
+      dev_nn5_seed(d, q, sel, t, work);
+      knn5(d.c.hcs, d.c.hcp, d.c.TC, sel, t, work);
+      dev_nn5_store(d.plain, q, t);
+    }
+  }
+}
+}  // namespace
+
 }  // namespace loam
+
+struct loam_dev_nn5 {
+  int device = 0;
+  hipStream_t st = nullptr;
+  float4 *map = nullptr, *hpts = nullptr, *hpts2 = nullptr, *qs = nullptr;
+  int *start = nullptr, *start2 = nullptr, *fill = nullptr, *fill2 = nullptr, *count = nullptr, *tsize = nullptr;
+  uint32_t *rec = nullptr, *rec2 = nullptr;
+  int *seeds = nullptr, *distinct = nullptr, *flags = nullptr;
+  int4 *flat = nullptr, *plain = nullptr;
+};
+
+namespace {
+void dev_nn5_free(loam_dev_nn5* h) {
+  void* ptrs[] = {h->map, h->hpts, h->hpts2, h->qs, h->start, h->start2, h->fill, h->fill2, h->count, h->tsize,
+                  h->rec, h->rec2, h->seeds, h->distinct, h->flags, h->flat, h->plain};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  if (h->st) (void)hipStreamDestroy(h->st);
+  delete h;
+}
+}  // namespace
+
+extern "C" int loam_dev_nn5_create(int device, loam_dev_nn5** out) {
+  if (!out) return LOAM_E_INVAL;
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return LOAM_E_HIP;  // (no CPU path, as loam_create)
+  if (device < 0 || device >= ndev) return LOAM_E_INVAL;
+  if (hipSetDevice(device) != hipSuccess) return LOAM_E_HIP;
+  loam_dev_nn5* h = new loam_dev_nn5();
+  h->device = device;
+  const size_t M = LOAM_DEV_NN5_MAX_MAP, Q = LOAM_DEV_NN5_MAX_QUERIES;
+  loam::DevAlloc A;
+  A(&h->map, M * sizeof(float4));
+  A(&h->hpts, M * sizeof(float4));
+  A(&h->hpts2, M * sizeof(float4));
+  A(&h->qs, Q * sizeof(float4));
+  A(&h->start, (M + 1) * sizeof(int));
+  A(&h->start2, (M + 1) * sizeof(int));
+  A(&h->fill, M * sizeof(int));
+  A(&h->fill2, M * sizeof(int));
+  A(&h->count, 2 * sizeof(int));
+  A(&h->tsize, 2 * sizeof(int));
+  A(&h->rec, M * sizeof(uint32_t));
+  A(&h->rec2, M * sizeof(uint32_t));
+  A(&h->seeds, Q * 5 * sizeof(int));
+  A(&h->distinct, Q * sizeof(int));
+  A(&h->flags, Q * sizeof(int));
+  A(&h->flat, Q * 3 * sizeof(int4));
+  A(&h->plain, Q * 3 * sizeof(int4));
+  hipError_t e = A.err;
+  if (e == hipSuccess) e = hipStreamCreate(&h->st);
+  if (e != hipSuccess) {
+    dev_nn5_free(h);
+    return e == hipErrorOutOfMemory ? LOAM_E_NOMEM : LOAM_E_HIP;
+  }
+  *out = h;
+  return LOAM_OK;
+}
+
+extern "C" int loam_dev_nn5_run(loam_dev_nn5* h, const loam_dev_nn5_job* job, int32_t* flat_idx, uint32_t* flat_dist,
+                                int32_t* plain_idx, uint32_t* plain_dist, int32_t* flags, int32_t* counts) {
+  using namespace loam;
+  if (!h || !job || !flat_idx || !flat_dist || !plain_idx || !plain_dist || !counts) return LOAM_E_INVAL;
+  const int nm = job->n_map, nq = job->n_queries;
+  if (!job->map || !job->queries || nm < 1 || nm > LOAM_DEV_NN5_MAX_MAP || nq < 1 || nq > LOAM_DEV_NN5_MAX_QUERIES)
+    return LOAM_E_INVAL;
+  if (job->form != LOAM_DEV_NN5_BATCH && job->form != LOAM_DEV_NN5_STREAM) return LOAM_E_INVAL;
+  if (job->distinct && !job->seeds) return LOAM_E_INVAL;
+  if (job->seeds)
+    for (int k = 0; k < 5 * nq; ++k)
+      if (job->seeds[k] < 0 || job->seeds[k] >= nm) return LOAM_E_INVAL;
+  hipStream_t st = h->st;
+  auto up = [&](void* d, const void* s, size_t bytes) { return hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, st); };
+  const int cnt2[2] = {nm, 0};  // (the hash build takes two clouds: the second one is empty)
+  hipError_t e = hipSetDevice(h->device);
+  if (e == hipSuccess) e = up(h->map, job->map, (size_t)nm * sizeof(float4));
+  if (e == hipSuccess) e = up(h->qs, job->queries, (size_t)nq * sizeof(float4));
+  if (e == hipSuccess) e = up(h->count, cnt2, sizeof(cnt2));
+  if (e == hipSuccess && job->seeds) e = up(h->seeds, job->seeds, (size_t)nq * 5 * sizeof(int));
+  if (e == hipSuccess && job->distinct) e = up(h->distinct, job->distinct, (size_t)nq * sizeof(int));
+  if (e == hipSuccess) e = hipMemsetAsync(h->flags, 0, (size_t)nq * sizeof(int), st);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    return LOAM_E_HIP;
+  }
+  // the map's index as mp_hash_from builds FromMap's (1 m cells, buckets kept to single cells, packed ranges)
+  HashJob hc;
+  hc.pts = h->map; hc.pts_stride = LOAM_DEV_NN5_MAX_MAP; hc.pts_off = nullptr; hc.pts_off_stride = 0;
+  hc.count = h->count; hc.count_stride_bytes = 2 * sizeof(int);
+  hc.start = h->start; hc.fill = h->fill; hc.out = h->hpts; hc.tsize = h->tsize; hc.tmax = LOAM_DEV_NN5_MAX_MAP;
+  hc.inv_h = 1.0f;
+  hc.shift = 0;
+  hc.chunks = nullptr;
+  hc.rec = h->rec;
+  HashJob hs = hc;
+  hs.count = h->count + 1; hs.start = h->start2; hs.fill = h->fill2; hs.out = h->hpts2; hs.tsize = h->tsize + 1;
+  hs.rec = h->rec2;
+  hash_build_pair(hc, hs, 1, st, false);
+  int T = 0;
+  e = hipMemcpyAsync(&T, h->tsize, sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return LOAM_E_HIP;
+  DevNn5 d;
+  d.c = MpNnCtx();
+  d.c.hcs = h->start; d.c.hcr = h->rec; d.c.hcp = h->hpts; d.c.TC = T;
+  d.c.fromC = h->map; d.c.nfc = nm;
+  d.qs = h->qs;
+  d.seeds = job->seeds ? h->seeds : nullptr;
+  d.distinct = job->distinct ? h->distinct : nullptr;
+  d.nq = nq;
+  d.flat = h->flat; d.plain = h->plain; d.flags = h->flags;
+  if (job->form == LOAM_DEV_NN5_BATCH) {
+    hipLaunchKernelGGL(k_dev_nn5_batch, dim3((nq + kMpFitThreads - 1) / kMpFitThreads), dim3(kMpFitThreads), 0, st, d);
+  } else {
+    constexpr int QPB = kMpQueryThreads / kMpNnLanes;
+    hipLaunchKernelGGL(k_dev_nn5_stream, dim3((nq + QPB - 1) / QPB), dim3(kMpQueryThreads), 0, st, d);
+  }
+  e = hipGetLastError();
+  std::vector<int4> of((size_t)nq * 3), op((size_t)nq * 3);
+  std::vector<int> fl((size_t)nq);
+  if (e == hipSuccess) e = hipMemcpyAsync(of.data(), h->flat, of.size() * sizeof(int4), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(op.data(), h->plain, op.size() * sizeof(int4), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(fl.data(), h->flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return LOAM_E_HIP;
+  auto unpack = [&](const std::vector<int4>& v, int32_t* idx, uint32_t* dist) {
+    for (int q = 0; q < nq; ++q) {
+      const int4 a = v[3 * q], b = v[3 * q + 1], c = v[3 * q + 2];
+      const int i5[5] = {a.x, a.y, a.z, a.w, b.x}, d5[5] = {b.y, b.z, b.w, c.x, c.y};
+      for (int k = 0; k < 5; ++k) {
+        idx[5 * q + k] = i5[k];
+        dist[5 * q + k] = (uint32_t)d5[k];
+      }
+    }
+  };
+  unpack(of, flat_idx, flat_dist);
+  unpack(op, plain_idx, plain_dist);
+  counts[0] = counts[1] = 0;
+  for (int q = 0; q < nq; ++q) {
+    if (flags) flags[q] = fl[q];
+    if (fl[q] & LOAM_DEV_NN5_OVERFLOW) ++counts[0];
+    if (fl[q] & LOAM_DEV_NN5_PLAIN) ++counts[1];
+  }
+  return LOAM_OK;
+}
+
+extern "C" int loam_dev_nn5_destroy(loam_dev_nn5* h) {
+  if (!h) return LOAM_E_INVAL;
+  (void)hipSetDevice(h->device);
+  if (h->st) (void)hipStreamSynchronize(h->st);
+  dev_nn5_free(h);
+  return LOAM_OK;
+}
 
 #ifdef LOAM_PHASES
 // the phase sums of the last-workgroup kernel of this file (PhaseAcc, dev_common.hpp); diagnostic
