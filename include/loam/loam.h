@@ -383,8 +383,10 @@ int loam_map_score(loam_ctx *ctx, const loam_cloud_out *corner, const loam_cloud
 
 /* ---- lanes: many independent sequences in lockstep (no reference equivalent) ----
  * n_lanes sequences in one context, each advanced by one sweep per step.  Lane l behaves exactly as
- * a fresh context that is fed lane l's sweeps through loam_chain_sweep, with no IMU message: the
- * same poses, registered clouds and map, bit for bit, whatever the other lanes do.  A step runs the
+ * a fresh context that receives lane l's IMU messages through loam_imu (loam_lanes_imu) and lane l's
+ * sweeps through loam_chain_sweep at lane l's stamps, in the same interleaving: the same poses,
+ * registered clouds, map and /imu_trans, bit for bit, whatever the other lanes do and whether or
+ * not they have an IMU.  A step runs the
  * batch's kernels on all lanes at once (one launch sequence per step, not per sequence) and keeps
  * what the streaming path keeps from sweep to sweep: the Last clouds, transformSum, the cube maps,
  * Bef / Aft.  system_delay, the odometry's init frame, skip_frame_num and the surround phase advance
@@ -395,7 +397,7 @@ int loam_map_score(loam_ctx *ctx, const loam_cloud_out *corner, const loam_cloud
  *     difference that was validated for one two-sweep problem only;
  *   - the persistent L-M kernels' workgroups wait on each other, and more than two of them running
  *     at once on one GPU can hang: a lanes step is safe beside any other context's work.
- * The streaming nodes, the batch and the IMU queues of the context are separate state and untouched;
+ * The streaming nodes, the batch and the context's own IMU queues (loam_imu) are separate state and untouched;
  * their entry points may be called whenever no lanes step is in flight. */
 #define LOAM_LANES_MAX 1024
 
@@ -430,6 +432,25 @@ int loam_lanes_open(loam_ctx *ctx, uint32_t n_lanes, uint32_t lane_map_capacity)
  * count = 0 is therefore how a lane that has run out of sweeps is retired.  Inside system_delay the
  * sweeps are not looked at, as in the node. */
 int loam_lanes_push(loam_ctx *ctx, double stamp, const loam_cloud_in *raw /* [n_lanes] */);
+/* loam_lanes_push with one sweep stamp per lane (recorded sequences do not share a clock);
+ * loam_lanes_push is the case of equal stamps.  The stamps matter only to lanes with IMU messages:
+ * the de-skew and mapping's roll / pitch blend look the queues up by them.  A null stamp array or
+ * a stamp that is not finite (either call): LOAM_E_INVAL, nothing is enqueued or counted. */
+int loam_lanes_push_stamped(loam_ctx *ctx, const double *stamp /* [n_lanes] */, const loam_cloud_in *raw /* [n_lanes] */);
+/* loam_imu for one lane: the message enters the lane's scanRegistration and laserMapping queues
+ * (on the host; the next push uploads the new entries).  A lane that never got a message runs
+ * without IMU; a lane may get its first message before any step.  From the first message of any
+ * lane on, a step in which some live lane has a message de-skews with the tile-parallel IMU form of
+ * the ring sort and runs k_lanes_imu; nothing of this is allocated or launched before.
+ * LOAM_E_INVAL: a null argument, lanes not open, lane >= n_lanes, a failed lane, a stamp below the
+ * lane's last one (the other lanes are unaffected), or a step in flight.  LOAM_E_NOMEM when the
+ * first message's allocation fails.  As with loam_imu, more than 200 messages between a lane's
+ * consumed pointer and its last message lap the queue and are outside the contract. */
+int loam_lanes_imu(loam_ctx *ctx, uint32_t lane, double stamp, const double quat_xyzw[4], const double lin_acc_xyz[3]);
+/* /imu_trans of every lane from the last pulled step, 12 floats per lane in loam_features.imu_trans
+ * order; zeros for a lane without IMU messages, a failed lane and a step inside system_delay.
+ * LOAM_E_INVAL while a step is in flight and before the first pull. */
+int loam_lanes_imu_trans(loam_ctx *ctx, float *out /* [n_lanes][12] */);
 /* Waits for the pushed step (its only synchronisation) and fills out[l] for every lane.  LOAM_OK
  * when the step ran, whatever the lanes report; LOAM_E_INVAL with nothing pushed. */
 int loam_lanes_pull(loam_ctx *ctx, loam_lane_out *out /* [n_lanes] */);

@@ -7,7 +7,7 @@ on one GPU:
     mapping(pose, corner, surf, full) laserMapping body  src/laserMapping.cpp:411-1097
     maintenance(sum, bef, aft)      transformMaintenance src/transformMaintenance.cpp:147-203
     batch_*                         config 4 (independent problems)
-    lanes_*                         many sequences in lockstep
+    lanes_*                         many sequences in lockstep (with IMU §23)
 
 There is no CPU path: without a GPU (or without the built library) every call raises.
 The package directory name contains '-', so import it with
@@ -185,7 +185,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_maintenance", "loam_chain_sweep",
            "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_map_localize", "loam_map_score", "loam_get_stats",
            "loam_lanes_open", "loam_lanes_push", "loam_lanes_pull", "loam_lanes_registered", "loam_lanes_map_export",
-           "loam_lanes_close",
+           "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -240,6 +240,9 @@ def lib():
         L.loam_lanes_registered.argtypes = [PP, ctypes.c_uint32, P(CloudOut)]
         L.loam_lanes_map_export.argtypes = [PP, ctypes.c_uint32, P(Map)]
         L.loam_lanes_close.argtypes = [PP]
+        L.loam_lanes_imu.argtypes = [PP, ctypes.c_uint32, ctypes.c_double, P(ctypes.c_double), P(ctypes.c_double)]
+        L.loam_lanes_push_stamped.argtypes = [PP, P(ctypes.c_double), P(CloudIn)]
+        L.loam_lanes_imu_trans.argtypes = [PP, P(ctypes.c_float)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -537,7 +540,8 @@ class Engine:
 
     def lanes_push(self, raws, stamp=0.0):
         """one step: raws[l] is lane l's next sweep ((n, >= 3) float array or a loam_cloud_in; an
-        empty array retires the lane).  Enqueues the step and returns (loam_lanes_push)."""
+        empty array retires the lane).  stamp: the sweeps' stamp, or a sequence of one stamp per
+        lane.  Enqueues the step and returns (loam_lanes_push / loam_lanes_push_stamped)."""
         if len(raws) != self.n_lanes:
             raise ValueError("one sweep per lane")
         a = (CloudIn * self.n_lanes)()
@@ -545,7 +549,26 @@ class Engine:
         for l, r in enumerate(raws):
             a[l], k = _cloud_in(r)
             keep.append(k)
-        _check(lib().loam_lanes_push(self.h, stamp, a))
+        if np.ndim(stamp) == 0:
+            _check(lib().loam_lanes_push(self.h, float(stamp), a))
+            return
+        if len(stamp) != self.n_lanes:
+            raise ValueError("one stamp per lane")
+        t = (ctypes.c_double * self.n_lanes)(*[float(v) for v in stamp])
+        _check(lib().loam_lanes_push_stamped(self.h, t, a))
+
+    def lanes_imu(self, lane, stamp, quat_xyzw, lin_acc):
+        """/imu/data of one lane (loam_lanes_imu): loam_imu for that lane's sequence"""
+        q = (ctypes.c_double * 4)(*[float(v) for v in quat_xyzw])
+        a = (ctypes.c_double * 3)(*[float(v) for v in lin_acc])
+        _check(lib().loam_lanes_imu(self.h, int(lane), stamp, q, a))
+
+    def lanes_imu_trans(self):
+        """/imu_trans of every lane from the last pulled step (loam_lanes_imu_trans): an
+        (n_lanes, 12) float32 array, zero rows for lanes without IMU"""
+        out = np.zeros((self.n_lanes, 12), np.float32)
+        _check(lib().loam_lanes_imu_trans(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
 
     def lanes_pull(self):
         """waits for the pushed step (loam_lanes_pull): a dict of numpy arrays, one row per lane:

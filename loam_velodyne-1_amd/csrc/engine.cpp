@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstddef>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -2286,15 +2287,34 @@ int lane_sweep_code(const loam_cloud_in& c, int cap) {
   return LOAM_OK;
 }
 
+// whether the step about to be enqueued runs laserMapping (lanes_enqueue's `pub`)
+bool lanes_will_map(const loam_ctx* x) {
+  const Lanes& L = x->lanes;
+  return L.od_inited && L.od_frame_count + 1 >= (int)x->cfg.skip_frame_num + 1;
+}
+
 // one step's device work on x->st, behind the sweeps' upload; sets L.step_pub / L.step_mapped
-hipError_t lanes_enqueue(loam_ctx* x, Prof* pf) {
+// imu: the step's LaneHdr block and new queue entries are on the device (lanes_imu_put): the ring
+// sort takes the tile-parallel IMU form and k_lanes_imu follows it
+hipError_t lanes_enqueue(loam_ctx* x, Prof* pf, bool imu) {
   Lanes& L = x->lanes;
   const int S = L.S;
   hipStream_t st = x->st;
   OdBuffers& o = L.od;
   hipError_t e = hipSuccess;
   auto T = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  sr_launch(L.sr, sr_params(x), st, pf);
+  SrParams prm = sr_params(x);
+  if (imu) {
+    prm.imu = L.imu.q_d;
+    prm.imu_lane = (const loamimu::LaneHdr*)L.imu.up_d;
+    prm.imu_tail = L.imu.tail_d;
+    prm.imu_tile_key = L.imu.tile_key_d;
+  }
+  sr_launch(L.sr, prm, st, pf);
+  if (imu) {
+    T(lanes_imu_commit(L, !L.od_inited, lanes_will_map(x), st));
+    x->prof.mark("k_lanes_imu");
+  }
   const FeatView f = feat_view(L.sr, 0, 1);
   L.step_pub = 0;
   L.step_mapped = 0;
@@ -2379,13 +2399,17 @@ extern "C" int loam_lanes_close(loam_ctx* x) {
   return LOAM_OK;
 }
 
-extern "C" int loam_lanes_push(loam_ctx* x, double stamp, const loam_cloud_in* raw) {
-  (void)stamp;  // (no IMU in lanes: nothing is looked up by time)
-  if (!x || !raw) return fail(LOAM_E_INVAL, "null argument");
+namespace {
+// loam_lanes_push / loam_lanes_push_stamped: lane l's sweep stamp is stamps ? stamps[l] : stamp
+int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud_in* raw) {
   Lanes& L = x->lanes;
   if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_push: lanes are not open");
   if (L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_push: a step is in flight (loam_lanes_pull first)");
   const int S = L.S;
+  for (int l = 0; l < S; ++l)
+    if (!std::isfinite(stamps ? stamps[l] : stamp)) return fail(LOAM_E_INVAL, "loam_lanes_push: a sweep stamp is not finite");
+  LanesImu& I = L.imu;
+  I.step_imu = false;
   L.have_reg = false;
   if (!L.sr_inited) {  // src/scanRegistration.cpp:213-219 (Q1): the sweeps are not looked at
     L.sr_init_count++;
@@ -2424,11 +2448,95 @@ extern "C" int loam_lanes_push(loam_ctx* x, double stamp, const loam_cloud_in* r
   HIP_TRY(hipMemcpyAsync(L.tab_d, nn, (size_t)2 * S * sizeof(int), hipMemcpyHostToDevice, st));
   HIP_TRY(sr_scatter_packed(L.stage_d, L.tab_d + S, L.tab_d, L.sr.raw, x->cap, S, st));
   HIP_TRY(hipMemcpyAsync(L.sr.raw_n, L.tab_d, (size_t)S * sizeof(int), hipMemcpyDeviceToDevice, st));
+  // IMU: any live lane with a message makes this an IMU step for all lanes
+  bool imu = false;
+  if (I.on) {
+    auto live = [&](int l) { return L.fail[l] == LOAM_OK && L.fail_new[l] == LOAM_OK; };
+    for (int l = 0; l < S && !imu; ++l) imu = live(l) && I.sr[l].last >= 0;
+    if (imu) {
+      const bool will_map = lanes_will_map(x);
+      loamimu::LaneHdr* hdr = (loamimu::LaneHdr*)I.up_h;
+      loamimu::LaneRec* rec = (loamimu::LaneRec*)(I.up_h + (size_t)S * sizeof(loamimu::LaneHdr));
+      int nrec = 0;
+      for (int l = 0; l < S; ++l) {
+        const loamimu::SrQueue& q = I.sr[l];
+        loamimu::LaneHdr& h = hdr[l];
+        std::memset(&h, 0, sizeof(h));
+        h.time_scan = stamps ? stamps[l] : stamp;
+        h.last = q.last;
+        h.has = live(l) && q.last >= 0 ? 1 : 0;
+        I.mp_have[l] = 0;
+        if (!h.has) continue;
+        // transformUpdate's blend (src/laserMapping.cpp:199-226) at this lane's stamp, from its
+        // committed pointer; the pull commits the advanced one when the lane's L-M ran
+        if (will_map && loamimu::mp_lookup(I.mp[l], h.time_scan, h.roll, h.pitch, I.mp_front[l])) {
+          h.mp_flag = 1;
+          I.mp_have[l] = 1;
+        }
+        // the entries pushed since the last step (the ring holds the last kQue of them)
+        nrec += loamimu::lane_records(q, I.n_new[l], l, rec + nrec);
+        I.n_new[l] = 0;
+      }
+      I.up_bytes = (size_t)S * sizeof(loamimu::LaneHdr) + (size_t)nrec * sizeof(loamimu::LaneRec);
+      HIP_TRY(lanes_imu_put(L, I.up_bytes, nrec, st));
+    }
+  }
   x->prof.mark("lanes_h2d");
-  const hipError_t he = lanes_enqueue(x, pf);
+  const hipError_t he = lanes_enqueue(x, pf, imu);
   L.in_flight = true;
   L.step_ran = true;
+  I.step_imu = imu;
   if (he != hipSuccess) return fail(LOAM_E_HIP, std::string("loam_lanes_push: ") + hipGetErrorString(he));
+  return LOAM_OK;
+}
+}  // namespace
+
+extern "C" int loam_lanes_push(loam_ctx* x, double stamp, const loam_cloud_in* raw) {
+  if (!x || !raw) return fail(LOAM_E_INVAL, "null argument");
+  return lanes_push(x, nullptr, stamp, raw);
+}
+
+extern "C" int loam_lanes_push_stamped(loam_ctx* x, const double* stamp, const loam_cloud_in* raw) {
+  if (!x || !stamp || !raw) return fail(LOAM_E_INVAL, "null argument");
+  return lanes_push(x, stamp, 0.0, raw);
+}
+
+extern "C" int loam_lanes_imu(loam_ctx* x, uint32_t lane, double stamp, const double* quat_xyzw,
+                              const double* lin_acc_xyz) {
+  if (!x || !quat_xyzw || !lin_acc_xyz) return fail(LOAM_E_INVAL, "null argument");
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_imu: lanes are not open");
+  if (lane >= (uint32_t)L.S) return fail(LOAM_E_INVAL, "loam_lanes_imu: lane index out of range");
+  // (the queues a push copied and the pointers a pull commits do not change in between)
+  if (L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_imu: a step is in flight (loam_lanes_pull first)");
+  if (L.fail[lane] != LOAM_OK) return fail(LOAM_E_INVAL, "loam_lanes_imu: the lane has failed");
+  LanesImu& I = L.imu;
+  if (!(stamp >= (I.on ? I.last_stamp[lane] : -1e300)))
+    return fail(LOAM_E_INVAL, "loam_lanes_imu: IMU stamps of a lane must be non-decreasing");
+  if (!I.on) {  // the first message of any lane: the queues, host and device
+    HIP_TRY(hipSetDevice(x->device));
+    const hipError_t he = lanes_imu_alloc(L);
+    if (he != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(LOAM_E_NOMEM, std::string("loam_lanes_imu: allocation failed: ") + hipGetErrorString(he));
+    }
+  }
+  I.last_stamp[lane] = stamp;
+  double roll, pitch, yaw;
+  loampose::rpy_from_quat(quat_xyzw, roll, pitch, yaw);  // tf::Matrix3x3(q).getRPY
+  loamimu::sr_push(I.sr[lane], stamp, roll, pitch, yaw, lin_acc_xyz);  // scanRegistration.cpp:638-660
+  loamimu::mp_push(I.mp[lane], stamp, roll, pitch);                     // laserMapping.cpp:323-335
+  I.n_new[lane]++;
+  return LOAM_OK;
+}
+
+extern "C" int loam_lanes_imu_trans(loam_ctx* x, float* out) {
+  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_imu_trans: lanes are not open");
+  if (L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_imu_trans: a step is in flight (loam_lanes_pull first)");
+  if (!L.pulled) return fail(LOAM_E_INVAL, "loam_lanes_imu_trans: no step was pulled");
+  std::memcpy(out, L.imu_trans.data(), (size_t)L.S * 12 * sizeof(float));
   return LOAM_OK;
 }
 
@@ -2440,8 +2548,10 @@ extern "C" int loam_lanes_pull(loam_ctx* x, loam_lane_out* out) {
   if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_pull: lanes are not open");
   if (!L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_pull: no step was pushed");
   const int S = L.S;
+  L.imu_trans.assign((size_t)S * 12, 0.0f);
   if (!L.step_ran) {  // inside system_delay: nothing was enqueued
     L.in_flight = false;
+    L.pulled = true;
     std::memset(out, 0, (size_t)S * sizeof(loam_lane_out));
     for (int l = 0; l < S; ++l) out[l].status = LOAM_E_NOT_READY;
     return LOAM_OK;
@@ -2482,8 +2592,12 @@ extern "C" int loam_lanes_pull(loam_ctx* x, loam_lane_out* out) {
       std::memcpy(&q.bef, w + kLoBef, sizeof(loam_pose6));
       q.n_registered = (uint32_t)w[kLoNReg];
       L.nreg[l] = q.n_registered;
+      // laserMapping's queue pointer walks inside transformUpdate, i.e. only when the L-M ran
+      if (L.imu.step_imu && L.imu.mp_have[l] && w[kLoLmRan]) L.imu.mp[l].front = L.imu.mp_front[l];
     }
+    if (L.imu.step_imu) std::memcpy(&L.imu_trans[(size_t)l * 12], L.imu.trans_h + (size_t)l * 12, 12 * sizeof(float));
   }
+  L.pulled = true;
   L.have_reg = L.step_mapped != 0;
   return LOAM_OK;
 }

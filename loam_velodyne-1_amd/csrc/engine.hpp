@@ -181,6 +181,11 @@ struct SrParams {
   float ring_lo, ring_hi;
   loamimu::SrQueue* imu = nullptr;  // device IMU queue of sweep 0 (streaming), nullptr = no IMU
   double time_scan = 0.0;           // timeScanCur: the sweep's stamp
+  // lanes, all four or none: imu is then a queue per sweep, and sweep s is
+  // de-skewed with imu[s] at imu_lane[s].time_scan when imu_lane[s].has (the tile-parallel form)
+  const loamimu::LaneHdr* imu_lane = nullptr;  // [S]
+  loamimu::SrTail* imu_tail = nullptr;         // [S] the tails the sweeps leave (committed by k_lanes_imu)
+  int* imu_tile_key = nullptr;                 // [S][ntiles][3] per-tile orientation maxima (k_sr_ring_count)
 };
 
 // Device allocation of the *_alloc functions: every request goes through one DevAlloc, which

@@ -35,6 +35,60 @@ struct SrQueue {
   float shiftFSX, shiftFSY, shiftFSZ, veloFSX, veloFSY, veloFSZ;
 };
 
+// Lanes (loam_lanes_imu): the device keeps a queue per lane.  The host is master of
+// the entries and of `last`; the device is master of the tail (front, Start, Cur, FromStart).
+// the tail as a sweep's tile-parallel de-skew leaves it: a second record, because every tile of the
+// sweep still reads the queue's own tail; k_lanes_imu copies it into the queue afterwards
+struct SrTail {
+  int front;
+  int valid;    // 1: written by this step's sweep (a sweep without a ring-filtered point writes nothing)
+  int i0;       // the sweep's first finite point (k_sr_ring_count's tile 0)
+  int pad;
+  float v[24];  // rollStart .. shiftZStart, rollCur .. shiftZCur, shiftFSX .. veloFSZ, in SrQueue's order
+};
+// what a lanes step uploads per lane
+struct LaneHdr {
+  double time_scan;   // the lane's sweep stamp (timeScanCur)
+  int has;            // 1: the lane is live and its queue holds a message: the sweep is de-skewed
+  int last;           // the queue's imuPointerLast
+  float roll, pitch;  // mapping steps: transformUpdate's IMU roll / pitch (mp_lookup) ...
+  int mp_flag;        // ... and whether there is one
+  int pad;
+};
+// one new queue entry of a lane
+struct LaneRec {
+  double time;
+  float v[12];  // roll, pitch, yaw, acc xyz, velo xyz, shift xyz
+  int lane, idx;
+};
+
+// (host) the last min(n_new, kQue) entries of q, oldest first, as lane `lane`'s records: what a
+// step uploads for a lane that got n_new messages since the step before; returns their number
+inline int lane_records(const SrQueue& q, int n_new, int lane, LaneRec* rec) {
+  const int m = n_new < kQue ? n_new : kQue;
+  for (int j = 0; j < m; ++j) {
+    const int k = ((q.last - (m - 1) + j) % kQue + kQue) % kQue;
+    LaneRec& r = rec[j];
+    r.time = q.time[k];
+    r.v[0] = q.roll[k]; r.v[1] = q.pitch[k]; r.v[2] = q.yaw[k];
+    r.v[3] = q.accX[k]; r.v[4] = q.accY[k]; r.v[5] = q.accZ[k];
+    r.v[6] = q.veloX[k]; r.v[7] = q.veloY[k]; r.v[8] = q.veloZ[k];
+    r.v[9] = q.shiftX[k]; r.v[10] = q.shiftY[k]; r.v[11] = q.shiftZ[k];
+    r.lane = lane;
+    r.idx = k;
+  }
+  return m;
+}
+// a record into its queue (k_lanes_imu_put's store, also run on the host by tests/lanes_imu_walk_check.cpp)
+LOAM_HD void lane_record_put(SrQueue& m, const LaneRec& r) {
+  const int k = r.idx;
+  m.time[k] = r.time;
+  m.roll[k] = r.v[0]; m.pitch[k] = r.v[1]; m.yaw[k] = r.v[2];
+  m.accX[k] = r.v[3]; m.accY[k] = r.v[4]; m.accZ[k] = r.v[5];
+  m.veloX[k] = r.v[6]; m.veloY[k] = r.v[7]; m.veloZ[k] = r.v[8];
+  m.shiftX[k] = r.v[9]; m.shiftY[k] = r.v[10]; m.shiftZ[k] = r.v[11];
+}
+
 // laserMapping's queue (:101-108)
 struct MpQueue {
   double time[kQue];
@@ -120,17 +174,55 @@ inline bool mp_lookup(const MpQueue& m, double timeLaserOdometry, float& rollLas
   return true;
 }
 
+// the point's orientation on the sweep's first / second half (:263-268, :274-280)
+LOAM_HD float ori_first(float ori, float startOri) {
+  if (D(ori) < D(startOri) - M_PI / 2) ori = (float)(D(ori) + 2 * M_PI);
+  else if (D(ori) > D(startOri) + M_PI * 3 / 2) ori = (float)(D(ori) - 2 * M_PI);
+  return ori;
+}
+LOAM_HD float ori_second(float ori, float endOri) {
+  ori = (float)(D(ori) + 2 * M_PI);
+  if (D(ori) < D(endOri) - M_PI * 3 / 2) ori = (float)(D(ori) + 2 * M_PI);
+  else if (D(ori) > D(endOri) + M_PI / 2) ori = (float)(D(ori) - 2 * M_PI);
+  return ori;
+}
+
+// The tile-parallel de-skew's per-tile orientation maxima (sr.hip), kept as keys:
+// float order as int order (the map is its own inverse); no finite float gives kNoOri.
+constexpr int kNoOri = (int)0x80000000;
+LOAM_HD int ori_key(float f) {
+  const int k = __builtin_bit_cast(int, f);
+  return k ^ ((k >> 31) & 0x7fffffff);
+}
+LOAM_HD float ori_of_key(int k) {
+  return __builtin_bit_cast(float, k ^ ((k >> 31) & 0x7fffffff));
+}
+// key3 of tile k: the largest ori_first over its ring-filtered points up to its own first flip, the
+// largest ori_second over the rest, the largest ori_second over the points up to its own flip.
+// The key of the largest branch-resolved orientation the tile holds when tile tF holds the sweep's
+// flip F (0x7fffffff: no flip): before tF a tile has no flip of its own and is all first branch,
+// tF's own flip is F, after tF every point is on the second branch.
+LOAM_HD int tile_ori_key(const int* key3, int k, int tF) {
+  if (k < tF) return key3[0];
+  if (k == tF) return key3[0] > key3[1] ? key3[0] : key3[1];
+  return key3[1] > key3[2] ? key3[1] : key3[2];
+}
+
 // first logical queue position k in [0, L] (from `front0`) whose stamp is later than t, else L: the
 // stop of the :288-293 walk started at front0 (stamps non-decreasing, loam_imu enforces it)
-LOAM_HD int first_later(const SrQueue& m, int front0, double t) {
-  const int L = (m.last - front0 + kQue) % kQue;
+// (time: the queue's stamps, wherever they are kept; last: its imuPointerLast)
+LOAM_HD int first_later_of(const double* time, int last, int front0, double t) {
+  const int L = (last - front0 + kQue) % kQue;
   int lo = 0, hi = L;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
-    if (t < m.time[(front0 + mid) % kQue]) hi = mid;
+    if (t < time[(front0 + mid) % kQue]) hi = mid;
     else lo = mid + 1;
   }
   return lo;
+}
+LOAM_HD int first_later(const SrQueue& m, int front0, double t) {
+  return first_later_of(m.time, m.last, front0, t);
 }
 
 // :295-331 the point's interpolated state from queue entry F

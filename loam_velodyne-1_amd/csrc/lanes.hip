@@ -15,7 +15,7 @@ struct LaneOutSrc {
 };
 
 // 32 lanes of a wave per lane of the step, one word each: the three error words, the two iteration
-// counts, the registered cloud's size, transformSum, Aft, Bef
+// counts, the registered cloud's size, transformSum, Aft, Bef, and whether mapping's L-M ran
 __global__ __launch_bounds__(256) void k_lanes_out(LaneOutSrc s, int* out, int S) {
   const int gid = blockIdx.x * 256 + threadIdx.x;
   const int l = gid >> 5, w = gid & 31;
@@ -31,8 +31,76 @@ __global__ __launch_bounds__(256) void k_lanes_out(LaneOutSrc s, int* out, int S
   else if (w == kLoNReg) v = s.nreg[l];
   else if (w < kLoAft) v = __float_as_int(s.od_state[(size_t)l * kOdStateFloats + kOdSum + (w - kLoOdSum)]);
   else if (w < kLoBef) v = __float_as_int(s.mp_state[(size_t)l * kMpStateFloats + kMpAft + (w - kLoAft)]);
+  else if (w == kLoLmRan) v = mi[kMiLmRan];
   else v = __float_as_int(s.mp_state[(size_t)l * kMpStateFloats + kMpBef + (w - kLoBef)]);
   out[(size_t)l * kLaneOutWords + w] = v;
+}
+
+// the step's new queue entries into the lanes' device queues (thread g < nrec), and every lane's
+// imuPointerLast (thread g < S)
+__global__ __launch_bounds__(256) void k_lanes_imu_put(const loamimu::LaneHdr* hdr, const loamimu::LaneRec* rec, int nrec,
+                                                       loamimu::SrQueue* q, int S) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g < nrec) {
+    const loamimu::LaneRec r = rec[g];
+    loamimu::lane_record_put(q[r.lane], r);
+  }
+  if (g < S) q[g].last = hdr[g].last;
+}
+
+struct LaneImuDst {
+  loamimu::SrQueue* q;     // [S]
+  loamimu::SrTail* tail;   // [S]
+  float* od_state;         // [S][kOdStateFloats]
+  float* mp_state;         // [S][kMpStateFloats]
+  int* mp_istate;          // [S][kMpStateInts]
+  float* trans;            // [S][12]
+};
+
+// 32 threads per lane, behind the ring sort.  A lane with a queue: the tail its sweep left
+// (SrTail) becomes the queue's, /imu_trans (src/scanRegistration.cpp:614-635) goes into the
+// odometry state in the order load_imu reads and into the step's result, and on the odometry's
+// init frame transformSum starts from the IMU pitch / roll (src/laserOdometry.cpp:451-452).  On
+// mapping steps every lane gets transformUpdate's (roll, pitch, flag).
+__global__ __launch_bounds__(256) void k_lanes_imu(const loamimu::LaneHdr* hdr, LaneImuDst d, int od_init, int mapping,
+                                                    int S) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  const int l = gid >> 5, w = gid & 31;
+  const bool live = l < S;
+  const loamimu::LaneHdr h = live ? hdr[l] : loamimu::LaneHdr{};
+  const bool has = live && h.has != 0;
+  float v = 0.0f;      // word w of the tail that holds from here on
+  int front = 0, valid = 0;
+  if (has) {
+    valid = d.tail[l].valid;
+    if (w < 24) v = valid ? d.tail[l].v[w] : (&d.q[l].rollStart)[w];
+    front = d.tail[l].front;
+  }
+  __syncthreads();  // (every thread has read `valid` before it is cleared)
+  if (has && valid) {
+    if (w < 24) (&d.q[l].rollStart)[w] = v;
+    if (w == 24) d.q[l].front = front;
+    if (w == 25) d.tail[l].valid = 0;
+  }
+  // imu_trans[k] = tail word kMap[k]: pitch / yaw / roll Start, pitch / yaw / roll Cur, FromStart
+  constexpr int kMap[12] = {1, 2, 0, 10, 11, 9, 18, 19, 20, 21, 22, 23};
+  int src = 0;
+#pragma unroll
+  for (int k = 0; k < 12; ++k)
+    if (w == k) src = kMap[k];
+  const float it = __shfl(v, (threadIdx.x & 32) + src, 64);
+  if (live && w < 12) {
+    d.trans[(size_t)l * 12 + w] = has ? it : 0.0f;
+    if (has) {
+      d.od_state[(size_t)l * kOdStateFloats + kOdImu + w] = it;
+      if (od_init && (w == 0 || w == 2)) d.od_state[(size_t)l * kOdStateFloats + kOdSum + w] = 0.0f + it;
+    }
+  }
+  if (live && mapping) {
+    if (w == 12) d.mp_state[(size_t)l * kMpStateFloats + kMpImuRP] = h.roll;
+    if (w == 13) d.mp_state[(size_t)l * kMpStateFloats + kMpImuRP + 1] = h.pitch;
+    if (w == 14) d.mp_istate[(size_t)l * kMpStateInts + kMiImu] = h.mp_flag;
+  }
 }
 }  // namespace
 
@@ -68,7 +136,83 @@ hipError_t lanes_alloc(Lanes& L, int S, int cap, int R, int map_cap, int od_max_
   return hipSuccess;
 }
 
+hipError_t lanes_imu_alloc(Lanes& L) {
+  LanesImu& I = L.imu;
+  const size_t S = (size_t)L.S;
+  const size_t up = S * sizeof(loamimu::LaneHdr) + S * loamimu::kQue * sizeof(loamimu::LaneRec);
+  hipError_t e = hipMalloc((void**)&I.q_d, S * sizeof(loamimu::SrQueue));
+  if (e == hipSuccess) e = hipMalloc((void**)&I.tail_d, S * sizeof(loamimu::SrTail));
+  if (e == hipSuccess) e = hipMalloc((void**)&I.tile_key_d, S * L.sr.ntiles() * 3 * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&I.up_d, up);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&I.up_h, up, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&I.trans_d, S * 12 * sizeof(float));
+  if (e == hipSuccess) e = hipHostMalloc((void**)&I.trans_h, S * 12 * sizeof(float), hipHostMallocDefault);
+  // (an empty queue: front 0, Start / Cur / FromStart zero; `last` arrives with every IMU step)
+  if (e == hipSuccess) e = hipMemset(I.q_d, 0, S * sizeof(loamimu::SrQueue));
+  if (e == hipSuccess) e = hipMemset(I.tail_d, 0, S * sizeof(loamimu::SrTail));
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    lanes_imu_free(L);
+    return e;
+  }
+  loamimu::SrQueue q0;
+  std::memset(&q0, 0, sizeof(q0));
+  q0.last = -1;
+  loamimu::MpQueue m0;
+  std::memset(&m0, 0, sizeof(m0));
+  m0.last = -1;
+  I.sr.assign(S, q0);
+  I.mp.assign(S, m0);
+  I.last_stamp.assign(S, -1e300);
+  I.n_new.assign(S, 0);
+  I.mp_front.assign(S, 0);
+  I.mp_have.assign(S, 0);
+  I.on = true;
+  return hipSuccess;
+}
+
+void lanes_imu_free(Lanes& L) {
+  LanesImu& I = L.imu;
+  if (I.q_d) (void)hipFree(I.q_d);
+  if (I.tail_d) (void)hipFree(I.tail_d);
+  if (I.tile_key_d) (void)hipFree(I.tile_key_d);
+  if (I.up_d) (void)hipFree(I.up_d);
+  if (I.up_h) (void)hipHostFree(I.up_h);
+  if (I.trans_d) (void)hipFree(I.trans_d);
+  if (I.trans_h) (void)hipHostFree(I.trans_h);
+  I = LanesImu();
+}
+
+hipError_t lanes_imu_put(Lanes& L, size_t bytes, int nrec, hipStream_t st) {
+  LanesImu& I = L.imu;
+  hipError_t e = hipMemcpyAsync(I.up_d, I.up_h, bytes, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  const loamimu::LaneHdr* hdr = (const loamimu::LaneHdr*)I.up_d;
+  const loamimu::LaneRec* rec = (const loamimu::LaneRec*)(I.up_d + (size_t)L.S * sizeof(loamimu::LaneHdr));
+  const int n = std::max(nrec, L.S);
+  hipLaunchKernelGGL(k_lanes_imu_put, dim3((n + 255) / 256), dim3(256), 0, st, hdr, rec, nrec, I.q_d, L.S);
+  return hipGetLastError();
+}
+
+hipError_t lanes_imu_commit(Lanes& L, bool od_init, bool mapping, hipStream_t st) {
+  LanesImu& I = L.imu;
+  LaneImuDst d;
+  d.q = I.q_d;
+  d.tail = I.tail_d;
+  d.od_state = L.od.state;
+  d.mp_state = L.mp.state;
+  d.mp_istate = L.mp.istate;
+  d.trans = I.trans_d;
+  hipLaunchKernelGGL(k_lanes_imu, dim3((L.S * 32 + 255) / 256), dim3(256), 0, st, (const loamimu::LaneHdr*)I.up_d, d,
+                     od_init ? 1 : 0, mapping ? 1 : 0, L.S);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(I.trans_h, I.trans_d, (size_t)L.S * 12 * sizeof(float), hipMemcpyDeviceToHost, st);
+  return e;
+}
+
 void lanes_free(Lanes& L) {
+  lanes_imu_free(L);
   sr_free(L.sr);
   od_free(L.od);
   mp_free(L.mp);

@@ -16,7 +16,30 @@ namespace loam {
 
 // a lane's block of the step's result (k_lanes_out), 32-bit words
 enum { kLoSrErr = 0, kLoOdErr, kLoMpErr, kLoOdIters, kLoMpIters, kLoNReg, kLoOdSum = 6, kLoAft = 12, kLoBef = 18,
-       kLaneOutWords = 24 };
+       kLoLmRan = 24, kLaneOutWords = 25 };
+
+// The lanes' IMU side (loam_lanes_imu); nothing of it exists until the first message.
+// Host: a scanRegistration queue (entries and `last`) and a laserMapping queue per lane.  Device:
+// the queues, whose tails (front, Start, Cur, FromStart) only the kernels write.
+struct LanesImu {
+  bool on = false;
+  std::vector<loamimu::SrQueue> sr;  // [S] host master of the entries and of last
+  std::vector<loamimu::MpQueue> mp;  // [S]
+  std::vector<double> last_stamp;    // [S]
+  std::vector<int> n_new;            // [S] messages since the last pushed step
+  loamimu::SrQueue* q_d = nullptr;   // [S]
+  loamimu::SrTail* tail_d = nullptr; // [S]
+  int* tile_key_d = nullptr;         // [S][ntiles][3]
+  // a step's upload: [S] LaneHdr, then the new entries as LaneRec (at most kQue per lane)
+  char* up_h = nullptr;              // pinned
+  char* up_d = nullptr;
+  float* trans_d = nullptr;          // [S][12] /imu_trans of the step (k_lanes_imu)
+  float* trans_h = nullptr;          // pinned copy
+  bool step_imu = false;             // the step in flight took the IMU form
+  std::vector<int> mp_front;         // [S] mp_lookup's advanced pointer of the step in flight ...
+  std::vector<char> mp_have;         // ... and whether the lane had a message to look up
+  size_t up_bytes = 0;               // what the last IMU step uploaded
+};
 
 struct Lanes {
   int S = 0;           // 0: not open
@@ -43,6 +66,9 @@ struct Lanes {
   std::vector<int> fail;       // [S] sticky failure of a lane (LOAM_OK: live); the host owns it
   std::vector<int> fail_new;   // [S] what the host found wrong with the pushed sweep
   std::vector<uint32_t> nreg;  // [S] registered points of the last pulled step
+  LanesImu imu;
+  bool pulled = false;           // a step has been pulled
+  std::vector<float> imu_trans;  // [S][12] /imu_trans of the last pulled step (zeros without IMU)
 };
 
 // launch choices of the lanes' L-M loops: the context's, without the two forms a lane may not take
@@ -53,6 +79,16 @@ hipError_t lanes_alloc(Lanes& L, int S, int cap, int R, int map_cap, int od_max_
 void lanes_free(Lanes& L);
 // k_lanes_out: every lane's block into out_d, then its copy into out_h
 hipError_t lanes_out(const Lanes& L, hipStream_t st);
+// the IMU side's buffers (the first loam_lanes_imu); on failure they are freed and imu.on stays false
+hipError_t lanes_imu_alloc(Lanes& L);
+void lanes_imu_free(Lanes& L);
+// k_lanes_imu_put: the step's upload (imu.up_h, `bytes` of it, nrec entries behind the headers)
+// to the device and the new entries and `last` into the device queues
+hipError_t lanes_imu_put(Lanes& L, size_t bytes, int nrec, hipStream_t st);
+// k_lanes_imu, behind the ring sort: commits the tails, writes every IMU lane's /imu_trans into the
+// odometry state (od_init: and transformSum's start, src/laserOdometry.cpp:451-452) and into
+// imu.trans_d, and on mapping steps every lane's (roll, pitch, flag) into the mapping state
+hipError_t lanes_imu_commit(Lanes& L, bool od_init, bool mapping, hipStream_t st);
 
 }  // namespace loam
 #endif

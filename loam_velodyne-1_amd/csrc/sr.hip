@@ -54,17 +54,10 @@ LOAM_D int ring_of(const SrParams& p, float px, float py, float pz) {
   return ring_id(p, (float)(atan(D(py) / sqrt(D(px * px + pz * pz))) * 180 / M_PI));
 }
 
-LOAM_D float ori_first(float ori, float startOri) {  // :263-268
-  if (D(ori) < D(startOri) - M_PI / 2) ori = (float)(D(ori) + 2 * M_PI);
-  else if (D(ori) > D(startOri) + M_PI * 3 / 2) ori = (float)(D(ori) - 2 * M_PI);
-  return ori;
-}
-LOAM_D float ori_second(float ori, float endOri) {  // :274-280
-  ori = (float)(D(ori) + 2 * M_PI);
-  if (D(ori) < D(endOri) - M_PI * 3 / 2) ori = (float)(D(ori) + 2 * M_PI);
-  else if (D(ori) > D(endOri) + M_PI / 2) ori = (float)(D(ori) - 2 * M_PI);
-  return ori;
-}
+using loamimu::kNoOri;
+using loamimu::ori_first;   // :263-268
+using loamimu::ori_key;
+using loamimu::ori_second;  // :274-280
 LOAM_D bool finite3(const float4& q) {
   return isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
 }
@@ -293,9 +286,22 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
 constexpr int kRingE = LOAM_RING_E;
 constexpr int kRingTile = kSrThreads * kRingE;
 
+// IMU (the lanes' form): a sweep with a queue (imu_lane[s].has) is de-skewed by
+// k_sr_ring_scatter<true>, whose tiles need the reference's forward-only queue pointer as it stands
+// at their first point: the largest "first entry later than the point" over the tiles before.
+// That index is monotone in the point's branch-resolved orientation, so a tile's largest is that
+// of its largest orientation, and the branch depends only on where the sweep's flip F lies
+// relative to the tile: this kernel stores, as order-preserving int keys, the tile's largest
+// ori_first over its points up to its own flip, its largest ori_second over the rest, and its
+// largest ori_second over the points up to its own flip (for a flip in an earlier tile);
+// loamimu::tile_ori_key picks among them (imu.hpp; tests/lanes_imu_walk_check.cpp runs the rule on
+// the host against the sequential walk).
+
+template <bool IMU>
 __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrParams p) {
   const int s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int n = b.raw_n[s], R = p.R;
+  const bool imu = IMU && p.imu_lane[s].has != 0;
   if (t == 0) {  // the sweep's error bits and ring bounds start here (tile 0 alone writes err in this launch)
     if (tid < 2 * R) b.ring_se[s * 2 * R + tid] = 0;
     if (tid == 0) b.err[s] = 0;
@@ -305,6 +311,8 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
   __shared__ int sh_first, sh_last, sh_F;
   __shared__ float sh_start, sh_end_raw;
   __shared__ int sh_cnt[64];
+  __shared__ float sh_end;
+  __shared__ int sh_key[3];
   // the tile's points first: their loads are in flight during the sweep-end scans and the start
   // orientation below
   float4 q[kRingE];
@@ -335,9 +343,23 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
   __syncthreads();
   // :230-238, the two orientations on two waves; only tile 0 needs endOri
   if (tid == 0) sh_start = sh_last >= 0 ? -atan2f_fdlibm(raw[sh_first].y, raw[sh_first].x) : 0.0f;
-  if (tid == 64 && t == 0 && sh_last >= 0) sh_end_raw = -atan2f_fdlibm(raw[sh_last].y, raw[sh_last].x);
+  if (tid == 64 && (t == 0 || imu) && sh_last >= 0) sh_end_raw = -atan2f_fdlibm(raw[sh_last].y, raw[sh_last].x);
   __syncthreads();
   const float startOri = sh_start;
+  if (IMU && imu) {  // every tile needs endOri (ori_second); tile 0 publishes it below as ever
+    if (tid == 0) {
+      float endOri = 0.0f;
+      if (sh_last >= 0) {
+        endOri = (float)(D(sh_end_raw) + 2 * M_PI);
+        if (D(endOri - startOri) > 3 * M_PI) endOri = (float)(D(endOri) - 2 * M_PI);
+        else if (D(endOri - startOri) < M_PI) endOri = (float)(D(endOri) + 2 * M_PI);
+      }
+      sh_end = endOri;
+      sh_key[0] = sh_key[1] = sh_key[2] = kNoOri;
+      if (t == 0) p.imu_tail[s].i0 = sh_first;
+    }
+    __syncthreads();
+  }
   if (tid == 0 && t == 0) {
     float endOri = 0.0f;
     if (sh_last >= 0) {
@@ -351,9 +373,11 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
     b.sweep_ori[2 * s + 1] = endOri;
   }
   int Floc = 0x7fffffff;
+  int k1[kRingE], k2[kRingE];  // (IMU) keys of the point's ori_first / ori_second, kNoOri for a dropped point
 #pragma unroll
   for (int e = 0; e < kRingE; ++e) {
     const int i = t * kRingTile + e * kSrThreads + tid;
+    k1[e] = k2[e] = kNoOri;
     if (i < n) {
       uint8_t sid = 255;
       float ori = 0.0f;
@@ -366,6 +390,10 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
           const float o1 = ori_first(ori, startOri);
           if (D(o1 - startOri) > M_PI) Floc = min(Floc, i);
           atomicAdd(&sh_cnt[scanID], 1);
+          if (IMU && imu) {
+            k1[e] = ori_key(o1);
+            k2[e] = ori_key(ori_second(ori, sh_end));
+          }
         }
       }
       b.tmp_ori[(size_t)s * b.cap + i] = ori;
@@ -377,14 +405,37 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
   __syncthreads();
   if (tid < R) b.tilecnt[((size_t)s * b.ntiles() + t) * R + tid] = sh_cnt[tid];
   if (tid == 0) b.tileF[(size_t)s * b.ntiles() + t] = sh_F;
+  if (IMU && imu) {
+    const int ownF = sh_F;
+    int m1 = kNoOri, m2 = kNoOri, m3 = kNoOri;
+#pragma unroll
+    for (int e = 0; e < kRingE; ++e) {
+      const int i = t * kRingTile + e * kSrThreads + tid;
+      if (i <= ownF) { m1 = max(m1, k1[e]); m3 = max(m3, k2[e]); }
+      else m2 = max(m2, k2[e]);
+    }
+    m1 = wave_max_i(m1); m2 = wave_max_i(m2); m3 = wave_max_i(m3);
+    if (lane == 0) { atomicMax(&sh_key[0], m1); atomicMax(&sh_key[1], m2); atomicMax(&sh_key[2], m3); }
+    __syncthreads();
+    if (tid < 3) p.imu_tile_key[((size_t)s * b.ntiles() + t) * 3 + tid] = sh_key[tid];
+  }
 }
 
+// IMU (the lanes' form): what k_sr_ring_sort<true> does to a sweep with a queue, a tile at a time.
+// The queue pointer at the tile's first point is the maximum over the tiles before (from
+// k_sr_ring_count's keys, above), then the running maximum within the tile; Start is computed by
+// every tile from the first finite point (or read from the queue's tail); the last tile with a
+// ring-filtered point writes the tail the sweep leaves into imu_tail[s], never into the queue,
+// which the other tiles are still reading.
+template <bool IMU>
 __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrParams p) {
   constexpr int kW = kSrThreads / 64, kSlots = kRingE * kW;  // (sub-tile, wave) slots in point order
   static_assert(kSlots <= 64 && (kSlots & (kSlots - 1)) == 0, "slot scan width");
   const int s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int n = b.raw_n[s], R = p.R, nt = (n + kRingTile - 1) / kRingTile;
   if (t >= (nt > 0 ? nt : 1)) return;
+  const bool imu = IMU && p.imu_lane[s].has != 0;
+  __shared__ int sh_later;  // (IMU) a later tile has a ring-filtered point
   __shared__ int sh_tot[64], sh_pre[64], sh_base[64], sh_F;
   __shared__ int sh_wcnt[64][kSlots];  // per ring: points of each slot, then their exclusive prefix
   // the tile's ring IDs, points and orientations first: their loads are in flight during the tile
@@ -406,6 +457,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
   }
   if (tid < R) { sh_tot[tid] = 0; sh_pre[tid] = 0; }
   if (tid == 0) sh_F = 0x7fffffff;
+  if (IMU && tid == 0) sh_later = 0;
   for (int k = tid; k < 64 * kSlots; k += kSrThreads) (&sh_wcnt[0][0])[k] = 0;
   __syncthreads();
   const int* tc = b.tilecnt + (size_t)s * b.ntiles() * R;
@@ -414,6 +466,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
     if (v) {
       atomicAdd(&sh_tot[k % R], v);
       if (k / R < t) atomicAdd(&sh_pre[k % R], v);
+      if (IMU && k / R > t) sh_later = 1;
     }
   }
   int F = 0x7fffffff;
@@ -460,6 +513,93 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
   if (nt == 0) return;
   F = sh_F;
   const float startOri = b.sweep_ori[2 * s], endOri = b.sweep_ori[2 * s + 1];
+  if (IMU && imu) {
+    const loamimu::SrQueue& Q = p.imu[s];
+    const double time_scan = p.imu_lane[s].time_scan;
+    __shared__ double sh_time[loamimu::kQue];
+    __shared__ loamimu::Start sh_S;
+    __shared__ int sh_carry, sh_scr[kSrThreads / 64 + 1];
+    const int front0 = Q.front, qlast = Q.last, i0 = p.imu_tail[s].i0;
+    for (int k = tid; k < loamimu::kQue; k += kSrThreads) sh_time[k] = Q.time[k];
+    if (tid == 0) sh_carry = 0;  // (the walk starts at imuPointerFront)
+    __syncthreads();
+    // the pointer at this tile's first point: over the tiles before, the entry of the largest
+    // orientation each of them holds under the branch F gives its points
+    for (int u = tid; u < t; u += kSrThreads) {
+      const int tF = F == 0x7fffffff ? 0x7fffffff : F / kRingTile;
+      const int k = loamimu::tile_ori_key(p.imu_tile_key + ((size_t)s * b.ntiles() + u) * 3, u, tF);
+      if (k != kNoOri) {
+        const float relTime = (loamimu::ori_of_key(k) - startOri) / (endOri - startOri);
+        const float pointTime = (float)(D(relTime) * 0.1);
+        atomicMax(&sh_carry, loamimu::first_later_of(sh_time, qlast, front0, time_scan + pointTime));
+      }
+    }
+    // Start: from the first finite point when it passed the ring filter, else the last sweep's
+    if (tid == 64) {
+      loamimu::Cur c;
+      if (i0 >= 0 && b.tmp_sid[(size_t)s * b.cap + i0] != 255) {
+        const float o = ori_first(b.tmp_ori[(size_t)s * b.cap + i0], startOri);  // i0 <= F
+        const float relTime = (o - startOri) / (endOri - startOri);
+        const float pointTime = (float)(D(relTime) * 0.1);  // scanPeriod (double, :55)
+        const int g = loamimu::first_later_of(sh_time, qlast, front0, time_scan + pointTime);
+        c = loamimu::interpolate(Q, (front0 + g) % loamimu::kQue, time_scan, pointTime);
+      } else {
+        c = loamimu::Cur{Q.rollStart, Q.pitchStart, Q.yawStart, Q.veloXStart, Q.veloYStart,
+                         Q.veloZStart, Q.shiftXStart, Q.shiftYStart, Q.shiftZStart};
+      }
+      sh_S = loamimu::make_start(c);
+    }
+    // every point's own entry, and the tile's last ring-filtered point
+    float pointTime[kRingE];
+    int g[kRingE], li = -1;
+#pragma unroll
+    for (int e = 0; e < kRingE; ++e) {
+      const int i = t * kRingTile + e * kSrThreads + tid;
+      g[e] = -1;
+      pointTime[e] = 0.0f;
+      if (sid[e] != 255) {
+        const float o = (i <= F) ? ori_first(ori[e], startOri) : ori_second(ori[e], endOri);
+        const float relTime = (o - startOri) / (endOri - startOri);
+        pointTime[e] = (float)(D(relTime) * 0.1);
+        g[e] = loamimu::first_later_of(sh_time, qlast, front0, time_scan + pointTime[e]);
+        li = i;
+      }
+    }
+    int lm;
+    (void)block_incl_max<kSrThreads>(li, sh_scr, lm);  // (its barriers also publish sh_carry and sh_S)
+    int carry = sh_carry;
+#pragma unroll
+    for (int e = 0; e < kRingE; ++e) {
+      const int i = t * kRingTile + e * kSrThreads + tid;
+      int tmax;
+      const int front_i = max(carry, block_incl_max<kSrThreads>(g[e], sh_scr, tmax));
+      carry = max(carry, tmax);
+      if (sid[e] != 255) {
+        const int pos = sh_base[sid[e]] + sh_pre[sid[e]] + sh_wcnt[sid[e]][e * kW + w] + rank[e];
+        const float o = (i <= F) ? ori_first(ori[e], startOri) : ori_second(ori[e], endOri);
+        const float relTime = (o - startOri) / (endOri - startOri);
+        float4 out = make_float4(q[e].y, q[e].z, q[e].x, (float)(sid[e] + 0.1 * D(relTime)));
+        const loamimu::Cur cur = loamimu::interpolate(Q, (front0 + front_i) % loamimu::kQue, time_scan, pointTime[e]);
+        float fs[6];
+        if (i != i0) {  // ShiftToStartIMU, VeloToStartIMU, TransformToStartIMU (:343-347)
+          loamimu::to_start(sh_S, cur, pointTime[e], fs);
+          out = loamimu::transform_to_start(sh_S, cur, fs, out);
+        }
+        b.full[(size_t)s * b.cap + pos] = out;
+        if (i == lm && !sh_later) {  // the sweep's last processed point: the tail it leaves
+          loamimu::SrTail& T = p.imu_tail[s];
+          const float st[9] = {sh_S.roll, sh_S.pitch, sh_S.yaw, sh_S.vx, sh_S.vy, sh_S.vz, sh_S.sx, sh_S.sy, sh_S.sz};
+          const float cu[9] = {cur.roll, cur.pitch, cur.yaw, cur.vx, cur.vy, cur.vz, cur.sx, cur.sy, cur.sz};
+          const float ofs[6] = {Q.shiftFSX, Q.shiftFSY, Q.shiftFSZ, Q.veloFSX, Q.veloFSY, Q.veloFSZ};
+          for (int k = 0; k < 9; ++k) { T.v[k] = st[k]; T.v[9 + k] = cu[k]; }
+          for (int k = 0; k < 6; ++k) T.v[18 + k] = i != i0 ? fs[k] : ofs[k];
+          T.front = (front0 + front_i) % loamimu::kQue;
+          T.valid = 1;
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int e = 0; e < kRingE; ++e) {
     const int i = t * kRingTile + e * kSrThreads + tid;
@@ -1927,12 +2067,17 @@ int sr_ring_fused_capacity() {
 
 void sr_launch(const SrBuffers& b, const SrParams& p, hipStream_t st, Prof* prof, hipEvent_t sorted) {
   auto mark = [&](const char* n) { if (prof) prof->mark(n); };
-  if (p.imu) {  // (the tile-parallel ring sorts clear them in their tile 0)
+  const bool lanes_imu = p.imu && p.imu_lane;  // the tile-parallel IMU form: a queue per sweep
+  if (p.imu && !lanes_imu) {  // (the tile-parallel ring sorts clear them in their tile 0)
     HIPCHK(hipMemsetAsync(b.ring_se, 0, (size_t)b.S * 2 * b.R * sizeof(int), st));
     HIPCHK(hipMemsetAsync(b.err, 0, (size_t)b.S * sizeof(int), st));
   }
   mark("sr_memset");
-  if (p.imu) {
+  if (lanes_imu) {  // (never the fused kernel: its tiles wait for each other)
+    const int rtiles = (b.cap + kRingTile - 1) / kRingTile;
+    hipLaunchKernelGGL(k_sr_ring_count<true>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+    hipLaunchKernelGGL(k_sr_ring_scatter<true>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+  } else if (p.imu) {
     hipLaunchKernelGGL(k_sr_ring_sort<true>, dim3(b.S), dim3(kSrThreads), 0, st, b, p);
   } else {
     const int rtiles = (b.cap + kRingTile - 1) / kRingTile;  // <= b.ntiles(): tilecnt rows fit
@@ -1944,8 +2089,8 @@ void sr_launch(const SrBuffers& b, const SrParams& p, hipStream_t st, Prof* prof
       HIPCHK(hipMemsetAsync(b.tileF, 0xff, (size_t)b.S * rtiles * sizeof(int), st));
       hipLaunchKernelGGL(k_sr_ring_fused, dim3(rtiles * b.S), dim3(kSrThreads), 0, st, b, p, rtiles);
     } else {
-      hipLaunchKernelGGL(k_sr_ring_count, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
-      hipLaunchKernelGGL(k_sr_ring_scatter, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+      hipLaunchKernelGGL(k_sr_ring_count<false>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+      hipLaunchKernelGGL(k_sr_ring_scatter<false>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
     }
   }
   mark("k_sr_ring_sort");
