@@ -474,8 +474,11 @@ int loam_set_stream_priority(loam_ctx *ctx, int priority);
 /* launch-shape choices of the batch / streaming L-M loops by batch size (no reference equivalent):
  * key = one of od_small_max, od_fused_max, mp_small_max, mp_fused_max, od_assoc_wg, fit_wg, graph,
  * vg_merge, vg_merge_min, vg_split, sr_ahead, sr_ahead_at, step_pipe, batch_streams, pipe_mp_sets, od_sel_min, od_win_mono,
- * od_win_mono_min, od_moments_min, od_persist, mp_persist, stream_defer, od_graph, pipe_sr_sets (loam_velodyne-1_amd/csrc/engine.hpp,
- * struct Tuning).  Every choice computes the same results bit for bit except od_moments_min (the odometry's
+ * od_win_mono_min, od_moments_min, od_persist, mp_persist, stream_defer, od_graph, pipe_sr_sets, od_nn_lane,
+ * od_nn_lane_min (loam_velodyne-1_amd/csrc/engine.hpp, struct Tuning).  od_nn_lane: the odometry association's
+ * nearest neighbour on a lane per query in the TransformToStart launch, for batches of od_nn_lane_min (and
+ * od_sel_min) problems or more: 0 off (a wave per query), 1 in the seeded association rounds, 2 in every
+ * round.  Every choice computes the same results bit for bit except od_moments_min (the odometry's
  * stored rows as per-query fp64 moments: within the north star's 1e-4 of the reference);
  * the defaults are the measured fastest.  LOAM_E_INVAL for an unknown key or a value out of range.
  * Takes effect from the next call (waits for the context's queued work). */

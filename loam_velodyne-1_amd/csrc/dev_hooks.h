@@ -82,6 +82,37 @@ int loam_dev_nn5_run(loam_dev_nn5* h, const loam_dev_nn5_job* job, int32_t* flat
 
 int loam_dev_nn5_destroy(loam_dev_nn5* h);
 
+/* The odometry association's nearest neighbour (od.hip) on a caller's Last cloud and queries: the
+ * cloud's 1 m voxel hash and chunk boxes are built by the product's hash build (the odometry form),
+ * then every query is searched by the lane-per-query first stage (lane_hash_nn, k_od_sel_nn's) and by
+ * the wave-per-query search (wave_hash_nn, k_od_assoc's). */
+typedef struct loam_dev_od_nn loam_dev_od_nn;
+
+#define LOAM_DEV_OD_NN_MAX_CLOUD 16384
+#define LOAM_DEV_OD_NN_MAX_QUERIES 4096
+
+typedef struct {
+  const float* cloud;   /* [n_cloud][4] x, y, z, intensity: its integer part is the ring, 0 .. 255 */
+  int32_t n_cloud;      /* 1 .. LOAM_DEV_OD_NN_MAX_CLOUD */
+  const float* queries; /* [n_queries][4] x, y, z, - (the cloud's frame) */
+  int32_t n_queries;    /* 1 .. LOAM_DEV_OD_NN_MAX_QUERIES */
+  const int32_t* seeds; /* NULL: every query unseeded; else [n_queries] cloud indices, -1 = unseeded */
+} loam_dev_od_nn_job;
+
+/* LOAM_E_HIP without a GPU, LOAM_E_NOMEM */
+int loam_dev_od_nn_create(int device, loam_dev_od_nn** out);
+
+/* Keys are (bits of the float squared distance << 32 | cloud index << 8 | ring); ~0: none.
+ * lane_key [n_queries]: the lane search's word (~0 where it left the query to the wave: no point of
+ * its cells below 1 m2); wave_key: wave_hash_nn's result (its chunk stage included); chunk_key (or
+ * NULL): wave_chunk_nn alone, what k_od_assoc runs for a query the lane left; left [n_queries]: 1
+ * where lane_key is ~0.  LOAM_E_INVAL for sizes out of range, a seed outside [-1, n_cloud), a ring
+ * outside 0 .. 255, null pointers. */
+int loam_dev_od_nn_run(loam_dev_od_nn* h, const loam_dev_od_nn_job* job, uint64_t* lane_key, uint64_t* wave_key,
+                       uint64_t* chunk_key, int32_t* left);
+
+int loam_dev_od_nn_destroy(loam_dev_od_nn* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,13 @@ struct Tuning {
                            // iteration: O(queries) per iteration, not bit-identical, within 1e-4 of the
                            // reference on every benched problem (round 5: config 5
                            // k_od_rows 4.50 -> 2.49 ms/step, 1024 problems 1.37 -> 1.03)
+  int od_nn_lane = 2;      // the association's 27-cell nearest neighbour on a lane per query in the k_od_sel
+                           // launch (k_od_sel_nn) instead of a wave per query in k_od_assoc, for P >=
+                           // od_sel_min: 0 off, 1 the seeded rounds, 2 every round; bit-identical results
+                           // (1024 problems 12.06 -> 11.88 ms/step with 2, 11.92 with 1)
+  int od_nn_lane_min = 512;  // ... for P >= this: a lane's serial walk needs the chip full of other lanes
+                           // (128 problems: 1.79 -> 1.88 ms/step with it; config 5, 64 HDL-64E problems,
+                           // whose cells hold several times the points: 6.40 -> 8.49)
   // key = value (loam_set_tuning); false for an unknown key or a value out of range.  get: the
   // current value of a key (loam_get_tuning); false for an unknown key
   bool get(const char* key, long long* v) {
@@ -118,7 +125,8 @@ struct Tuning {
                     {"pipe_mp_sets", &pipe_mp_sets, 1, 2}, {"od_sel_min", &od_sel_min, 1, 1 << 20},
                     {"od_win_mono", &od_win_mono, 0, 3}, {"od_win_mono_min", &od_win_mono_min, 1, 1 << 20},
                     {"od_moments_min", &od_moments_min, 1, 1 << 30}, {"od_persist", &od_persist, 0, 1},
-                    {"mp_persist", &mp_persist, 0, 1}};
+                    {"mp_persist", &mp_persist, 0, 1}, {"od_nn_lane", &od_nn_lane, 0, 2},
+                    {"od_nn_lane_min", &od_nn_lane_min, 1, 1 << 20}};
     for (const K& k : ks)
       if (std::strcmp(key, k.n) == 0) {
         if (read) {

@@ -5,6 +5,8 @@
 //                 sort).  Replaces kdtreeCornerLast / kdtreeSurfLast (:78-79, :436-437, :905-906).
 //  the L-M loop (:465-828) as one launch sequence per iteration over every problem at once:
 //  k_od_begin     IMU prior, whether L-M runs (:461-465)
+//  k_od_sel(_nn)  batches, before k_od_assoc: TransformToStart of the queries on a lane each; for large
+//                 batches also the nearest neighbour within the 27 cells (tuning od_nn_lane)
 //  k_od_assoc     every 5th iteration, one wave per query: TransformToStart, exact NN through the
 //                 hash (27 cells; exhaustive fallback when the best match is farther than one cell),
 //                 then the ring-window scans of :486-523 / :598-645 as 64-wide chunks with a
@@ -18,7 +20,10 @@
 //                 NaN guard, convergence test (od_step)
 //  k_od_fini      pose accumulation (:830-856)
 //  k_od_end       TransformToEnd of lessSharp / lessFlat / full (:875-891) into the next Last clouds.
+#include <vector>
+
 #include "dev_common.hpp"
+#include "dev_hooks.h"
 #include "od.hpp"
 #include "pose_math.hpp"
 
@@ -395,6 +400,37 @@ struct WinBound {
   float same = 25.0f, other = 25.0f;
 };
 
+// the nearest neighbour beyond one cell (wave_hash_nn's second stage, and the whole wave search of
+// a query k_od_sel_nn left open): the minimum key over the chunks of the whole cloud whose box
+// may hold a point closer than 5 m and not beyond `bound`, or ~0
+LOAM_D uint64_t wave_chunk_nn(const float4* cloud, const float4* ch, int n, float4 q, float bound, int& wpts,
+                              int& wbox) {
+  const int lane = lane_id();
+  uint64_t best = ~0ull;
+  const int nch = (n + kChunk - 1) / kChunk;
+  for (int k0 = 0; k0 < nch; k0 += 64) {
+    const int k = k0 + lane;
+    float bd = 0.0f;
+    if (k < nch) bd = box_d2(ch[2 * k], ch[2 * k + 1], q);
+    const bool need = k < nch && bd < 25.0f && bd <= bound;
+    uint64_t nb = __ballot(need);
+    wbox += min(64, nch - k0);
+    while (nb) {
+      const int c = k0 + __ffsll((unsigned long long)nb) - 1;
+      nb &= nb - 1;
+      if (LOAM_ASSOC_PHASE == 0 || LOAM_ASSOC_PHASE == 2) wpts += min(kChunk, n - c * kChunk);
+      const int t = c * kChunk + lane;
+      if (lane < kChunk && t < n) {
+        const float4 a = cloud[t];
+        const float d = sqdist(a.x, a.y, a.z, q.x, q.y, q.z);
+        const uint64_t key = ((uint64_t)fkey(d) << 32) | ((uint32_t)t << 8) | (uint32_t)(int)a.w;
+        best = key < best ? key : best;
+      }
+    }
+  }
+  return wave_min_u64_x(best);
+}
+
 // exact nearest neighbour of q among the hashed cloud (wave-cooperative), as far as it matters:
 // returns the packed (float distance bits << 32 | index << 8 | ring) minimum (ties on the index,
 // as before: the ring is a function of the point), or ~0 when no point lies
@@ -475,30 +511,121 @@ LOAM_D uint64_t wave_hash_nn(const int* start, const float4* hp, int T, const fl
     return best;
   }
   if (LOAM_ASSOC_SKIP & 2) return best;
-  // farther than one cell: the chunks of the whole cloud that may hold a point closer than 5 m
-  best = ~0ull;
-  const int nch = (n + kChunk - 1) / kChunk;
-  for (int k0 = 0; k0 < nch; k0 += 64) {
-    const int k = k0 + lane;
-    float bd = 0.0f;
-    if (k < nch) bd = box_d2(ch[2 * k], ch[2 * k + 1], q);
-    const bool need = k < nch && bd < 25.0f && bd <= bound;
-    uint64_t nb = __ballot(need);
-    wbox += min(64, nch - k0);
-    while (nb) {
-      const int c = k0 + __ffsll((unsigned long long)nb) - 1;
-      nb &= nb - 1;
-      if (LOAM_ASSOC_PHASE == 0 || LOAM_ASSOC_PHASE == 2) wpts += min(kChunk, n - c * kChunk);
-      const int t = c * kChunk + lane;
-      if (lane < kChunk && t < n) {
-        const float4 a = cloud[t];
-        const float d = sqdist(a.x, a.y, a.z, q.x, q.y, q.z);
-        const uint64_t key = ((uint64_t)fkey(d) << 32) | ((uint32_t)t << 8) | (uint32_t)(int)a.w;
+  return wave_chunk_nn(cloud, ch, n, q, bound, wpts, wbox);
+}
+
+// ---- the same first stage with a lane per query (k_od_sel_nn): the minimum key over the points of
+// the cells wave_hash_nn's first stage visits (the same box test with the same bound), or kNnLaneNone
+// when none of them lies closer than 1 m — the query is then left to wave_chunk_nn.  The minimum
+// of a set does not depend on the visiting order, so a settled key equals wave_hash_nn's.
+// As knn5_flat (mp.hip): the 27 bucket ranges are loaded together, the non-empty ones listed in
+// the lane's LDS column `lst` (stride S, packed as hash_rec) and the concatenated candidates
+// gathered kLaneNnInFlight per step.  A range that does not pack sends the lane through its cells
+// one by one.  work: the candidates evaluated (wave_hash_nn's `total`).
+constexpr uint64_t kNnLaneNone = ~0ull;
+#ifndef LOAM_LANE_NN_INFLIGHT
+#define LOAM_LANE_NN_INFLIGHT 4
+#endif
+constexpr int kLaneNnInFlight = LOAM_LANE_NN_INFLIGHT;
+// (measured at 1024 problems, DESIGN.md §24: 2 / 4 / 8 gathers in flight 12.02 / 11.92 / 11.92 ms/step; the
+// range loads in groups of 9, 60 VGPRs: equal; a list of 16 or 12 entries for 8 waves per SIMD:
+// 12.2 / 12.4, the lanes beyond the list walk their cells one by one)
+constexpr int kLaneNnList = 27, kLaneNnGroup = 27;
+LOAM_D uint64_t nn_key(const float4& a, const float4& q) {
+  const float d = sqdist(a.x, a.y, a.z, q.x, q.y, q.z);
+  const uint32_t tag = (uint32_t)__float_as_int(a.w);  // index | ring << 24
+  return ((uint64_t)fkey(d) << 32) | ((tag & 0xffffffu) << 8) | (tag >> 24);
+}
+template <int S>
+LOAM_D uint64_t lane_hash_nn(const int* start, const float4* hp, int T, int n, float4 q, float bound, uint32_t* lst,
+                             int& work) {
+  if (T <= 0) return kNnLaneNone;
+  const int cx = cell_of(q.x, 1.0f), cy = cell_of(q.y, 1.0f), cz = cell_of(q.z, 1.0f);
+  auto bucket_of = [&](int c, bool& need) {
+    const int dx = c % 3 - 1, dy = (c / 3) % 3 - 1, dz = c / 9 - 1;
+    const float4 lo = make_float4((float)(cx + dx), (float)(cy + dy), (float)(cz + dz), 0.0f);
+    const float4 hi = make_float4((float)(cx + dx + 1), (float)(cy + dy + 1), (float)(cz + dz + 1), 0.0f);
+    const float bd = box_d2(lo, hi, q);
+    need = bd < 1.0f && bd <= bound;
+    return (int)(cell_hash(cx + dx, cy + dy, cz + dz) & (uint32_t)(T - 1));
+  };
+  int nl = 0, total = 0;
+  bool fits = true;
+  // (the range loads of a group of cells are issued together, then listed)
+#pragma unroll
+  for (int g0 = 0; g0 < 27; g0 += kLaneNnGroup) {
+    int2 rg[kLaneNnGroup];
+#pragma unroll
+    for (int u = 0; u < kLaneNnGroup; ++u) {
+      if (g0 + u >= 27) break;
+      bool need;
+      const int bk = bucket_of(g0 + u, need);
+      rg[u] = make_int2(0, 0);
+      if (need) rg[u] = load_pair(start + bk);
+    }
+#pragma unroll
+    for (int u = 0; u < kLaneNnGroup; ++u) {
+      if (g0 + u >= 27) break;
+      const int cnt = rg[u].y - rg[u].x;
+      LOAM_CHECK(rg[u].x >= 0 && cnt >= 0 && rg[u].x + cnt <= n, rg[u].x, cnt);
+      if (cnt > 0) {
+        const uint32_t e = hash_rec(rg[u].x, cnt);
+        if (e == kRecNone || nl == kLaneNnList) {
+          fits = false;
+        } else {
+          lst[nl * S] = e;
+          ++nl;
+        }
+        total += cnt;
+      }
+    }
+  }
+  if (LOAM_ASSOC_PHASE == 0 || LOAM_ASSOC_PHASE == 1) work += total;
+  uint64_t best = kNnLaneNone;
+  if (fits) {
+    // the list is walked one entry ahead (knn5_flat): the next entry's LDS read is off the chain
+    int ci = 1, left = 0, pos = 0;
+    uint32_t nx = lst[0];
+    auto next = [&]() {
+      if (left == 0) {
+        pos = (int)(nx & ((1u << 19) - 1));
+        left = (int)(nx >> 19);
+        nx = lst[min(ci, kLaneNnList - 1) * S];
+        ++ci;
+      }
+      --left;
+      return pos++;
+    };
+    for (int k = 0; k < total; k += kLaneNnInFlight) {
+      int idx[kLaneNnInFlight];
+#pragma unroll
+      for (int u = 0; u < kLaneNnInFlight; ++u) idx[u] = k + u < total ? next() : idx[0];
+      float4 a[kLaneNnInFlight];
+#pragma unroll
+      for (int u = 0; u < kLaneNnInFlight; ++u) {
+        LOAM_CHECK(idx[u] >= 0 && idx[u] < n, idx[u], n);
+        a[u] = hp[idx[u]];
+      }
+#pragma unroll
+      for (int u = 0; u < kLaneNnInFlight; ++u) {
+        const uint64_t key = nn_key(a[u], q);  // (a repeated candidate does not change a minimum)
+        best = key < best ? key : best;
+      }
+    }
+  } else {
+#pragma unroll 1
+    for (int c = 0; c < 27; ++c) {
+      bool need;
+      const int bk = bucket_of(c, need);
+      if (!need) continue;
+      const int2 r = load_pair(start + bk);
+      for (int k = r.x; k < r.y; ++k) {
+        const uint64_t key = nn_key(hp[k], q);
         best = key < best ? key : best;
       }
     }
   }
-  return wave_min_u64_x(best);
+  return best != kNnLaneNone && __uint_as_float((uint32_t)(best >> 32)) < 1.0f ? best : kNnLaneNone;
 }
 
 // One direction of a ring-window scan (:486-523 / :598-645) over the cloud L from c (exclusive):
@@ -878,6 +1005,53 @@ __global__ __launch_bounds__(kOdThreads) void k_od_sel(OdBuffers b, FeatView f) 
   b.sel[(size_t)p * b.cap_q + q] = loampose::transform_to_start(T, po);
 }
 
+// k_od_sel that also searches its query's nearest neighbour within the 27 cells (lane_hash_nn,
+// tuning od_nn_lane) and leaves the key, or kNnLaneNone, in b.nnw for k_od_assoc: the wave then
+// starts at the ring windows.  The bound is wave_hash_nn's: the previous round's nearest
+// neighbour at this transform (od_assoc_wave's nnb).  A wave may hold corner and surf queries:
+// the table is chosen per lane.  COUNT: the profiling form adds the candidates to kIsGathered.
+template <bool COUNT>
+__global__ __launch_bounds__(kOdThreads) void k_od_sel_nn(OdBuffers b, FeatView f, int last_buf) {
+  __shared__ uint32_t lst[kLaneNnList * kOdThreads];
+  const XcdBlock blk = xcd_block();
+  const int p = blk.y;
+  int* ist = b.istate + (size_t)p * kOdStateInts;
+  if (!ist[kIsActive] || ist[kIsStop]) return;
+  const float* st = b.state + (size_t)p * kOdStateFloats;
+  float T[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) T[k] = st[k];
+  const int nc = f.count(p, 0), nq = nc + f.count(p, 2);
+  const int q = blk.x * kOdThreads + threadIdx.x;
+  int work = 0;
+  if (q < nq) {
+    const bool corner = q < nc;
+    const float4 po = corner ? f.sharp[(size_t)p * f.sharp_stride + q] : f.flat[(size_t)p * f.flat_stride + (q - nc)];
+    const float4 s4 = loampose::transform_to_start(T, po);
+    b.sel[(size_t)p * b.cap_q + q] = s4;
+    const size_t lp = (size_t)last_buf * b.P + p;
+    const float4* L = corner ? b.lastC + lp * b.capC : b.lastS + lp * b.capS;
+    const int n = b.nlast[(p * kOdBufs + last_buf) * 2 + (corner ? 0 : 1)];
+    float bound = 3.4e38f;
+    if (ist[kIsIters] > 0) {  // seeded: ind holds this frame's previous round
+      const int j0 = b.ind[(size_t)p * 3 * b.cap_q + q];
+      if (j0 >= 0) {
+        const float4 sp = L[j0];
+        bound = sqdist(sp.x, sp.y, sp.z, s4.x, s4.y, s4.z);
+      }
+    }
+    const int* start = corner ? b.hC_start + lp * (b.tC + 1) : b.hS_start + lp * (b.tS + 1);
+    const float4* hp = corner ? b.hC_pts + lp * b.capC : b.hS_pts + lp * b.capS;
+    const int hT = corner ? b.hC_T[last_buf * b.P + p] : b.hS_T[last_buf * b.P + p];
+    b.nnw[(size_t)p * b.cap_q + q] = lane_hash_nn<kOdThreads>(start, hp, hT, n, s4, bound, lst + threadIdx.x, work);
+  }
+  if constexpr (COUNT) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) work += __shfl_xor(work, o, 64);
+    if (lane_id() == 0 && work) atomicAdd(&ist[kIsGathered], work);
+  }
+}
+
 // One wave's association queries q0, q0 + G, ... of problem p (:472-527, :587-650): k_od_assoc's
 // body, also the association phase of the persistent streaming L-M (k_od_lm_stream).  T: the
 // transform for TransformToStart (SEL; otherwise the queries' k_od_sel points are read); seeded:
@@ -886,7 +1060,8 @@ __global__ __launch_bounds__(kOdThreads) void k_od_sel(OdBuffers b, FeatView f) 
 template <bool SEL>
 LOAM_D void od_assoc_wave(const OdBuffers& b, const FeatView& f, int p, int last_buf, int q0, int G, const float* T,
                           bool seeded, int* cells, float4* bq_s4, float4* bq_d, int4* bq_j, const int* rsC,
-                          const int* rsS, int& wpts, int& wbox) {
+                          const int* rsS, int& wpts, int& wbox, const uint64_t* nnw = nullptr,
+                          uint64_t* bq_nn = nullptr) {
   const int lane = lane_id();
   const int nc = f.count(p, 0), ns = f.count(p, 2), nq = nc + ns;
   const size_t lp = (size_t)last_buf * b.P + p;
@@ -928,6 +1103,7 @@ LOAM_D void od_assoc_wave(const OdBuffers& b, const FeatView& f, int p, int last
         bq_s4[lane] = s4;
         bq_j[lane] = make_int4(j[0], j[1], j[2], (int)sp[1].w | ((int)sp[2].w << 16));
         bq_d[lane] = make_float4(nnb, d1, d2, 0.0f);
+        if (nnw) bq_nn[lane] = nnw[ql];
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -943,10 +1119,25 @@ LOAM_D void od_assoc_wave(const OdBuffers& b, const FeatView& f, int p, int last
       // the cells' window bounds in the first round only (later rounds have their seeds: the extra
       // pass over the cells cost more than the chunks it saved there)
       WinBound wb;
+      // the nearest neighbour: k_od_sel_nn's word where the round has one and nothing else is wanted
+      // from the cells (kind < 0: no window bounds, which LOAM_WIN_WB 1 takes in the first round),
+      // a query it left open through the chunks alone; otherwise the whole wave search
+      auto wave_nn = [&](bool corner, int kind, int fe, bool mono) {
+        const float4* L = corner ? CL : SL;
+        const float4* ch = corner ? b.cC + lp * 2 * chunks_of(b.capC) : b.cS + lp * 2 * chunks_of(b.capS);
+        const int n = corner ? C : S;
+        if (nnw && kind < 0) {
+          const uint64_t w = bq_nn[i];
+          if (w != kNnLaneNone || (LOAM_ASSOC_SKIP & 2)) return w;
+          return wave_chunk_nn(L, ch, n, s4, nnb, wpts, wbox);
+        }
+        return corner ? wave_hash_nn(b.hC_start + lp * (b.tC + 1), b.hC_pts + lp * b.capC, hCT, L, ch, n, 1.0f, 1.0f, s4,
+                                     nnb, cells, wpts, wbox, kind, fe, mono, &wb)
+                      : wave_hash_nn(b.hS_start + lp * (b.tS + 1), b.hS_pts + lp * b.capS, hST, L, ch, n, 1.0f, 1.0f, s4,
+                                     nnb, cells, wpts, wbox, kind, fe, mono, &wb);
+      };
       if (q < nc && monoC && use_mono) {
-        const float4* ch = b.cC + lp * 2 * chunks_of(b.capC);
-        const uint64_t nn = wave_hash_nn(b.hC_start + lp * (b.tC + 1), b.hC_pts + lp * b.capC, hCT, CL, ch, C, 1.0f,
-                                         1.0f, s4, nnb, cells, wpts, wbox, seeded || !LOAM_WIN_WB ? -1 : 0, min(nc, C), true, &wb);
+        const uint64_t nn = wave_nn(true, seeded || !LOAM_WIN_WB ? -1 : 0, min(nc, C), true);
         i1 = i2 = -1;
         if (nn != ~0ull && D(__uint_as_float((uint32_t)(nn >> 32))) < 25) {
           const int c = (int)((uint32_t)nn >> 8), scan = (int)((uint32_t)nn & 255u), fe = min(nc, C);
@@ -956,9 +1147,7 @@ LOAM_D void od_assoc_wave(const OdBuffers& b, const FeatView& f, int p, int last
           if (k3 != ~0ull) i2 = mono_decode(c, k3);
         }
       } else if (q >= nc && monoS && use_mono) {
-        const float4* ch = b.cS + lp * 2 * chunks_of(b.capS);
-        const uint64_t nn = wave_hash_nn(b.hS_start + lp * (b.tS + 1), b.hS_pts + lp * b.capS, hST, SL, ch, S, 1.0f,
-                                         1.0f, s4, nnb, cells, wpts, wbox, seeded || !LOAM_WIN_WB ? -1 : 1, min(ns, S), true, &wb);
+        const uint64_t nn = wave_nn(false, seeded || !LOAM_WIN_WB ? -1 : 1, min(ns, S), true);
         i1 = i2 = -1;
         if (nn != ~0ull && D(__uint_as_float((uint32_t)(nn >> 32))) < 25) {
           const int c = (int)((uint32_t)nn >> 8), scan = (int)((uint32_t)nn & 255u), fe = min(ns, S);
@@ -971,13 +1160,11 @@ LOAM_D void od_assoc_wave(const OdBuffers& b, const FeatView& f, int p, int last
         }
       } else if (q < nc) {
         const float4* ch = b.cC + lp * 2 * chunks_of(b.capC);
-        const uint64_t nn = wave_hash_nn(b.hC_start + lp * (b.tC + 1), b.hC_pts + lp * b.capC, hCT, CL, ch, C, 1.0f,
-                                         1.0f, s4, nnb, cells, wpts, wbox, seeded ? -1 : 0, min(nc, C), monoC, &wb);
+        const uint64_t nn = wave_nn(true, seeded ? -1 : 0, min(nc, C), monoC);
         wave_assoc_corner(CL, ch, min(nc, C), nn, s4, j1, r1, d1, wb, monoC, i1, i2, wpts, wbox);
       } else {
         const float4* ch = b.cS + lp * 2 * chunks_of(b.capS);
-        const uint64_t nn = wave_hash_nn(b.hS_start + lp * (b.tS + 1), b.hS_pts + lp * b.capS, hST, SL, ch, S, 1.0f,
-                                         1.0f, s4, nnb, cells, wpts, wbox, seeded ? -1 : 1, min(ns, S), monoS, &wb);
+        const uint64_t nn = wave_nn(false, seeded ? -1 : 1, min(ns, S), monoS);
         wave_assoc_surf(SL, ch, min(ns, S), nn, s4, j1, r1, d1, j2, r2, d2, wb, monoS, i1, i2, i3, wpts, wbox);
       }
       if (lane == 0) {
@@ -1003,12 +1190,13 @@ LOAM_D void od_assoc_wave(const OdBuffers& b, const FeatView& f, int p, int last
 // slower; per-query certificates that settle a seeded query without a search, round 5: exact, 31 %
 // of the queries settled at config 4, but slower: DESIGN.md §15)
 template <bool COUNT, bool SEL>
-__global__ __launch_bounds__(kAsThreads) __attribute__((amdgpu_waves_per_eu(SEL ? 1 : 8))) void k_od_assoc(OdBuffers b, FeatView f, int last_buf) {
+__global__ __launch_bounds__(kAsThreads) __attribute__((amdgpu_waves_per_eu(SEL ? 1 : 8))) void k_od_assoc(OdBuffers b, FeatView f, int last_buf, int nn_lane) {
   const XcdBlock blk = xcd_block();
   const int p = blk.y, lane = lane_id(), w = threadIdx.x >> 6;
   const int* ist = b.istate + (size_t)p * kOdStateInts;
   if (!ist[kIsActive] || ist[kIsStop]) return;
   __shared__ int cells[kAsWaves][64];
+  __shared__ uint64_t bq_nn[kAsWaves][64];  // k_od_sel_nn's words of the staged queries (nn_lane)
   __shared__ float4 bq_s4[kAsWaves][64], bq_d[kAsWaves][64];
   __shared__ int4 bq_j[kAsWaves][64];
   __shared__ int rsC[kRingTab], rsS[kRingTab];  // the ring start tables (ring-monotone clouds)
@@ -1028,7 +1216,8 @@ __global__ __launch_bounds__(kAsThreads) __attribute__((amdgpu_waves_per_eu(SEL 
   int wpts = 0, wbox = 0;  // wave-uniform work counters (loam_stats od_assoc_gathered / _boxes)
   const bool seeded = ist[kIsIters] > 0;  // ind holds this frame's previous round
   od_assoc_wave<SEL>(b, f, p, last_buf, blk.x * kAsWaves + w, gridDim.x * kAsWaves, T, seeded, cells[w], bq_s4[w],
-                     bq_d[w], bq_j[w], rsC, rsS, wpts, wbox);
+                     bq_d[w], bq_j[w], rsC, rsS, wpts, wbox,
+                     !SEL && nn_lane ? b.nnw + (size_t)p * b.cap_q : nullptr, bq_nn[w]);
   if (COUNT && lane == 0) {
     if (wpts) atomicAdd((int*)&ist[kIsGathered], wpts);
     if (wbox) atomicAdd((int*)&ist[kIsBoxes], wbox);
@@ -1981,6 +2170,7 @@ hipError_t od_alloc(OdBuffers& b, int P, int R, int cap_pts, int max_iter) {
   A(&b.hS_T, (size_t)kOdBufs * P * sizeof(int));
   A(&b.ind, (size_t)P * 3 * b.cap_q * sizeof(int));
   A(&b.sel, (size_t)P * b.cap_q * sizeof(float4));
+  A(&b.nnw, (size_t)P * b.cap_q * sizeof(uint64_t));
   A(&b.q_cf, (size_t)P * max_iter * b.cap_q * sizeof(float4));
   A(&b.q_ok, (size_t)P * max_iter * b.cap_q * sizeof(int8_t));
   A(&b.mom, (size_t)P * kOdMom * b.cap_q * sizeof(double));
@@ -2018,7 +2208,7 @@ void od_free(OdBuffers& b) {
   if (b.hash_done) (void)hipEventDestroy(b.hash_done);
   void* ptrs[] = {b.state_set[0], b.state_set[1], b.state_set[2], b.istate_set[0], b.istate_set[1], b.istate_set[2], b.lastC, b.lastS, b.fullEnd, b.nlast, b.nfullEnd, b.hC_start,
                   b.hS_start, b.hC_fill, b.hS_fill, b.hC_pts, b.hS_pts, b.hC_T, b.hS_T, b.cC, b.cS,
-                  b.ind, b.sel, b.q_cf, b.q_ok, b.mom, b.qa, b.part, b.done, b.mono, b.rstart, b.fC, b.fS,
+                  b.ind, b.sel, b.nnw, b.q_cf, b.q_ok, b.mom, b.qa, b.part, b.done, b.mono, b.rstart, b.fC, b.fS,
                   b.ls_part, b.ls_flag, b.ls_epoch};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
@@ -2106,15 +2296,20 @@ void od_solve(const OdBuffers& b, const FeatView& f, int last_buf, hipStream_t s
       const int ga = P >= 64 ? (tn.od_assoc_wg > 0 ? tn.od_assoc_wg : std::max(16, std::min(1024, b.cap_q / 9)))
                              : (b.cap_q + kAsWaves - 1) / kAsWaves;
       if (P >= tn.od_sel_min) {
-        hipLaunchKernelGGL(k_od_sel, dim3(b.gq, P), dim3(kOdThreads), 0, st, b, f);
+        // the nearest neighbour on a lane per query in the k_od_sel launch (od_nn_lane: 1 the seeded
+        // rounds, 2 every round; iteration 0 is the unseeded one) for batches of od_nn_lane_min or more
+        const int nnl = P >= tn.od_nn_lane_min && (tn.od_nn_lane == 2 || (tn.od_nn_lane == 1 && it > 0)) ? 1 : 0;
+        if (!nnl) hipLaunchKernelGGL(k_od_sel, dim3(b.gq, P), dim3(kOdThreads), 0, st, b, f);
+        else if (prof) hipLaunchKernelGGL(k_od_sel_nn<true>, dim3(b.gq, P), dim3(kOdThreads), 0, st, b, f, last_buf);
+        else hipLaunchKernelGGL(k_od_sel_nn<false>, dim3(b.gq, P), dim3(kOdThreads), 0, st, b, f, last_buf);
         if (prof) {
-          hipLaunchKernelGGL((k_od_assoc<true, false>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf);
+          hipLaunchKernelGGL((k_od_assoc<true, false>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, nnl);
         } else {
-          hipLaunchKernelGGL((k_od_assoc<false, false>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf);
+          hipLaunchKernelGGL((k_od_assoc<false, false>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, nnl);
         }
       } else {
-        if (prof) hipLaunchKernelGGL((k_od_assoc<true, true>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf);
-        else hipLaunchKernelGGL((k_od_assoc<false, true>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf);
+        if (prof) hipLaunchKernelGGL((k_od_assoc<true, true>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, 0);
+        else hipLaunchKernelGGL((k_od_assoc<false, true>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, 0);
       }
       mark("k_od_assoc");
     }
@@ -2144,6 +2339,176 @@ void od_fini(const OdBuffers& b, const FeatView& f, hipStream_t st) {
 }
 }  // namespace loam
 
+
+// ---------------------------------------------------------------- the lane nearest neighbour's diagnostic hook
+namespace loam {
+namespace {
+struct DevOdNn {
+  const float4 *cloud, *hp, *ch, *qs;
+  const int *start, *seeds;  // seeds: [nq] cloud indices, -1 = unseeded, or nullptr
+  int n, T, nq;
+  uint64_t *lane, *wave, *chunk;  // [nq] each
+};
+LOAM_D float dev_od_nn_bound(const DevOdNn& d, int q, float4 s4) {
+  const int j0 = d.seeds ? d.seeds[q] : -1;
+  if (j0 < 0) return 3.4e38f;
+  const float4 sp = d.cloud[j0];
+  return sqdist(sp.x, sp.y, sp.z, s4.x, s4.y, s4.z);
+}
+// k_od_sel_nn's form: a lane per query, kOdThreads workgroups
+__global__ __launch_bounds__(kOdThreads) void k_dev_od_nn_lane(DevOdNn d) {
+  __shared__ uint32_t lst[kLaneNnList * kOdThreads];
+  const int q = blockIdx.x * kOdThreads + threadIdx.x;
+  if (q >= d.nq) return;
+  const float4 s4 = d.qs[q];
+  int work = 0;
+  d.lane[q] = lane_hash_nn<kOdThreads>(d.start, d.hp, d.T, d.n, s4, dev_od_nn_bound(d, q, s4), lst + threadIdx.x, work);
+}
+// k_od_assoc's form: a wave per query; wave_hash_nn, and wave_chunk_nn alone (what a query the lane
+// left open gets)
+__global__ __launch_bounds__(64) void k_dev_od_nn_wave(DevOdNn d) {
+  __shared__ int cells[64];
+  const int q = blockIdx.x;
+  const float4 s4 = d.qs[q];
+  const float bound = dev_od_nn_bound(d, q, s4);
+  int wpts = 0, wbox = 0;
+  const uint64_t w = wave_hash_nn(d.start, d.hp, d.T, d.cloud, d.ch, d.n, 1.0f, 1.0f, s4, bound, cells, wpts, wbox);
+  const uint64_t c = wave_chunk_nn(d.cloud, d.ch, d.n, s4, bound, wpts, wbox);
+  if (lane_id() == 0) {
+    d.wave[q] = w;
+    d.chunk[q] = c;
+  }
+}
+}  // namespace
+}  // namespace loam
+
+struct loam_dev_od_nn {
+  int device = 0;
+  hipStream_t st = nullptr;
+  float4 *cloud = nullptr, *hpts = nullptr, *hpts2 = nullptr, *qs = nullptr, *chunks = nullptr, *chunks2 = nullptr;
+  int *start = nullptr, *start2 = nullptr, *fill = nullptr, *fill2 = nullptr, *count = nullptr, *tsize = nullptr;
+  int* seeds = nullptr;
+  uint64_t* keys = nullptr;  // [3][LOAM_DEV_OD_NN_MAX_QUERIES]
+};
+
+namespace {
+void dev_od_nn_free(loam_dev_od_nn* h) {
+  void* ptrs[] = {h->cloud, h->hpts, h->hpts2, h->qs, h->chunks, h->chunks2, h->start, h->start2,
+                  h->fill, h->fill2, h->count, h->tsize, h->seeds, h->keys};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  if (h->st) (void)hipStreamDestroy(h->st);
+  delete h;
+}
+}  // namespace
+
+extern "C" int loam_dev_od_nn_create(int device, loam_dev_od_nn** out) {
+  if (!out) return LOAM_E_INVAL;
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return LOAM_E_HIP;  // (no CPU path, as loam_create)
+  if (device < 0 || device >= ndev) return LOAM_E_INVAL;
+  if (hipSetDevice(device) != hipSuccess) return LOAM_E_HIP;
+  loam_dev_od_nn* h = new loam_dev_od_nn();
+  h->device = device;
+  const size_t M = LOAM_DEV_OD_NN_MAX_CLOUD, Q = LOAM_DEV_OD_NN_MAX_QUERIES;
+  loam::DevAlloc A;
+  A(&h->cloud, M * sizeof(float4));
+  A(&h->hpts, M * sizeof(float4));
+  A(&h->hpts2, M * sizeof(float4));
+  A(&h->qs, Q * sizeof(float4));
+  A(&h->chunks, 2 * (size_t)loam::chunks_of((int)M) * sizeof(float4));
+  A(&h->chunks2, 2 * (size_t)loam::chunks_of((int)M) * sizeof(float4));
+  A(&h->start, (M + 1) * sizeof(int));
+  A(&h->start2, (M + 1) * sizeof(int));
+  A(&h->fill, M * sizeof(int));
+  A(&h->fill2, M * sizeof(int));
+  A(&h->count, 2 * sizeof(int));
+  A(&h->tsize, 2 * sizeof(int));
+  A(&h->seeds, Q * sizeof(int));
+  A(&h->keys, 3 * Q * sizeof(uint64_t));
+  hipError_t e = A.err;
+  if (e == hipSuccess) e = hipStreamCreate(&h->st);
+  if (e != hipSuccess) {
+    dev_od_nn_free(h);
+    return e == hipErrorOutOfMemory ? LOAM_E_NOMEM : LOAM_E_HIP;
+  }
+  *out = h;
+  return LOAM_OK;
+}
+
+extern "C" int loam_dev_od_nn_run(loam_dev_od_nn* h, const loam_dev_od_nn_job* job, uint64_t* lane_key,
+                                  uint64_t* wave_key, uint64_t* chunk_key, int32_t* left) {
+  using namespace loam;
+  if (!h || !job || !lane_key || !wave_key || !left) return LOAM_E_INVAL;
+  const int n = job->n_cloud, nq = job->n_queries;
+  if (!job->cloud || !job->queries || n < 1 || n > LOAM_DEV_OD_NN_MAX_CLOUD || nq < 1 || nq > LOAM_DEV_OD_NN_MAX_QUERIES)
+    return LOAM_E_INVAL;
+  if (job->seeds)
+    for (int k = 0; k < nq; ++k)
+      if (job->seeds[k] < -1 || job->seeds[k] >= n) return LOAM_E_INVAL;
+  for (int k = 0; k < n; ++k) {  // the ring rides in a byte of the key
+    const float r = job->cloud[4 * k + 3];
+    if (!(r >= 0.0f && r < 256.0f)) return LOAM_E_INVAL;
+  }
+  hipStream_t st = h->st;
+  auto up = [&](void* d, const void* s, size_t bytes) { return hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, st); };
+  const int cnt2[2] = {n, 0};  // (the hash build takes two clouds: the second one is empty)
+  hipError_t e = hipSetDevice(h->device);
+  if (e == hipSuccess) e = up(h->cloud, job->cloud, (size_t)n * sizeof(float4));
+  if (e == hipSuccess) e = up(h->qs, job->queries, (size_t)nq * sizeof(float4));
+  if (e == hipSuccess) e = up(h->count, cnt2, sizeof(cnt2));
+  if (e == hipSuccess && job->seeds) e = up(h->seeds, job->seeds, (size_t)nq * sizeof(int));
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    return LOAM_E_HIP;
+  }
+  // the cloud's index as od_build_hashes builds a Last cloud's (1 m cells, two points per bucket, chunk boxes)
+  HashJob hc;
+  hc.pts = h->cloud; hc.pts_stride = LOAM_DEV_OD_NN_MAX_CLOUD; hc.pts_off = nullptr; hc.pts_off_stride = 0;
+  hc.count = h->count; hc.count_stride_bytes = 2 * sizeof(int);
+  hc.start = h->start; hc.fill = h->fill; hc.out = h->hpts; hc.tsize = h->tsize; hc.tmax = LOAM_DEV_OD_NN_MAX_CLOUD;
+  hc.inv_h = 1.0f;
+  hc.shift = 1;
+  hc.chunks = h->chunks;
+  HashJob hs = hc;
+  hs.count = h->count + 1; hs.start = h->start2; hs.fill = h->fill2; hs.out = h->hpts2; hs.tsize = h->tsize + 1;
+  hs.chunks = h->chunks2;
+  hash_build_pair(hc, hs, 1, st, true);
+  int T = 0;
+  e = hipMemcpyAsync(&T, h->tsize, sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return LOAM_E_HIP;
+  DevOdNn d;
+  d.cloud = h->cloud; d.hp = h->hpts; d.ch = h->chunks; d.qs = h->qs;
+  d.start = h->start; d.seeds = job->seeds ? h->seeds : nullptr;
+  d.n = n; d.T = T; d.nq = nq;
+  const size_t Q = LOAM_DEV_OD_NN_MAX_QUERIES;
+  d.lane = h->keys; d.wave = h->keys + Q; d.chunk = h->keys + 2 * Q;
+  hipLaunchKernelGGL(k_dev_od_nn_lane, dim3((nq + kOdThreads - 1) / kOdThreads), dim3(kOdThreads), 0, st, d);
+  hipLaunchKernelGGL(k_dev_od_nn_wave, dim3(nq), dim3(64), 0, st, d);
+  e = hipGetLastError();
+  std::vector<uint64_t> ck((size_t)nq);
+  if (e == hipSuccess) e = hipMemcpyAsync(lane_key, d.lane, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(wave_key, d.wave, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(ck.data(), d.chunk, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return LOAM_E_HIP;
+  for (int q = 0; q < nq; ++q) {
+    left[q] = lane_key[q] == ~0ull ? 1 : 0;
+    if (chunk_key) chunk_key[q] = ck[q];
+  }
+  return LOAM_OK;
+}
+
+extern "C" int loam_dev_od_nn_destroy(loam_dev_od_nn* h) {
+  if (!h) return LOAM_E_INVAL;
+  (void)hipSetDevice(h->device);
+  if (h->st) (void)hipStreamSynchronize(h->st);
+  dev_od_nn_free(h);
+  return LOAM_OK;
+}
 
 #ifdef LOAM_PHASES
 // the phase sums of the last-workgroup kernel of this file (PhaseAcc, dev_common.hpp); diagnostic

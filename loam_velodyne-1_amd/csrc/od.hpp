@@ -118,6 +118,8 @@ struct OdBuffers {
   float4* fC = nullptr;     // [kOdBufs][P][2 * subs_of(capC)] sub-chunk boxes of Last corner (HashJob::fine)
   float4* fS = nullptr;     // [kOdBufs][P][2 * subs_of(capS)] sub-chunk boxes of Last surf
   float4* sel = nullptr;      // [P][cap_q] queries at the current transform (association rounds)
+  uint64_t* nnw = nullptr;    // [P][cap_q] k_od_sel_nn: the nearest neighbour's key (distance bits << 32 | index << 8 |
+                              // ring) of every query settled within its 27 cells, else ~0 (tuning od_nn_lane)
   int* ind = nullptr;         // [P][3][cap_q] association of every query (refreshed every 5th iteration)
   float4* q_cf = nullptr;     // [P][max_iter][cap_q] coefficients (zero when rejected)
   int8_t* q_ok = nullptr;     // [P][max_iter][cap_q] accepted flags
