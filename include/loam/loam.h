@@ -389,8 +389,11 @@ int loam_map_score(loam_ctx *ctx, const loam_cloud_out *corner, const loam_cloud
  * not they have an IMU.  A step runs the
  * batch's kernels on all lanes at once (one launch sequence per step, not per sequence) and keeps
  * what the streaming path keeps from sweep to sweep: the Last clouds, transformSum, the cube maps,
- * Bef / Aft.  system_delay, the odometry's init frame, skip_frame_num and the surround phase advance
- * identically in every lane, so published and mapped are the same for every live lane of a step.
+ * Bef / Aft.  system_delay, the odometry's init frame and skip_frame_num advance identically in every
+ * lane, so published and mapped are the same for every live lane of a step that was never restarted.
+ * A restarted lane (loam_lanes_restart) reports LOAM_E_NOT_READY on its wait steps and published =
+ * LOAM_PUB_CLOUDS, mapped = 0 on its own init step, whatever the others report; its mapped can be 0
+ * where theirs is 1 only on those steps, and is never 1 where theirs is 0.
  * The lanes never take the two launch forms loam_set_tuning's od_persist / mp_persist and
  * od_moments_min select, at any n_lanes (1 included), and no tuning turns them on:
  *   - the per-query moments are not bit-identical to the other forms, and a sequence compounds a
@@ -402,7 +405,7 @@ int loam_map_score(loam_ctx *ctx, const loam_cloud_out *corner, const loam_cloud
 #define LOAM_LANES_MAX 1024
 
 typedef struct {
-  int32_t status;     /* LOAM_OK, LOAM_E_NOT_READY inside system_delay, or the lane's sticky failure */
+  int32_t status;     /* LOAM_OK, LOAM_E_NOT_READY inside system_delay and on a restarted lane's wait steps, or the lane's sticky failure */
   int32_t published;  /* loam_odometry's LOAM_PUB_* flags of this lane's frame */
   int32_t mapped;     /* 1 when laserMapping ran on this sweep */
   int32_t od_iters, mp_iters;   /* L-M iterations of this frame's odometry / mapping (0 when none ran) */
@@ -459,9 +462,36 @@ int loam_lanes_pull(loam_ctx *ctx, loam_lane_out *out /* [n_lanes] */);
  * n_lanes).  LOAM_E_CAPACITY writes the required size into out->count. */
 int loam_lanes_registered(loam_ctx *ctx, uint32_t lane, loam_cloud_out *out);
 /* loam_map_export for one lane's map: canonical cube order, centre, Aft / Bef; surround_phase is
- * the lanes' shared mapping frame counter.  LOAM_E_INVAL while a step is in flight, for a failed
+ * the lane's own mapping frame counter (4 at open and at a restart, advanced on each of the lane's
+ * mapping frames; the same in every lane that was never restarted).  LOAM_E_INVAL while a step is in flight, for a failed
  * lane and for lane >= n_lanes. */
 int loam_lanes_map_export(loam_ctx *ctx, uint32_t lane, loam_map *out);
+/* Lane `lane` becomes a fresh sequence: empty map, centre (10, 5, 10), zero transformSum / Bef / Aft,
+ * odometry not initialised, empty IMU queues (host and device; loam_lanes_imu accepts any first
+ * stamp again), surround_phase 4, sticky failure cleared.  From its first consumed sweep on, the
+ * lane behaves exactly as a fresh context created with system_delay = 0 that receives the lane's
+ * IMU messages (those sent after this call) through loam_imu and its sweeps through
+ * loam_chain_sweep: bit for bit, whatever the other lanes do.  No other lane changes by a bit.
+ * A live lane may be restarted (a parameter sweep over one recording), and so may a failed or a
+ * retired one; a second restart before the lane's init step only recomputes the wait.
+ * Phase rule: the lanes keep one launch sequence per step, so mapping runs on the same steps for
+ * every lane.  The lane's init frame (Last = the raw lessSharp / lessFlat clouds, no L-M, published
+ * = LOAM_PUB_CLOUDS) is taken on the step before a mapping step of the shared phase, as a fresh
+ * context maps on the frame after its init frame.  With s = skip_frame_num and c = the shared
+ * odometry frame counter (s at the shared init frame, 0 after a mapping step, + 1 per other step)
+ *     *wait_steps = (2 s - c) mod (s + 1),   in 0..s:
+ * the number of coming steps on which raw[lane] is not looked at and the lane reports status =
+ * LOAM_E_NOT_READY and zero /imu_trans.  The caller offers the sequence's first sweep on the step
+ * after them; that step is the lane's init step (mapped = 0 even where the other lanes map).
+ * Called inside system_delay or before the shared init frame, the lane is cleared and takes the
+ * shared init frame with the others; *wait_steps is then the number of steps until that frame.
+ * A restarted lane consumes no system_delay of its own: the caller drops the sweeps its node would
+ * not have looked at (the node never looks at them either).
+ * The clear is one kernel launch for all lanes restarted between two steps, in front of the next
+ * step; the first call allocates two lane lists (n_lanes ints each, pinned and device).
+ * LOAM_E_INVAL, and nothing is changed: null context or wait_steps, lanes not open, lane >=
+ * n_lanes, a step in flight.  LOAM_E_NOMEM when the first call's allocation fails. */
+int loam_lanes_restart(loam_ctx *ctx, uint32_t lane, uint32_t *wait_steps);
 /* Frees the lanes' working set (waits for a step in flight).  LOAM_E_INVAL when not open. */
 int loam_lanes_close(loam_ctx *ctx);
 

@@ -186,6 +186,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_map_localize", "loam_map_score", "loam_get_stats",
            "loam_lanes_open", "loam_lanes_push", "loam_lanes_pull", "loam_lanes_registered", "loam_lanes_map_export",
            "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
+           "loam_lanes_restart",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -243,6 +244,7 @@ def lib():
         L.loam_lanes_imu.argtypes = [PP, ctypes.c_uint32, ctypes.c_double, P(ctypes.c_double), P(ctypes.c_double)]
         L.loam_lanes_push_stamped.argtypes = [PP, P(ctypes.c_double), P(CloudIn)]
         L.loam_lanes_imu_trans.argtypes = [PP, P(ctypes.c_float)]
+        L.loam_lanes_restart.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -562,6 +564,15 @@ class Engine:
         q = (ctypes.c_double * 4)(*[float(v) for v in quat_xyzw])
         a = (ctypes.c_double * 3)(*[float(v) for v in lin_acc])
         _check(lib().loam_lanes_imu(self.h, int(lane), stamp, q, a))
+
+    def lanes_restart(self, lane):
+        """lane `lane` becomes a fresh sequence (loam_lanes_restart).  Returns wait_steps: the number
+        of coming steps on which the lane's sweep is not looked at (status LOAM_E_NOT_READY); the
+        sequence's first sweep goes in on the step after them, the lane's init step.  With s =
+        skip_frame_num and c the shared odometry frame counter it is (2 s - c) mod (s + 1)."""
+        w = ctypes.c_uint32(0)
+        _check(lib().loam_lanes_restart(self.h, int(lane), ctypes.byref(w)))
+        return int(w.value)
 
     def lanes_imu_trans(self):
         """/imu_trans of every lane from the last pulled step (loam_lanes_imu_trans): an

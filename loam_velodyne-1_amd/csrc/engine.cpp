@@ -2296,7 +2296,8 @@ bool lanes_will_map(const loam_ctx* x) {
 // one step's device work on x->st, behind the sweeps' upload; sets L.step_pub / L.step_mapped
 // imu: the step's LaneHdr block and new queue entries are on the device (lanes_imu_put): the ring
 // sort takes the tile-parallel IMU form and k_lanes_imu follows it
-hipError_t lanes_enqueue(loam_ctx* x, Prof* pf, bool imu) {
+// n_init: the lanes whose own init frame this step is (loam_lanes_restart), listed at L.rs_d + S
+hipError_t lanes_enqueue(loam_ctx* x, Prof* pf, bool imu, int n_init) {
   Lanes& L = x->lanes;
   const int S = L.S;
   hipStream_t st = x->st;
@@ -2334,6 +2335,10 @@ hipError_t lanes_enqueue(loam_ctx* x, Prof* pf, bool imu) {
     const bool pub = L.od_frame_count >= (int)x->cfg.skip_frame_num + 1;
     hipLaunchKernelGGL(k_od_end, dim3(kOdEndWg, S), dim3(256), 0, st, o, f, nxt, 2, pub ? 1 : 0);
     x->prof.mark("k_od_end");
+    if (n_init) {  // restarted lanes: the init frame's Last clouds and state over the ordinary frame's
+      T(lanes_init_frame(L, f, L.rs_d + S, n_init, nxt, st));
+      x->prof.mark("k_lanes_init");
+    }
     od_build_hashes(o, nxt, st);
     x->prof.mark("k_hash_build_last");
     L.od_last = nxt;
@@ -2353,7 +2358,12 @@ hipError_t lanes_enqueue(loam_ctx* x, Prof* pf, bool imu) {
       in.pose = o.state + kOdSum; in.pose_stride = kOdStateFloats;
       mp_frame(L.mp, in, st, pf);
       L.step_mapped = 1;
-      if (++L.map_frame_count >= 5) L.map_frame_count = 0;  // :1038-1040
+      for (int l = 0; l < S; ++l)  // :1038-1040, for the lanes this was a mapping frame for
+        if (L.life[l].kind == kLaneRuns && ++L.life[l].phase >= 5) L.life[l].phase = 0;
+      if (n_init) {  // (skip_frame_num = 0) an init frame does not map: the lane's store is empty again
+        T(lanes_restart_clear(L, L.rs_d + S, n_init, kClearMp, st));
+        x->prof.mark("k_lanes_restart");
+      }
     }
   }
   T(lanes_out(L, st));
@@ -2421,14 +2431,25 @@ int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud
   HIP_TRY(hipSetDevice(x->device));
   // a lane whose sweep cannot be uploaded, and a lane that failed before, is an empty sweep on the
   // device: its slot goes through the kernels as an empty problem of a batch does
+  // a restarted lane: an empty problem too until its init frame, and raw[l] is not looked at
+  int n_clear = 0, n_init = 0;
+  for (int l = 0; l < S; ++l) {
+    LaneLife& f = L.life[l];
+    f.kind = kLaneRuns;
+    if (f.wait < 0) continue;
+    f.kind = f.wait == 0 ? kLaneInits : kLaneWaits;
+    L.rs_h[n_clear++] = l;
+    if (f.kind == kLaneInits) L.rs_h[S + n_init++] = l;
+  }
   std::vector<loam_cloud_in> eff((size_t)S);
   int* nn = L.tab_h;
   int* off = nn + S;
   size_t run = 0;
   for (int l = 0; l < S; ++l) {
-    L.fail_new[l] = lane_sweep_code(raw[l], x->cap);
+    const bool waits = L.life[l].kind == kLaneWaits;
+    L.fail_new[l] = waits ? LOAM_OK : lane_sweep_code(raw[l], x->cap);
     eff[l] = raw[l];
-    if (L.fail_new[l] != LOAM_OK || L.fail[l] != LOAM_OK) eff[l].count = 0;
+    if (waits || L.fail_new[l] != LOAM_OK || L.fail[l] != LOAM_OK) eff[l].count = 0;
     nn[l] = (int)eff[l].count;
     off[l] = (int)run;
     run += eff[l].count;
@@ -2436,6 +2457,12 @@ int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud
   hipStream_t st = x->st;
   Prof* pf = x->prof.on ? &x->prof : nullptr;
   x->prof.begin(st);
+  if (n_clear) {  // the restarted lanes as lanes_alloc left them, in front of everything the step does
+    HIP_TRY(hipMemcpyAsync(L.rs_d, L.rs_h, (size_t)2 * S * sizeof(int), hipMemcpyHostToDevice, st));
+    x->prof.mark("lanes_h2d");
+    HIP_TRY(lanes_restart_clear(L, L.rs_d, n_clear, kClearOd | kClearMp | (I.on ? kClearImu : 0), st));
+    x->prof.mark("k_lanes_restart");
+  }
   // packed in chunks of sweeps, each chunk's copy enqueued before the next is packed
   constexpr int kPushChunk = 128;  // sweeps
   for (int s0 = 0; s0 < S; s0 += kPushChunk) {
@@ -2451,7 +2478,9 @@ int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud
   // IMU: any live lane with a message makes this an IMU step for all lanes
   bool imu = false;
   if (I.on) {
-    auto live = [&](int l) { return L.fail[l] == LOAM_OK && L.fail_new[l] == LOAM_OK; };
+    auto live = [&](int l) {
+      return L.fail[l] == LOAM_OK && L.fail_new[l] == LOAM_OK && L.life[l].kind != kLaneWaits;
+    };
     for (int l = 0; l < S && !imu; ++l) imu = live(l) && I.sr[l].last >= 0;
     if (imu) {
       const bool will_map = lanes_will_map(x);
@@ -2469,7 +2498,9 @@ int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud
         if (!h.has) continue;
         // transformUpdate's blend (src/laserMapping.cpp:199-226) at this lane's stamp, from its
         // committed pointer; the pull commits the advanced one when the lane's L-M ran
-        if (will_map && loamimu::mp_lookup(I.mp[l], h.time_scan, h.roll, h.pitch, I.mp_front[l])) {
+        // (not on the lane's own init frame, which does not map)
+        if (will_map && L.life[l].kind == kLaneRuns &&
+            loamimu::mp_lookup(I.mp[l], h.time_scan, h.roll, h.pitch, I.mp_front[l])) {
           h.mp_flag = 1;
           I.mp_have[l] = 1;
         }
@@ -2482,7 +2513,8 @@ int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud
     }
   }
   x->prof.mark("lanes_h2d");
-  const hipError_t he = lanes_enqueue(x, pf, imu);
+  const hipError_t he = lanes_enqueue(x, pf, imu, n_init);
+  for (int l = 0; l < n_clear; ++l) L.life[L.rs_h[l]].wait--;  // (an init frame ends the restart: -1)
   L.in_flight = true;
   L.step_ran = true;
   I.step_imu = imu;
@@ -2530,6 +2562,51 @@ extern "C" int loam_lanes_imu(loam_ctx* x, uint32_t lane, double stamp, const do
   return LOAM_OK;
 }
 
+extern "C" int loam_lanes_restart(loam_ctx* x, uint32_t lane, uint32_t* wait_steps) {
+  if (!x || !wait_steps) return fail(LOAM_E_INVAL, "null argument");
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_restart: lanes are not open");
+  if (lane >= (uint32_t)L.S) return fail(LOAM_E_INVAL, "loam_lanes_restart: lane index out of range");
+  if (L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_restart: a step is in flight (loam_lanes_pull first)");
+  const int s = (int)x->cfg.skip_frame_num;
+  LaneLife& f = L.life[lane];
+  if (L.od_inited) {
+    if (!L.rs_h) {  // the first restart: the steps' lane lists
+      HIP_TRY(hipSetDevice(x->device));
+      const hipError_t he = lanes_restart_alloc(L);
+      if (he != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(LOAM_E_NOMEM, std::string("loam_lanes_restart: allocation failed: ") + hipGetErrorString(he));
+      }
+    }
+    // The lane's init frame is the step before a mapping step of the shared phase (a fresh context
+    // maps on the frame after its init frame: od_frame_count = s, and the init frame does not
+    // count).  Step j from here maps when od_frame_count + j reaches s + 1 (mod s + 1), so the init
+    // frame is step j = s - od_frame_count (mod s + 1), in 1..s+1, and j - 1 steps are waited.
+    f.wait = (2 * s - L.od_frame_count) % (s + 1);
+    *wait_steps = (uint32_t)f.wait;
+  } else {
+    // before the shared init frame nothing of the lane is on the device yet: it takes that frame
+    // with the others, after what is left of system_delay (Q1: one step at least)
+    *wait_steps = L.sr_inited ? 0u : (uint32_t)std::max(1, (int)x->cfg.system_delay - L.sr_init_count);
+  }
+  f.phase = 4;  // mapFrameCount = mapFrameNum - 1 (src/laserMapping.cpp:405)
+  L.fail[lane] = LOAM_OK;
+  L.fail_new[lane] = LOAM_OK;
+  L.nreg[lane] = 0;
+  LanesImu& I = L.imu;
+  if (I.on) {  // the lane's queues as lanes_imu_alloc left them (the device's: k_lanes_restart)
+    std::memset(&I.sr[lane], 0, sizeof(I.sr[lane]));
+    std::memset(&I.mp[lane], 0, sizeof(I.mp[lane]));
+    I.sr[lane].last = I.mp[lane].last = -1;
+    I.last_stamp[lane] = -1e300;
+    I.n_new[lane] = 0;
+    I.mp_front[lane] = 0;
+    I.mp_have[lane] = 0;
+  }
+  return LOAM_OK;
+}
+
 extern "C" int loam_lanes_imu_trans(loam_ctx* x, float* out) {
   if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
   Lanes& L = x->lanes;
@@ -2566,12 +2643,19 @@ extern "C" int loam_lanes_pull(loam_ctx* x, loam_lane_out* out) {
   for (int l = 0; l < S; ++l) {
     const int* w = L.out_h + (size_t)l * kLaneOutWords;
     loam_lane_out& q = out[l];
+    const int kind = L.life[l].kind;
+    if (kind == kLaneWaits) {  // restarted, before its init frame: its sweep was not looked at
+      L.nreg[l] = 0;
+      q.status = LOAM_E_NOT_READY;
+      continue;
+    }
+    const bool mapped = L.step_mapped && kind == kLaneRuns;
     if (L.fail[l] == LOAM_OK) {  // this step's failure, the host's finding first
       int code = L.fail_new[l];
       if (code == LOAM_OK && (w[kLoSrErr] & ERR_EMPTY)) code = LOAM_E_INVAL;
       if (code == LOAM_OK && (w[kLoSrErr] & ERR_CAP_RING)) code = LOAM_E_CAPACITY;
       if (code == LOAM_OK && w[kLoOdErr]) code = LOAM_E_CAPACITY;
-      if (code == LOAM_OK && L.step_mapped && w[kLoMpErr]) code = LOAM_E_CAPACITY;
+      if (code == LOAM_OK && mapped && w[kLoMpErr]) code = LOAM_E_CAPACITY;
       L.fail[l] = code;
     }
     L.nreg[l] = 0;
@@ -2580,13 +2664,13 @@ extern "C" int loam_lanes_pull(loam_ctx* x, loam_lane_out* out) {
       continue;
     }
     q.status = LOAM_OK;
-    q.published = L.step_pub;
-    q.mapped = L.step_mapped;
-    if (L.step_pub & LOAM_PUB_POSE) {
+    q.published = kind == kLaneInits ? LOAM_PUB_CLOUDS : L.step_pub;
+    q.mapped = mapped ? 1 : 0;
+    if (q.published & LOAM_PUB_POSE) {
       q.od_iters = w[kLoOdIters];
       std::memcpy(&q.od_sum, w + kLoOdSum, sizeof(loam_pose6));
     }
-    if (L.step_mapped) {
+    if (mapped) {
       q.mp_iters = w[kLoMpIters];
       std::memcpy(&q.aft, w + kLoAft, sizeof(loam_pose6));
       std::memcpy(&q.bef, w + kLoBef, sizeof(loam_pose6));
@@ -2631,7 +2715,7 @@ extern "C" int loam_lanes_map_export(loam_ctx* x, uint32_t lane, loam_map* out) 
   if (L.fail[lane] != LOAM_OK) return fail(LOAM_E_INVAL, "loam_lanes_map_export: the lane has failed");
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipStreamSynchronize(x->st));
-  return map_export_of(x, L.mp, (int)lane, L.map_frame_count, out);
+  return map_export_of(x, L.mp, (int)lane, L.life[lane].phase, out);
 }
 
 namespace loam {

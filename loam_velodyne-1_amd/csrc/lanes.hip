@@ -102,7 +102,146 @@ __global__ __launch_bounds__(256) void k_lanes_imu(const loamimu::LaneHdr* hdr, 
     if (w == 14) d.mp_istate[(size_t)l * kMpStateInts + kMiImu] = h.mp_flag;
   }
 }
+struct LaneClear {
+  // the odometry problem and the sweep's error word
+  float* od_state;   // [S][kOdStateFloats]
+  int* od_istate;    // [S][kOdStateInts]
+  int* nlast;        // [S][kOdBufs][2]
+  int* nfullEnd;     // [S][kOdBufs]
+  int *hC_T, *hS_T;  // [kOdBufs][S]
+  int* od_done;      // [S]
+  int* sr_err;       // [S]
+  // the mapping store
+  float* mp_state;   // [S][kMpStateFloats]
+  int* mp_istate;    // [S][kMpStateInts]
+  int4* slots;       // [2][S][kCubeNum]
+  int* mp_done;      // [S]
+  int* nreg;         // [S]
+  // the IMU side (null before the first loam_lanes_imu)
+  int* q;            // [S][kQueWords]
+  int* tail;         // [S][kTailWords]
+  int* tile_key;     // [S][ntile3]
+  int ntile3;
+  int S;
+};
+constexpr int kQueWords = (int)(sizeof(loamimu::SrQueue) / 4), kTailWords = (int)(sizeof(loamimu::SrTail) / 4);
+static_assert(sizeof(loamimu::SrQueue) % 4 == 0 && sizeof(loamimu::SrTail) % 4 == 0, "cleared by words");
+constexpr int kRestartTiles = 10;  // workgroups per lane: each pool's 4851 slot entries in two coalesced passes
+
+// loam_lanes_restart: lane list[blockIdx.y] as lanes_alloc (od_alloc, mp_alloc's mp_reset,
+// lanes_imu_alloc) left it.  The two pools' slot tables are the bulk (an int4 per cube, coalesced
+// over the workgroups of the lane); workgroup 0 also clears the lane's small blocks.  A lane
+// appears once in the list and no word is shared between lanes: plain stores.
+__global__ __launch_bounds__(256) void k_lanes_restart(LaneClear c, const int* list, int what) {
+  const int l = list[blockIdx.y];
+  if (l < 0 || l >= c.S) return;
+  const int tid = threadIdx.x;
+  if (what & kClearMp) {
+    const int4 z = make_int4(0, 0, 0, 0);
+    for (int pool = 0; pool < 2; ++pool) {
+      int4* s = c.slots + ((size_t)pool * c.S + l) * kCubeNum;
+      for (int i = blockIdx.x * 256 + tid; i < kCubeNum; i += gridDim.x * 256) s[i] = z;
+    }
+  }
+  if (blockIdx.x != 0) return;
+  if (what & kClearMp) {
+    if (tid < kMpStateFloats) c.mp_state[(size_t)l * kMpStateFloats + tid] = 0.0f;
+    if (tid < kMpStateInts)  // laserCloudCenWidth / Height / Depth (src/laserMapping.cpp:64-66), as k_mp_reset
+      c.mp_istate[(size_t)l * kMpStateInts + tid] = tid == kMiCenW || tid == kMiCenD ? 10 : tid == kMiCenH ? 5 : 0;
+    if (tid == 0) { c.mp_done[l] = 0; c.nreg[l] = 0; }
+  }
+  if (what & kClearOd) {
+    if (tid < kOdStateFloats) c.od_state[(size_t)l * kOdStateFloats + tid] = 0.0f;
+    if (tid < kOdStateInts) c.od_istate[(size_t)l * kOdStateInts + tid] = 0;
+    if (tid < kOdBufs * 2) c.nlast[l * kOdBufs * 2 + tid] = 0;
+    if (tid < kOdBufs) {
+      c.nfullEnd[l * kOdBufs + tid] = 0;
+      c.hC_T[tid * c.S + l] = 0;
+      c.hS_T[tid * c.S + l] = 0;
+    }
+    if (tid == 0) { c.od_done[l] = 0; c.sr_err[l] = 0; }
+  }
+  if ((what & kClearImu) && c.q) {
+    for (int i = tid; i < kQueWords; i += 256) c.q[(size_t)l * kQueWords + i] = 0;
+    for (int i = tid; i < kTailWords; i += 256) c.tail[(size_t)l * kTailWords + i] = 0;
+    for (int i = tid; i < c.ntile3; i += 256) c.tile_key[(size_t)l * c.ntile3 + i] = 0;
+  }
+}
+
+// A restarted lane's init frame inside a step whose shared launches ran an ordinary frame on it
+// (its odometry inactive: the cleared CornerLastNum / SurfLastNum, src/laserOdometry.cpp:465).
+// Lane list[blockIdx.y] ends the step as k_od_end's mode 0 and od_frame's init frame leave a
+// context (src/laserOdometry.cpp:427-456): Last[dst] = the raw lessSharp / lessFlat clouds with
+// their fractional intensities, no full cloud, transform = 0, transformSum = (0 + imuPitchStart, 0,
+// 0 + imuRollStart, 0, 0, 0) from the /imu_trans k_lanes_imu left in the state (zeros without IMU),
+// matP and the int state zero, the overflow of a Last cloud in the error word.
+__global__ __launch_bounds__(256) void k_lanes_init(OdBuffers b, FeatView f, const int* list, int dst) {
+  const int p = list[blockIdx.y];
+  if (p < 0 || p >= b.P) return;
+  const int nl = f.count(p, 1), nf = f.count(p, 3);
+  const int cl = min(nl, b.capC), cf = min(nf, b.capS);
+  float4* oc = b.lastC + ((size_t)dst * b.P + p) * b.capC;
+  float4* os = b.lastS + ((size_t)dst * b.P + p) * b.capS;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < cl + cf; i += gridDim.x * 256) {
+    if (i < cl) oc[i] = f.lsharp[(size_t)p * f.lsharp_stride + i];
+    else os[i - cl] = f.lflat[(size_t)p * f.lflat_stride + (i - cl)];
+  }
+  if (blockIdx.x != 0) return;
+  float* st = b.state + (size_t)p * kOdStateFloats;
+  int* ist = b.istate + (size_t)p * kOdStateInts;
+  const int w = threadIdx.x;
+  if (w < kOdImu) st[w] = w == kOdSum || w == kOdSum + 2 ? 0.0f + st[kOdImu + (w - kOdSum)] : 0.0f;
+  if (w < kOdStateInts) ist[w] = w == kIsErr && (nl > b.capC || nf > b.capS) ? ERR_CAP_ROWS : 0;
+  if (w == 0) {
+    b.nlast[(p * kOdBufs + dst) * 2 + 0] = cl;
+    b.nlast[(p * kOdBufs + dst) * 2 + 1] = cf;
+    b.nfullEnd[p * kOdBufs + dst] = 0;
+  }
+}
 }  // namespace
+
+hipError_t lanes_restart_alloc(Lanes& L) {
+  if (L.rs_h) return hipSuccess;
+  hipError_t e = hipHostMalloc((void**)&L.rs_h, (size_t)2 * L.S * sizeof(int), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&L.rs_d, (size_t)2 * L.S * sizeof(int));
+  if (e != hipSuccess) {
+    if (L.rs_h) (void)hipHostFree(L.rs_h);
+    L.rs_h = nullptr;
+    L.rs_d = nullptr;
+  }
+  return e;
+}
+
+hipError_t lanes_restart_clear(Lanes& L, const int* list_d, int n, int what, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  LaneClear c;
+  c.od_state = L.od.state;
+  c.od_istate = L.od.istate;
+  c.nlast = L.od.nlast;
+  c.nfullEnd = L.od.nfullEnd;
+  c.hC_T = L.od.hC_T;
+  c.hS_T = L.od.hS_T;
+  c.od_done = L.od.done;
+  c.sr_err = L.sr.err;
+  c.mp_state = L.mp.state;
+  c.mp_istate = L.mp.istate;
+  c.slots = (int4*)L.mp.slots;
+  c.mp_done = L.mp.done;
+  c.nreg = L.mp.nreg;
+  c.q = (int*)L.imu.q_d;
+  c.tail = (int*)L.imu.tail_d;
+  c.tile_key = L.imu.tile_key_d;
+  c.ntile3 = L.sr.ntiles() * 3;
+  c.S = L.S;
+  hipLaunchKernelGGL(k_lanes_restart, dim3(kRestartTiles, n), dim3(256), 0, st, c, list_d, what);
+  return hipGetLastError();
+}
+
+hipError_t lanes_init_frame(Lanes& L, const FeatView& f, const int* list_d, int n, int dst, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_lanes_init, dim3(kOdEndWg, n), dim3(256), 0, st, L.od, f, list_d, dst);
+  return hipGetLastError();
+}
 
 Tuning lanes_tuning(Tuning t) {
   t.od_persist = 0;
@@ -133,6 +272,7 @@ hipError_t lanes_alloc(Lanes& L, int S, int cap, int R, int map_cap, int od_max_
   L.fail.assign(S, LOAM_OK);
   L.fail_new.assign(S, LOAM_OK);
   L.nreg.assign(S, 0);
+  L.life.assign(S, LaneLife());
   return hipSuccess;
 }
 
@@ -222,6 +362,8 @@ void lanes_free(Lanes& L) {
   if (L.tab_d) (void)hipFree(L.tab_d);
   if (L.out_d) (void)hipFree(L.out_d);
   if (L.out_h) (void)hipHostFree(L.out_h);
+  if (L.rs_h) (void)hipHostFree(L.rs_h);
+  if (L.rs_d) (void)hipFree(L.rs_d);
   L = Lanes();
 }
 

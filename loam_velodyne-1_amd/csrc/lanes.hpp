@@ -41,6 +41,16 @@ struct LanesImu {
   size_t up_bytes = 0;               // what the last IMU step uploaded
 };
 
+// a lane's own life cycle (loam_lanes_restart); the host owns it
+struct LaneLife {
+  int wait = -1;   // -1: the lane follows the shared counters; >= 0: restarted, its init frame is the step after `wait` more
+  int kind = 0;    // the step in flight: kLaneRuns, kLaneWaits (an empty problem, LOAM_E_NOT_READY) or kLaneInits
+  int phase = 4;   // laserMapping's mapFrameCount of this lane (loam_lanes_map_export's surround_phase)
+};
+enum { kLaneRuns = 0, kLaneWaits, kLaneInits };
+// what k_lanes_restart clears of a lane
+enum { kClearOd = 1, kClearMp = 2, kClearImu = 4 };
+
 struct Lanes {
   int S = 0;           // 0: not open
   SrBuffers sr;        // S sweeps
@@ -58,7 +68,12 @@ struct Lanes {
   // laserOdometry's systemInited / frameCount, laserMapping's mapFrameCount
   int sr_init_count = 0;
   bool sr_inited = false, od_inited = false;
-  int od_last = 0, od_frame_count = 1, map_frame_count = 4;
+  int od_last = 0, od_frame_count = 1;
+  std::vector<LaneLife> life;  // [S]
+  // loam_lanes_restart's lists of a step (allocated by the first restart): the lanes to clear in
+  // front of it, then the lanes whose init frame it is
+  int* rs_h = nullptr;         // pinned [2S]
+  int* rs_d = nullptr;         // device [2S]
   // the protocol: a step pushed and not yet pulled; what that step published; whether the last
   // pulled step left registered clouds
   bool in_flight = false, step_ran = false, have_reg = false;
@@ -89,6 +104,16 @@ hipError_t lanes_imu_put(Lanes& L, size_t bytes, int nrec, hipStream_t st);
 // odometry state (od_init: and transformSum's start, src/laserOdometry.cpp:451-452) and into
 // imu.trans_d, and on mapping steps every lane's (roll, pitch, flag) into the mapping state
 hipError_t lanes_imu_commit(Lanes& L, bool od_init, bool mapping, hipStream_t st);
+
+// the restart lists' buffers (the first loam_lanes_restart)
+hipError_t lanes_restart_alloc(Lanes& L);
+// k_lanes_restart: one launch that leaves the n lanes of list_d (device) as lanes_alloc left them,
+// in the parts `what` names (kClear*)
+hipError_t lanes_restart_clear(Lanes& L, const int* list_d, int n, int what, hipStream_t st);
+// k_lanes_init, behind the step's shared k_od_end and in front of its hash build: the n lanes of
+// list_d end the step as the odometry's init frame leaves a context: Last[dst] = the raw lessSharp
+// / lessFlat clouds, transform zero, transformSum zero or the IMU start pitch / roll, istate zero
+hipError_t lanes_init_frame(Lanes& L, const FeatView& f, const int* list_d, int n, int dst, hipStream_t st);
 
 }  // namespace loam
 #endif

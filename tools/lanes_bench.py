@@ -2,7 +2,7 @@
 stepped by loam_chain_sweep from one thread, through the C-ABI on one GPU.
 
   python tools/lanes_bench.py [--s 1,16,64] [--sweeps 27] [--map-cap 131072] [--yard-max 1024]
-                              [--profile-s 64] [--imu] [--out FILE]
+                              [--profile-s 64] [--imu] [--restart K,M] [--occupancy N] [--out FILE]
 
 Per S: S lanes over eight distinct VLP-16 synthetic streams laid out cyclically.  The wall time of
 lanes_step (push + pull), and of the push alone (host packing + enqueue), median and range over the
@@ -16,7 +16,21 @@ synthgen.imu_stream of its stream (100 Hz, the messages up to each sweep's end b
 through loam_lanes_imu, and the yardstick contexts get the same messages through loam_imu before
 their chain_sweep; the time of those calls is reported on its own (imu_feed_ms, per
 step) and is not part of the step times on either side.  One JSON line per S.  Run under a time
-limit."""
+limit.
+
+--restart K,M (instead of the above): per S, one lanes run of --sweeps steps whose
+first half has no restart and whose second half restarts K lanes (K = 0: S / 4) before every M-th
+step through loam_lanes_restart: the wall time of lanes_step in both halves (mapping steps and the
+others apart), of the restart calls per event, and the parent's only alternative measured in the
+same process, loam_lanes_close + loam_lanes_open; then the same run once more with
+loam_set_profiling on in the second half for k_lanes_restart's and k_lanes_init's device time per
+launch (the profiled run's wall times are not reported: the events cost time).
+A restarted lane goes on with its stream's next sweeps (as a fresh sequence).
+
+--occupancy N (instead of the above): a directory of N synthetic recordings of 10..40 sweeps over
+S = 16 lanes, (a) recycled: a lane whose recording has ended is restarted onto the next one, (b)
+retired and left dead: waves of 16 recordings, each wave a loam_lanes_open ... loam_lanes_close that
+lasts as long as its longest recording.  Total sweeps per second both ways, open / close included."""
 import argparse
 import importlib
 import json
@@ -140,6 +154,106 @@ def run_yardstick(n, streams, K, map_cap, imu=None):
     return res, last
 
 
+def run_restart(S, streams, K, map_cap, k_lanes, every, profile):
+    eng = loam.Engine(loam.default_config(system_delay=1))
+    t0 = time.perf_counter()
+    eng.lanes_open(S, map_cap)
+    open_ms = (time.perf_counter() - t0) * 1e3
+    half = K // 2
+    step = {(on, m): [] for on in (False, True) for m in (0, 1)}
+    calls, nxt, events = [], 0, 0
+    for k in range(K):
+        raws = [streams[l % N_STREAMS][k] for l in range(S)]
+        on = k >= half
+        if k == half and profile:
+            eng.set_profiling(True)
+        if on and (k - half) % every == 0:
+            t0 = time.perf_counter()
+            for _ in range(k_lanes):
+                eng.lanes_restart(nxt % S)
+                nxt += 1
+            calls.append((time.perf_counter() - t0) * 1e3)
+            events += 1
+        t0 = time.perf_counter()
+        eng.lanes_push(raws, stamp=0.1 * k)
+        o = eng.lanes_pull()
+        if k >= 2 + WARM:
+            step[(on, int(o["mapped"].max()))].append((time.perf_counter() - t0) * 1e3)
+    if profile:
+        kt = eng.kernel_times()
+        eng.close()
+        return dict(device_ms_per_launch={n: round(kt[n][0] / kt[n][1], 4) for n in ("k_lanes_restart", "k_lanes_init")
+                                          if n in kt and kt[n][1]},
+                    launches={n: kt[n][1] for n in ("k_lanes_restart", "k_lanes_init") if n in kt})
+    t0 = time.perf_counter()
+    eng.lanes_close()
+    t1 = time.perf_counter()
+    eng.lanes_open(S, map_cap)
+    t2 = time.perf_counter()
+    eng.lanes_close()
+    eng.close()
+    return dict(S=S, restart_lanes=k_lanes, every=every, sweeps=K, first_open_ms=round(open_ms, 1),
+                step_mapped_ms_without=spread(step[(False, 1)]), step_mapped_ms_with=spread(step[(True, 1)]),
+                step_unmapped_ms_without=spread(step[(False, 0)]), step_unmapped_ms_with=spread(step[(True, 0)]),
+                restart_events=events, restart_calls_ms_per_event=spread(calls),
+                close_ms=round((t1 - t0) * 1e3, 2), reopen_ms=round((t2 - t1) * 1e3, 2),
+                close_plus_open_ms=round((t2 - t0) * 1e3, 2))
+
+
+def run_occupancy(n_rec, streams, map_cap, S=16):
+    rng = np.random.default_rng(0)
+    lens = [int(v) for v in rng.integers(10, 41, size=n_rec)]
+    recs = [(i % N_STREAMS, lens[i]) for i in range(n_rec)]
+    empty = np.zeros((0, 4), np.float32)
+    # (a) recycled with loam_lanes_restart; a recording's sweep 0 is the one system_delay drops
+    eng = loam.Engine(loam.default_config(system_delay=1))
+    t0 = time.perf_counter()
+    eng.lanes_open(S, map_cap)
+    todo = list(range(n_rec))
+    lane = [None] * S  # (recording, next sweep, steps to wait)
+    for l in range(S):
+        lane[l] = (todo.pop(0), 0, 0) if todo else None
+    steps = restarts = 0
+    while any(v is not None for v in lane):
+        raws = []
+        for l in range(S):
+            if lane[l] is not None and lane[l][2] == 0 and lane[l][1] >= recs[lane[l][0]][1]:
+                lane[l] = None  # the recording has ended: the next one, or the lane is retired
+                if todo:
+                    lane[l] = (todo.pop(0), 1, eng.lanes_restart(l))
+                    restarts += 1
+            if lane[l] is None:
+                raws.append(empty)
+                continue
+            r, j, w = lane[l]
+            raws.append(streams[recs[r][0]][j if w == 0 else 0])
+            lane[l] = (r, j + 1, 0) if w == 0 else (r, j, w - 1)
+        if any(v is not None for v in lane):
+            eng.lanes_step(raws, stamp=0.1 * steps)
+            steps += 1
+    eng.lanes_close()
+    recycled_s = time.perf_counter() - t0
+    # (b) waves of S recordings, an ended one fed count = 0 until the wave's longest has ended
+    t0 = time.perf_counter()
+    wsteps = 0
+    for w0 in range(0, n_rec, S):
+        wave = recs[w0:w0 + S]
+        eng.lanes_open(len(wave), map_cap)
+        for k in range(max(n for _, n in wave)):
+            eng.lanes_step([streams[i][k] if k < n else empty for i, n in wave], stamp=0.1 * k)
+            wsteps += 1
+        eng.lanes_close()
+    waves_s = time.perf_counter() - t0
+    eng.close()
+    total = sum(lens)
+    return dict(occupancy_recordings=n_rec, S=S, sweeps_total=total, lengths_min_max=[min(lens), max(lens)],
+                recycled=dict(steps=steps, restarts=restarts, wall_s=round(recycled_s, 3),
+                              sweeps_per_s=round(total / recycled_s, 1), occupancy=round(total / (steps * S), 3)),
+                left_dead=dict(steps=wsteps, waves=(n_rec + S - 1) // S, wall_s=round(waves_s, 3),
+                               sweeps_per_s=round(total / waves_s, 1), occupancy=round(total / (wsteps * S), 3)),
+                recycled_over_left_dead=round(waves_s / recycled_s, 3))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--s", default="1,16,64")
@@ -148,9 +262,11 @@ def main():
     ap.add_argument("--yard-max", type=int, default=1024)
     ap.add_argument("--profile-s", type=int, default=0)
     ap.add_argument("--imu", action="store_true")
+    ap.add_argument("--restart", default=None, help="K,M: restart K lanes (0: S / 4) before every M-th step")
+    ap.add_argument("--occupancy", type=int, default=0, help="recordings of 10..40 sweeps over 16 lanes")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    K = a.sweeps
+    K = 40 if a.occupancy else a.sweeps
     streams = [sg.stream_sweeps(K, 1 + i) for i in range(N_STREAMS)]
     imu = imu_schedules(K) if a.imu else None
     pts = int(np.mean([sw.shape[0] for sw in streams[0]]))
@@ -165,6 +281,17 @@ def main():
                 for ln in lines:
                     f.write(json.dumps(ln) + "\n")
 
+    if a.occupancy:
+        emit(run_occupancy(a.occupancy, streams, a.map_cap))
+        return
+    if a.restart:
+        k_lanes, every = [int(v) for v in a.restart.split(",")]
+        for S in [int(v) for v in a.s.split(",") if v]:
+            n = k_lanes or max(1, S // 4)
+            line = run_restart(S, streams, K, a.map_cap, n, every, False)
+            line.update(run_restart(S, streams, K, a.map_cap, n, every, True))
+            emit(line)
+        return
     for S in [int(v) for v in a.s.split(",") if v]:
         res, last, _, _ = run_lanes(S, streams, K, a.map_cap, imu=imu)
         ny = min(S, a.yard_max)
