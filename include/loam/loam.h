@@ -93,7 +93,8 @@ typedef struct {
   uint64_t n_sharp, n_less_sharp, n_flat, n_less_flat;
   uint64_t od_iters, od_assoc_rounds, od_rows_sum, od_corner_last, od_surf_last, od_queries;
   uint64_t od_assoc_points;                     /* sum over problems of rounds x (C + S) */
-  uint64_t mp_iters, mp_rows_sum, mp_stack, mp_map_points, mp_map_valid_points;
+  uint64_t mp_iters, mp_rows_sum, mp_stack, mp_map_points;
+  uint64_t mp_map_valid_points;                 /* points of the valid cubes after the last map update (a batch: prev's, its only one) */
   uint64_t mp_stack_iters;                      /* sum over problems of iterations x stack size */
   uint64_t mp_fits;                             /* line / plane fits computed (the rest reused: same ordered 5-NN) */
   uint64_t od_query_iters;                      /* sum over problems of L-M iterations x queries (sharp + flat) */
@@ -190,7 +191,12 @@ int loam_maintenance(const loam_pose6 *odom_sum, const loam_pose6 *bef, const lo
  * n >= 64 (tunings step_pipe / sr_ahead) consecutive runs overlap as a software pipeline — a run's
  * odometry beside the previous run's mapping, the next run's scan registration and odometry seed
  * enqueued ahead (they re-run the same uploaded problems, unless loam_batch_feed supplies each run's
- * sweeps) — and sync waits for all of it.  download returns the last run's results. */
+ * sweeps) — and sync waits for all of it.  download returns the last run's results.
+ * A problem ends at cur's solved pose: the map with cur inserted and the registered clouds
+ * (/velodyne_cloud_registered) are not built, since no batch call returns them.  So in a batch's
+ * stats mp_map_valid_points is the figure of prev's map update (the only one that runs), and the
+ * map-store overflow that only inserting cur could raise (LOAM_E_CAPACITY from download) is not
+ * raised; an overflow while mapping prev, or of a stack, still is. */
 int loam_batch_upload(loam_ctx *ctx, uint32_t n, const loam_cloud_in *prev,
                       const loam_cloud_in *cur);
 int loam_batch_run(loam_ctx *ctx);

@@ -1173,7 +1173,7 @@ int loam_batch_upload(loam_ctx* x, uint32_t n, const loam_cloud_in* prev, const 
     hipError_t he = sr_alloc(x->srb, 2 * (int)n, x->cap, x->R);
     if (he == hipSuccess) he = od_alloc(x->odb, (int)n, x->R, x->cap, (int)x->cfg.od_max_iter);
     if (he == hipSuccess)
-      he = mp_alloc(x->mpb, (int)n, x->R, x->cap, mp_batch_map_capacity(x->cap), (int)x->cfg.mp_max_iter);
+      he = mp_alloc(x->mpb, (int)n, x->R, x->cap, mp_batch_map_capacity(x->cap), (int)x->cfg.mp_max_iter, /*batch=*/true);
     if (he != hipSuccess) {
       sr_free(x->srb);
       sr_free(x->srb2);
@@ -1233,7 +1233,7 @@ int ensure_second_sets(loam_ctx* x, int slots) {
   if (x->srb2.S) return LOAM_OK;
   hipError_t he = sr_alloc(x->srb2, 2 * P, x->cap, x->R);
   if (he == hipSuccess)
-    he = mp_alloc(x->mpb2, P, x->R, x->cap, mp_batch_map_capacity(x->cap), (int)x->cfg.mp_max_iter);
+    he = mp_alloc(x->mpb2, P, x->R, x->cap, mp_batch_map_capacity(x->cap), (int)x->cfg.mp_max_iter, /*batch=*/true);
   if (he != hipSuccess) {
     sr_free(x->srb2);
     sr_free(x->srb3);
@@ -1286,7 +1286,6 @@ hipError_t batch_enqueue(loam_ctx* x, Prof* pf, bool events) {
   };
   ahead_point(0);
   // odometry seeded from prev as a solved zero-increment frame, then one loop body on cur
-  // (the full clouds' TransformToEnd happens in mapping's registration kernel, mp_batch_frame*)
   if (x->seed_ready) {  // enqueued one step ahead (st3, seed_done)
     T(hipStreamWaitEvent(x->st, x->seed_done, 0));
     x->seed_ready = false;
@@ -1305,7 +1304,7 @@ hipError_t batch_enqueue(loam_ctx* x, Prof* pf, bool events) {
   if (overlap) {
     T(hipEventRecord(x->fork, x->st));
     T(hipStreamWaitEvent(x->st2, x->fork, 0));
-    mp_batch_frame1(x->mpbuf(idx), o, ls, fprev, x->st2, nullptr);
+    mp_batch_frame1(x->mpbuf(idx), o, ls, x->st2, nullptr);
     T(hipEventRecord(x->join, x->st2));
   }
   // the pose accumulation (k_od_fini, one serial double-trig chain per problem) beside
@@ -1325,15 +1324,15 @@ hipError_t batch_enqueue(loam_ctx* x, Prof* pf, bool events) {
   if (overlap) {
     T(hipStreamWaitEvent(x->st, x->join, 0));
   } else {
-    mp_batch_frame1(x->mpbuf(idx), o, ls, fprev, x->st, pf);
+    mp_batch_frame1(x->mpbuf(idx), o, ls, x->st, pf);
   }
   ahead_point(2);
   if (ahead) T(hipEventRecord(x->seed_at, x->st));
-  // (frame 1 is done: the second stream is free for frame 2's independent branches)
+  // (frame 1 is done: the second stream is free for frame 2's stack VoxelGrid)
   SideStream side;
   side.st = x->st2;
-  side.fork[0] = x->fork; side.join[0] = x->join; side.fork[1] = x->fork2; side.join[1] = x->join2;
-  mp_batch_frame2(x->mpbuf(idx), o, le, fcur, x->st, pf, overlap ? &side : nullptr);
+  side.fork = x->fork; side.join = x->join;
+  mp_batch_frame2(x->mpbuf(idx), o, le, x->st, pf, overlap ? &side : nullptr);
   x->mp_last = idx;
   if (events) T(hipEventRecord(x->ev[3], x->st));
   x->srb_last = idx;
@@ -1424,7 +1423,7 @@ hipError_t batch_enqueue_pipe(loam_ctx* x) {
   if (!x->sr_ready || !x->seed_ready) T(enqueue_ahead(x, idx, ls, seed_free_last(x, idx, n)));
   x->sr_ready = x->seed_ready = false;
   x->od_s_last = ls;
-  const FeatView fprev = feat_view(sb, 0, 2), fcur = feat_view(sb, 1, 2);
+  const FeatView fcur = feat_view(sb, 1, 2);
   // odometry (st)
   o.istate = o.istate_set[idx];
   o.state = o.state_set[idx];
@@ -1443,8 +1442,8 @@ hipError_t batch_enqueue_pipe(loam_ctx* x) {
   T(hipEventRecord(x->ev[2], x->st));
   // mapping: frame 1 once the seed (and this call's earlier work on st) is there, frame 2 once the
   // odometry is.  tune.pipe_mp_sets = 2: the steps alternate between two mapping sets on st4 / st2,
-  // so the next step's frame 1 runs beside this step's frame 2 (no side branches then); 1: one set
-  // on st4, frame 2's independent branches on st2
+  // so the next step's frame 1 runs beside this step's frame 2 (no side branch then); 1: one set
+  // on st4, frame 2's stack VoxelGrid on st2
   const bool two = x->tune.pipe_mp_sets == 2;
   const int m = x->pipe_k++ & 1;  // (the mapping sets alternate by step, whatever the SR slots)
   hipStream_t ms = two && m ? x->st2 : x->st4;
@@ -1454,16 +1453,16 @@ hipError_t batch_enqueue_pipe(loam_ctx* x) {
   SideStream side1;  // (no branches: only the event once Last[ls] is read)
   side1.inputs_read = x->mp1_read;
   PT_BEGIN("mp1", ms);
-  mp_batch_frame1(mb, o, ls, fprev, ms, nullptr, &side1);
+  mp_batch_frame1(mb, o, ls, ms, nullptr, &side1);
   PT_END("mp1", ms);
   T(hipEventRecord(x->mp1_done, ms));
   T(hipStreamWaitEvent(ms, x->od_done, 0));
   PT_BEGIN("mp2", ms);
   SideStream side;
   side.st = two ? nullptr : x->st2;
-  side.fork[0] = x->fork; side.join[0] = x->join; side.fork[1] = x->fork2; side.join[1] = x->join2;
+  side.fork = x->fork; side.join = x->join;
   side.inputs_read = x->inputs_read[idx];
-  mp_batch_frame2(mb, o, le, fcur, ms, nullptr, &side);
+  mp_batch_frame2(mb, o, le, ms, nullptr, &side);
   PT_END("mp2", ms);
 #ifdef LOAM_PIPE_TRACE
   ++g_pt.step;

@@ -64,7 +64,7 @@ struct Tuning {
                            // pipeline (the odometry of a step beside the mapping of the previous one;
                            // batch_enqueue_pipe), which supersedes sr_ahead (round 4: 128 problems
                            // 2.75 -> 2.37 ms/step, 1024: 14.56 -> 14.25)
-  int pipe_mp_sets = 2;    // the step pipeline's mapping: 1 one set (st4, side branches on st2), 2 two sets
+  int pipe_mp_sets = 2;    // the step pipeline's mapping: 1 one set (st4, the stack VoxelGrid on st2), 2 two sets
                            // alternating on st4 / st2 (the next frame 1 beside this frame 2; round 4:
                            // 128 problems 2.37 -> 2.20 ms/step, 1024: 14.23 -> 14.03)
   int od_graph = 1;        // loam_chain_sweep replays the odometry's L-M launches as a captured HIP graph

@@ -2037,43 +2037,24 @@ __global__ __launch_bounds__(256) void k_mp_compact_copy(MpBuffers b) {
   }
 }
 
-// k_mp_register workgroups per problem
+// k_mp_register workgroups per instance (streaming and lanes; the batch registers nothing)
 #ifndef LOAM_REG_WG
-#define LOAM_REG_WG 8  // (1024 problems, k_mp_register ms/step with a per-lane end_rot: 64 -> 1.02, 32 -> 0.77, 16 -> 0.61; with end_rot_wave: 16 -> 0.52, 8 -> 0.50, 4 -> 0.51)
+#define LOAM_REG_WG 8
 #endif
 constexpr int kMpRegWg = LOAM_REG_WG;
 __global__ __launch_bounds__(256) void k_mp_register(MpBuffers b, MpInput in) {
   const int p = blockIdx.y;
   const loampose::MapRot r = rot_load(b, p);
   const int n = min(in.nfull[p * in.nfull_stride], b.capS);
-  if (in.end_mode) {  // odometry's TransformToEnd of the raw cloud first (k_od_end's, :875-891)
-    float t[6] = {0, 0, 0, 0, 0, 0};
-    loampose::Imu imu = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (in.end_mode == 2) {
-      const float* st = in.end_state + (size_t)p * kOdStateFloats;
-      for (int k = 0; k < 6; ++k) t[k] = st[k];
-      const float* q = st + kOdImu;
-      imu.pitchStart = q[0]; imu.yawStart = q[1]; imu.rollStart = q[2];
-      imu.pitchLast = q[3]; imu.yawLast = q[4]; imu.rollLast = q[5];
-      imu.shiftX = q[6]; imu.shiftY = q[7]; imu.shiftZ = q[8];
-      imu.veloX = q[9]; imu.veloY = q[10]; imu.veloZ = q[11];
-    }
-    const loampose::EndRot er = loampose::end_rot_wave(t, imu);
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-      const float4 a = loampose::transform_to_end(t, imu, er, in.full[(size_t)p * in.full_stride + i], in.end_mode == 1);
-      b.reg[(size_t)p * b.capS + i] = loampose::point_to_map(r, a);
-    }
-  } else {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
-      b.reg[(size_t)p * b.capS + i] = loampose::point_to_map(r, in.full[(size_t)p * in.full_stride + i]);
-  }
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+    b.reg[(size_t)p * b.capS + i] = loampose::point_to_map(r, in.full[(size_t)p * in.full_stride + i]);
   if (blockIdx.x == 0 && threadIdx.x == 0) b.nreg[p] = n;
 }
 
 }  // namespace
 
 // ---------------------------------------------------------------- host side
-hipError_t mp_alloc(MpBuffers& b, int P, int R, int cap_pts, int map_cap, int max_iter) {
+hipError_t mp_alloc(MpBuffers& b, int P, int R, int cap_pts, int map_cap, int max_iter, bool batch) {
   DevAlloc A;
   b.P = P;
   b.capC = kLessSharpPerRing * R;
@@ -2091,9 +2072,13 @@ hipError_t mp_alloc(MpBuffers& b, int P, int R, int cap_pts, int map_cap, int ma
   A(&b.pool, 2 * Pm * sizeof(float4));
   A(&b.valid, (size_t)P * kMaxValid * sizeof(int));
   A(&b.vpre, (size_t)P * (kMaxValid + 1) * 2 * sizeof(int));
-  A(&b.inC, (size_t)P * b.capC * sizeof(float4));
-  A(&b.inS, (size_t)P * b.capS * sizeof(float4));
-  A(&b.inF, (size_t)P * b.capS * sizeof(float4));
+  // (a batch set reads the odometry's Last buffers in place and registers no cloud: its inC / inS /
+  // inF and reg / nreg stay null)
+  if (!batch) {
+    A(&b.inC, (size_t)P * b.capC * sizeof(float4));
+    A(&b.inS, (size_t)P * b.capS * sizeof(float4));
+    A(&b.inF, (size_t)P * b.capS * sizeof(float4));
+  }
   A(&b.in_n, (size_t)P * 3 * sizeof(int));
   A(&b.in_pose, (size_t)P * 6 * sizeof(float));
   A(&b.stack2, Ps * sizeof(float4));
@@ -2137,14 +2122,14 @@ hipError_t mp_alloc(MpBuffers& b, int P, int R, int cap_pts, int map_cap, int ma
   // the VoxelGrid scratch: sort arrays over the cube inputs or the stacks, a list entry per cube
   // segment; the stack job's big-segment split: 2P parents, points / outputs like the stacks
   if (A.err == hipSuccess) A.err = vg_scratch_alloc(b.vg, std::max(Pm, Ps), (size_t)P * 2 * kMaxValid, 2 * P, Ps);
-  A(&b.reg, (size_t)P * b.capS * sizeof(float4));
+  if (!batch) A(&b.reg, (size_t)P * b.capS * sizeof(float4));
   A(&b.part, (size_t)P * std::max(kMpSmallGrid, kMpFitGridMax) * 28 * sizeof(double));
   A(&b.rot, (size_t)P * 6 * sizeof(double));
   A(&b.done, (size_t)P * sizeof(int));
   A(&b.ls_part, (size_t)2 * kMpSmallGrid * 28 * sizeof(double));
   A(&b.ls_flag, (size_t)kMpSmallGrid * sizeof(unsigned long long));
   A(&b.ls_epoch, sizeof(unsigned long long));
-  A(&b.nreg, (size_t)P * sizeof(int));
+  if (!batch) A(&b.nreg, (size_t)P * sizeof(int));
   if (A.err == hipSuccess) A.err = mp_reset(b, nullptr);
   if (A.err == hipSuccess) A.err = hipMemset(b.ls_flag, 0, (size_t)kMpSmallGrid * sizeof(unsigned long long));
   if (A.err == hipSuccess) A.err = hipMemset(b.ls_epoch, 0, sizeof(unsigned long long));
@@ -2176,13 +2161,14 @@ __global__ void k_mp_reset(MpBuffers b) {
   ist[kMiCenW] = 10; ist[kMiCenH] = 5; ist[kMiCenD] = 10;  // :64-66
 }
 
-hipError_t mp_reset(MpBuffers& b, hipStream_t st) {
+hipError_t mp_reset(MpBuffers& b, hipStream_t st, bool both_tables) {
   mp_wait_update(b, st);
   b.pool_cur = 0;
   hipError_t e = hipMemsetAsync(b.state, 0, (size_t)b.P * kMpStateFloats * sizeof(float), st);
   if (e == hipSuccess) e = hipMemsetAsync(b.done, 0, (size_t)b.P * sizeof(int), st);
   if (e == hipSuccess) e = hipMemsetAsync(b.istate, 0, (size_t)b.P * kMpStateInts * sizeof(int), st);
-  if (e == hipSuccess) e = hipMemsetAsync(b.slots, 0, (size_t)2 * b.P * kCubeNum * 4 * sizeof(int), st);
+  // (pool 0's slot table first: the one the next frame reads)
+  if (e == hipSuccess) e = hipMemsetAsync(b.slots, 0, (size_t)(both_tables ? 2 : 1) * b.P * kCubeNum * 4 * sizeof(int), st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_mp_reset, dim3((b.P + 255) / 256), dim3(256), 0, st, b);
   return hipGetLastError();
@@ -2270,9 +2256,13 @@ void mp_lm_loop(MpBuffers& b, int P, hipStream_t st, Prof* prof, bool map_empty,
 }
 }  // namespace
 
-void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof, bool map_empty,
-              const std::function<void()>& before_register, int stack_max, const SideStream* side,
-              hipStream_t defer) {
+// ---- the stages of a mapping frame; every caller composes the ones whose results it hands out ----
+namespace {
+// front: the pose and the valid cubes, the stacks and their VoxelGrid, FromMap and its hashes.
+// from_map = false: the store was just reset (batch frame 1), FromMap is empty by construction and
+// neither gathered nor hashed (k_mp_prepare has set nfrom and the valid count to 0; no L-M runs)
+void mp_front(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof, int stack_max, const SideStream* side,
+              bool from_map) {
   const int P = b.P;
   auto mark = [&](const char* n) { if (prof) prof->mark(n); };
   mp_wait_update(b, st);  // (the previous frame's map update, when it was deferred)
@@ -2283,39 +2273,27 @@ void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof, bool 
   if (side && side->inputs_read) b.note(hipEventRecord(side->inputs_read, st));  // (in.corner / in.surf read)
   // the stack VoxelGrid: with a side stream it runs there, beside the FromMap gather and the map
   // hash builds (which read only the store)
-  const bool fork = side && side->st && !prof && !map_empty;
+  const bool fork = side && side->st && !prof && from_map;
   if (fork) {
-    b.note(hipEventRecord(side->fork[0], st));
-    b.note(hipStreamWaitEvent(side->st, side->fork[0], 0));
+    b.note(hipEventRecord(side->fork, st));
+    b.note(hipStreamWaitEvent(side->st, side->fork, 0));
   }
   mp_stack_vg(b, P, fork ? side->st : st, stack_max);
-  if (fork) b.note(hipEventRecord(side->join[0], side->st));
+  if (fork) b.note(hipEventRecord(side->join, side->st));
   mark("vg_stack");
+  if (!from_map) return;
   hipLaunchKernelGGL(k_mp_gather, dim3(32, P), dim3(256), 0, st, b);
   mark("k_mp_gather");
   mp_hash_from(b, P, st);
   mark("k_hash_build_map");
-  if (fork) b.note(hipStreamWaitEvent(st, side->join[0], 0));
-  mp_lm_loop(b, P, st, prof, map_empty, /*persist=*/true);
-  // the registration reads only the final pose and the full cloud: beside the insertion with a
-  // side stream (the batch: no before_register hook)
-  const bool reg_side = fork && !before_register && !defer;
-  // defer: the map update on the other stream, forked here; the registration stays on st
-  hipStream_t us = st;
-  if (defer) {
-    if (!b.upd_fork) b.note(hipEventCreateWithFlags(&b.upd_fork, hipEventDisableTiming));
-    if (!b.upd_done) b.note(hipEventCreateWithFlags(&b.upd_done, hipEventDisableTiming));
-    b.note(hipEventRecord(b.upd_fork, st));
-    b.note(hipStreamWaitEvent(defer, b.upd_fork, 0));
-    us = defer;
-  }
-  if (reg_side) {
-    b.note(hipEventRecord(side->fork[1], st));
-    b.note(hipStreamWaitEvent(side->st, side->fork[1], 0));
-    hipLaunchKernelGGL(k_mp_register, dim3(kMpRegWg, P), dim3(256), 0, side->st, b, in);
-    b.note(hipEventRecord(side->join[1], side->st));
-  }
-  // insertion + per-valid-cube downsampling into the other pool
+  if (fork) b.note(hipStreamWaitEvent(st, side->join, 0));
+}
+
+// the map update on us: insertion + per-valid-cube downsampling into the other pool, which becomes
+// the current one (k_mp_lm_end zeroed the cascade's list counters)
+void mp_update(MpBuffers& b, hipStream_t us, Prof* prof) {
+  const int P = b.P;
+  auto mark = [&](const char* n) { if (prof) prof->mark(n); };
   // a few instances: 1024 threads per instance (the per-instance serial parts are the cost)
   // 1024 threads per instance also for batches (k_mp_insert 0.40 -> 0.25 ms/step at batch 1024 against 256)
   hipLaunchKernelGGL(k_mp_insert<1024>, dim3(P), dim3(1024), 0, us, b, (int*)b.vg.keys, (int*)b.vg.vals);
@@ -2333,18 +2311,30 @@ void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof, bool 
   hipLaunchKernelGGL(k_mp_compact_table<1024>, dim3(P), dim3(1024), 0, us, b);
   hipLaunchKernelGGL(k_mp_compact_copy, dim3(64, P), dim3(256), 0, us, b);
   mark("k_mp_compact");
+  b.pool_cur = 1 - b.pool_cur;
+}
+}  // namespace
+
+void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof,
+              const std::function<void()>& before_register, int stack_max, hipStream_t defer) {
+  mp_front(b, in, st, prof, stack_max, nullptr, /*from_map=*/true);
+  mp_lm_loop(b, b.P, st, prof, false, /*persist=*/true);
+  // defer: the map update on the other stream, forked here; the registration stays on st
   if (defer) {
-    b.note(hipEventRecord(b.upd_done, us));
+    if (!b.upd_fork) b.note(hipEventCreateWithFlags(&b.upd_fork, hipEventDisableTiming));
+    if (!b.upd_done) b.note(hipEventCreateWithFlags(&b.upd_done, hipEventDisableTiming));
+    b.note(hipEventRecord(b.upd_fork, st));
+    b.note(hipStreamWaitEvent(defer, b.upd_fork, 0));
+  }
+  mp_update(b, defer ? defer : st, prof);
+  if (defer) {
+    b.note(hipEventRecord(b.upd_done, defer));
     b.upd_pending = true;
   }
   if (before_register) before_register();
-  if (reg_side) {
-    b.note(hipStreamWaitEvent(st, side->join[1], 0));
-  } else {
-    hipLaunchKernelGGL(k_mp_register, dim3(kMpRegWg, P), dim3(256), 0, st, b, in);
-    mark("k_mp_register");
-  }
-  b.pool_cur = 1 - b.pool_cur;
+  // (reads the final pose and the full cloud only, not the store)
+  hipLaunchKernelGGL(k_mp_register, dim3(kMpRegWg, b.P), dim3(256), 0, st, b, in);
+  if (prof) prof->mark("k_mp_register");
 }
 
 template <typename Hook>
@@ -2447,10 +2437,10 @@ int mp_stream_run(MpBuffers& b, hipStream_t st, const MpInput& in, const int* n,
                   bool* updated, Hook hook, hipStream_t defer) {
   const hipEvent_t e0 = io.e0, e1 = io.e1;
   hipError_t le = hipEventRecord(e0, st);
-  mp_frame(b, in, st, nullptr, false, [&]() {
+  mp_frame(b, in, st, nullptr, [&]() {
     if (le != hipSuccess) return;
     le = hook();
-  }, std::max(n[0], n[1]), nullptr, defer);
+  }, std::max(n[0], n[1]), defer);
   if (le == hipSuccess) le = hipEventRecord(e1, st);
   // a deferred update's valid-point count (stats) into the mapped host block after it, one slot
   // per frame parity: this call reads the previous frame's (complete: this frame's kernels on st
@@ -3246,41 +3236,47 @@ hipError_t mp_localize_solve(MpLoc& L, const MpBuffers& s, const MpInput& in, in
   return hipMemcpyAsync(L.res_h(), L.res, (size_t)n * kLocResWords * sizeof(int), hipMemcpyDeviceToHost, st);
 }
 
+// A batch problem ends at cur's solved pose: no call returns its map or its registered clouds, so
+// the batch frames build neither the registered clouds nor the map with cur inserted.
+namespace {
+// the corner / surf clouds of the odometry's Last[buf] (the batch frames read no full cloud)
+MpInput batch_input(const OdBuffers& od, int buf) {
+  MpInput in;
+  in.corner = od.lastC + (size_t)buf * od.P * od.capC;
+  in.surf = od.lastS + (size_t)buf * od.P * od.capS;
+  in.full = nullptr;
+  in.corner_stride = od.capC; in.surf_stride = od.capS; in.full_stride = 0;
+  in.ncorner = od.nlast + buf * 2; in.nsurf = od.nlast + buf * 2 + 1; in.nfull = nullptr;
+  in.ncorner_stride = 2 * kOdBufs; in.nsurf_stride = 2 * kOdBufs; in.nfull_stride = 0;
+  return in;
+}
+}  // namespace
+
 // frame 1 of the batch problem: reset, then prev (the seed's Last[buf]) into the empty store at
 // the zero pose.  Reads only what the odometry seeding wrote, so it may run beside od_solve.
-void mp_batch_frame1(MpBuffers& b, const OdBuffers& od, int buf, const FeatView& fprev, hipStream_t st, Prof* prof,
-                     const SideStream* side) {
-  b.note(mp_reset(b, st));
+// The store is empty by construction: no FromMap gather or hash build, no L-M launches
+// (k_mp_lm_begin / k_mp_lm_end still set the state frame 2 reads and zero the cascade's counters),
+// then the map update, which leaves prev's map in pool 1 for frame 2.
+void mp_batch_frame1(MpBuffers& b, const OdBuffers& od, int buf, hipStream_t st, Prof* prof, const SideStream* side) {
+  // (only pool 0's slot table, which this frame reads, must be empty: k_mp_compact_table writes
+  // every entry of pool 1's)
+  b.note(mp_reset(b, st, /*both_tables=*/false));
   if (prof) prof->mark("mp_reset");
-  MpInput in;
-  in.corner = od.lastC + (size_t)buf * od.P * od.capC;
-  in.surf = od.lastS + (size_t)buf * od.P * od.capS;
-  in.corner_stride = od.capC; in.surf_stride = od.capS;
-  in.ncorner = od.nlast + buf * 2; in.nsurf = od.nlast + buf * 2 + 1;
-  in.ncorner_stride = 2 * kOdBufs; in.nsurf_stride = 2 * kOdBufs;
-  // the full cloud: prev's raw one, TransformToEnd with the zero transform in k_mp_register
-  in.full = fprev.full; in.full_stride = fprev.full_stride;
-  in.nfull = fprev.nfull_p; in.nfull_stride = fprev.nfull_stride;
-  in.end_mode = 1;
+  MpInput in = batch_input(od, buf);
   in.pose = nullptr; in.pose_stride = 0;
-  mp_frame(b, in, st, prof, /*map_empty=*/true, nullptr, -1, side);
+  mp_front(b, in, st, prof, -1, side, /*from_map=*/false);
+  mp_lm_loop(b, b.P, st, prof, /*map_empty=*/true, /*persist=*/true);
+  mp_update(b, st, prof);
 }
 
-// frame 2: cur (TransformToEnd's Last[buf]) with the odometry transformSum
-void mp_batch_frame2(MpBuffers& b, const OdBuffers& od, int buf, const FeatView& fcur, hipStream_t st, Prof* prof,
-                     const SideStream* side) {
-  MpInput in;
-  in.corner = od.lastC + (size_t)buf * od.P * od.capC;
-  in.surf = od.lastS + (size_t)buf * od.P * od.capS;
-  in.corner_stride = od.capC; in.surf_stride = od.capS;
-  in.ncorner = od.nlast + buf * 2; in.nsurf = od.nlast + buf * 2 + 1;
-  in.ncorner_stride = 2 * kOdBufs; in.nsurf_stride = 2 * kOdBufs;
-  // the full cloud: cur's raw one, TransformToEnd with the solved transform in k_mp_register
-  in.full = fcur.full; in.full_stride = fcur.full_stride;
-  in.nfull = fcur.nfull_p; in.nfull_stride = fcur.nfull_stride;
-  in.end_state = od.state; in.end_mode = 2;
+// frame 2: cur (TransformToEnd's Last[buf]) with the odometry transformSum, up to its solved pose
+// (k_mp_lm_end); the store stays prev's map (pool 1) until the next step's reset
+void mp_batch_frame2(MpBuffers& b, const OdBuffers& od, int buf, hipStream_t st, Prof* prof, const SideStream* side) {
+  MpInput in = batch_input(od, buf);
   in.pose = od.state + kOdSum; in.pose_stride = kOdStateFloats;
-  mp_frame(b, in, st, prof, false, nullptr, -1, side);
+  mp_front(b, in, st, prof, -1, side, /*from_map=*/true);
+  mp_lm_loop(b, b.P, st, prof, false, /*persist=*/true);
+  if (prof) prof->mark("k_mp_lm_end");  // (no later mark of the step would take it)
 }
 
 // per-instance mapping L-M iteration counts of the last frame (loam_batch_iterations)

@@ -42,11 +42,7 @@ struct MpInput {
   int ncorner_stride, nsurf_stride, nfull_stride;
   const float* pose;   // transformSum of the odometry message (nullptr = zero pose)
   int pose_stride;
-  // the batch path: `full` is the raw ring-sorted cloud, and k_mp_register applies odometry's
-  // TransformToEnd itself (end_mode 1: zero transform, 2: the transform in end_state, OdBuffers
-  // state layout), so the full cloud is neither written to nor read back from fullEnd
-  const float* end_state = nullptr;
-  int end_mode = 0;
+  // (the batch frames register nothing: their full / nfull are null)
 };
 
 struct MpBuffers {
@@ -58,7 +54,7 @@ struct MpBuffers {
   float4* pool = nullptr;     // [2][P][map_cap]
   int* valid = nullptr;       // [P][kMaxValid]
   int* vpre = nullptr;        // [P][kMaxValid + 1][2] FromMap prefix (corner, surf)
-  // streaming inputs
+  // streaming inputs (inC / inS / inF: null in a batch set, mp_alloc)
   float4 *inC = nullptr, *inS = nullptr, *inF = nullptr;
   int* in_n = nullptr;        // [P][3]
   float* in_pose = nullptr;   // [P][6]
@@ -98,7 +94,7 @@ struct MpBuffers {
   int* vg_mlist = nullptr;                 // [P][2][kMaxValid] cube segments k_vg_merge may take
   int* vseg_nold = nullptr;                // [P][2][kMaxValid] leading points from the cube's last DS
   int* vseg_skip = nullptr;                // [P][2][kMaxValid] 1: k_vg_merge wrote the segment
-  float4* reg = nullptr;      // [P][capS] registered full cloud
+  float4* reg = nullptr;      // [P][capS] registered full cloud (null in a batch set, as nreg)
   double* part = nullptr;     // [P][kMpSmallGrid][28] k_mp_lm_small's per-workgroup JᵀJ | Jᵀb | rows
   int* done = nullptr;        // [P] its workgroups finished (the last one runs the step)
   // the persistent one-instance L-M (k_mp_lm_stream): per workgroup and iteration parity its partial
@@ -114,7 +110,7 @@ struct MpBuffers {
   // and a reset wait for it first (upd_pending)
   hipEvent_t upd_fork = nullptr, upd_done = nullptr;
   bool upd_pending = false;
-  Tuning tune;                // host-side launch choices (mp_frame)
+  Tuning tune;                // host-side launch choices (the frames' stages)
   hipError_t sticky = hipSuccess;  // first failed HIP call of the launch sequences
   void note(hipError_t e) {
     if (sticky == hipSuccess) sticky = e;
@@ -128,27 +124,31 @@ struct MpBuffers {
 };
 
 inline int mp_batch_map_capacity(int cap) { return 2 * cap; }
-hipError_t mp_alloc(MpBuffers& b, int P, int R, int cap_pts, int map_cap, int max_iter);  // on failure: freed, b empty
+// on failure: freed, b empty.  batch: a set of the batch frames, which read their clouds in place and
+// register nothing: inC / inS / inF and reg / nreg are not allocated
+hipError_t mp_alloc(MpBuffers& b, int P, int R, int cap_pts, int map_cap, int max_iter, bool batch = false);
 void mp_free(MpBuffers& b);
-hipError_t mp_reset(MpBuffers& b, hipStream_t st);
-// map_empty: the store was just reset (no L-M can run: its launches are skipped)
+// both_tables = false: only pool 0's slot table is cleared (the one the next frame reads; for a
+// caller whose next map update rewrites pool 1's whole table before anything reads it)
+hipError_t mp_reset(MpBuffers& b, hipStream_t st, bool both_tables = true);
+// One whole mapping frame (streaming, lanes): front (prepare, stacks + their VoxelGrid, FromMap
+// gather + hashes), the L-M loop, the map update, the registration of the full cloud.
 // before_register: called once every kernel before k_mp_register is enqueued (the streaming path
 // stages the full cloud there); stack_max: the largest stack segment (corner or surf input count)
 // when the host knows it, else -1
-// side: an idle second stream (and two fork / join event pairs) for the frame's independent
-// branches: the stack VoxelGrid beside the FromMap gather + hash builds, and the registration of the
-// full cloud beside the map insertion / per-cube VoxelGrid
-struct SideStream {
-  hipStream_t st = nullptr;
-  hipEvent_t fork[2] = {nullptr, nullptr}, join[2] = {nullptr, nullptr};
-  hipEvent_t inputs_read = nullptr;  // optional: recorded once the frame has read its input clouds
-};
 // defer: a second stream for the map update (streaming frames): the update runs there after the
 // L-M, beside the registration and the caller's downloads; the frame's pose and registered cloud do
 // not wait for it (b.upd_pending until the next frame's first kernel has waited for it)
-void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof = nullptr, bool map_empty = false,
+void mp_frame(MpBuffers& b, const MpInput& in, hipStream_t st, Prof* prof = nullptr,
               const std::function<void()>& before_register = nullptr, int stack_max = -1,
-              const SideStream* side = nullptr, hipStream_t defer = nullptr);
+              hipStream_t defer = nullptr);
+// the batch frames' side stream: an idle second stream and a fork / join event pair for the stack
+// VoxelGrid beside the FromMap gather + hash builds (st = nullptr: no branch)
+struct SideStream {
+  hipStream_t st = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+  hipEvent_t inputs_read = nullptr;  // optional: recorded once the frame has read its input clouds
+};
 // the pending deferred map update (if any) before later work on st
 void mp_wait_update(MpBuffers& b, hipStream_t st);
 // imu_rp: the IMU (roll, pitch) transformUpdate blends in (nullptr = no IMU); *updated = whether
@@ -166,13 +166,16 @@ int mp_stream_frame_dev(MpBuffers& b, hipStream_t st, const loam_pose6& odom_sum
 // /laser_cloud_surround of the last streaming frame (instance 0): its 5x5x5 cube neighbourhood
 // concatenated and VoxelGrid 0.2 (src/laserMapping.cpp:1038-1058)
 int mp_stream_surround(MpBuffers& b, hipStream_t st, loam_cloud_out* out, std::string& err);
+// The batch problem's two frames.  It ends at cur's solved pose: frame 1 (reset, prev into the empty
+// store: front without FromMap, no L-M launches, the map update) and frame 2 (cur: front and L-M
+// loop, nothing after k_mp_lm_end).  Neither registers a cloud, and the map with cur inserted is
+// not built: no batch call returns them.
 // buf: the odometry's Last buffer the frame reads (frame 1: the seed's, frame 2: TransformToEnd's)
-// fprev / fcur: the scan registration outputs whose full clouds the frames register
-// side: only its inputs_read event is used (the frame runs on st alone)
-void mp_batch_frame1(MpBuffers& b, const OdBuffers& od, int buf, const FeatView& fprev, hipStream_t st,
-                     Prof* prof = nullptr, const SideStream* side = nullptr);
-void mp_batch_frame2(MpBuffers& b, const OdBuffers& od, int buf, const FeatView& fcur, hipStream_t st,
-                     Prof* prof = nullptr, const SideStream* side = nullptr);
+// side: frame 1 uses only its inputs_read event (it runs on st alone)
+void mp_batch_frame1(MpBuffers& b, const OdBuffers& od, int buf, hipStream_t st, Prof* prof = nullptr,
+                     const SideStream* side = nullptr);
+void mp_batch_frame2(MpBuffers& b, const OdBuffers& od, int buf, hipStream_t st, Prof* prof = nullptr,
+                     const SideStream* side = nullptr);
 int mp_batch_download(MpBuffers& b, hipStream_t st, loam_pose6* aft, loam_stats* stats, std::string& err);
 hipError_t mp_batch_iters(MpBuffers& b, hipStream_t st, int32_t* iters);
 
