@@ -498,6 +498,30 @@ int loam_lanes_map_export(loam_ctx *ctx, uint32_t lane, loam_map *out);
  * LOAM_E_INVAL, and nothing is changed: null context or wait_steps, lanes not open, lane >=
  * n_lanes, a step in flight.  LOAM_E_NOMEM when the first call's allocation fails. */
 int loam_lanes_restart(loam_ctx *ctx, uint32_t lane, uint32_t *wait_steps);
+/* One map into n lanes of the open lanes, between two steps: loam_map_import for lanes.  lane[i],
+ * i < n, are distinct lane indices.  Every listed lane's cube map, grid centre, Bef / Aft and
+ * surround_phase are replaced as loam_map_import replaces a context's: centre = in->center, Bef =
+ * in->bef, surround_phase = in->surround_phase, Aft = aft[i] (in->aft for every lane when aft is
+ * NULL); points in any order, each to the cube the reference's insertion would choose, input order
+ * kept inside a cube, nothing downsampled, two empty clouds = a map reset that keeps the poses.
+ * dropped as in loam_map_import (the same for every lane: one map, one centre).
+ * A listed lane behaves from here on, bit for bit, as a context would that received
+ * loam_map_import(in with aft = aft[i]) at the same point of its call sequence; its odometry, scan
+ * registration, IMU queues and sticky state are not touched, and no unlisted lane changes by a bit.
+ * The map is uploaded and sorted once and copied on the device into every listed lane.
+ * May be called whenever lanes are open and no step is in flight (before the first push and inside
+ * system_delay too), except for a lane between loam_lanes_restart and the pull of its init step:
+ * import after the lane's init step (that frame neither reads nor writes the map, and the restart
+ * clears the lane's store up to and including that step).  A restart clears an imported map.
+ * LOAM_E_INVAL, and nothing changes in any lane and dropped is not written: a null ctx / lane / in,
+ * lanes not open, a step in flight, n == 0 or n > n_lanes, a lane index >= n_lanes, a lane listed
+ * twice, a failed lane (restart it first), a lane waiting for its init step, and loam_map_import's
+ * own argument errors.  LOAM_E_CAPACITY, and nothing changes in any lane: the kept points exceed
+ * lane_map_capacity (dropped is filled).  LOAM_E_NOMEM when the first call's allocation (two blocks
+ * of 9 + 7 n_lanes words) fails. */
+int loam_lanes_map_import(loam_ctx *ctx, uint32_t n, const uint32_t *lane /* [n] */,
+                          const loam_map *in, const loam_pose6 *aft /* [n] or NULL */,
+                          uint64_t dropped[2]);
 /* Frees the lanes' working set (waits for a step in flight).  LOAM_E_INVAL when not open. */
 int loam_lanes_close(loam_ctx *ctx);
 

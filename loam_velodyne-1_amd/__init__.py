@@ -186,7 +186,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_map_localize", "loam_map_score", "loam_get_stats",
            "loam_lanes_open", "loam_lanes_push", "loam_lanes_pull", "loam_lanes_registered", "loam_lanes_map_export",
            "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
-           "loam_lanes_restart",
+           "loam_lanes_restart", "loam_lanes_map_import",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -245,6 +245,8 @@ def lib():
         L.loam_lanes_push_stamped.argtypes = [PP, P(ctypes.c_double), P(CloudIn)]
         L.loam_lanes_imu_trans.argtypes = [PP, P(ctypes.c_float)]
         L.loam_lanes_restart.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32)]
+        L.loam_lanes_map_import.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), P(Map), P(Pose6),
+                                            P(ctypes.c_uint64)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -514,11 +516,9 @@ class Engine:
                 "center": np.array(m.center[:], np.int32), "surround_phase": int(m.surround_phase),
                 "aft": m.aft.arr(), "bef": m.bef.arr()}
 
-    def map_import(self, corner, surf, center=(10, 5, 10), surround_phase=4, aft=None, bef=None):
-        """replaces the context's map and mapping pose state (loam_map_import): corner / surf [N, 4]
-        map-frame points in any order; returns the (corner, surf) counts of the points left out
-        (outside the grid about `center`, or non-finite).  Resume: pass what map_export gave.
-        Localize in a prior map with a fresh odometry: bef = None (zeros), aft = the pose guess."""
+    @staticmethod
+    def _map_in(corner, surf, center, surround_phase, aft, bef):
+        """a loam_map over the caller's arrays (and the arrays, to be kept alive over the call)"""
         m = Map()
         keep = []
         for c, a in ((m.corner, corner), (m.surf, surf)):
@@ -529,6 +529,14 @@ class Engine:
         m.surround_phase = int(surround_phase)
         m.aft = Pose6.of(np.zeros(6) if aft is None else aft)
         m.bef = Pose6.of(np.zeros(6) if bef is None else bef)
+        return m, keep
+
+    def map_import(self, corner, surf, center=(10, 5, 10), surround_phase=4, aft=None, bef=None):
+        """replaces the context's map and mapping pose state (loam_map_import): corner / surf [N, 4]
+        map-frame points in any order; returns the (corner, surf) counts of the points left out
+        (outside the grid about `center`, or non-finite).  Resume: pass what map_export gave.
+        Localize in a prior map with a fresh odometry: bef = None (zeros), aft = the pose guess."""
+        m, keep = self._map_in(corner, surf, center, surround_phase, aft, bef)
         dropped = (ctypes.c_uint64 * 2)(0, 0)
         _check(lib().loam_map_import(self.h, ctypes.byref(m), dropped))
         return int(dropped[0]), int(dropped[1])
@@ -609,6 +617,27 @@ class Engine:
         """one lane's cube map and mapping pose state (loam_lanes_map_export): the dict map_export
         returns, so save_map takes it"""
         return self._map_export(lambda m: lib().loam_lanes_map_export(self.h, int(lane), ctypes.byref(m)))
+
+    def lanes_map_import(self, lanes, corner, surf, center=(10, 5, 10), surround_phase=4, aft=None, bef=None,
+                         corner_offset=None, surf_offset=None):
+        """one map into the listed lanes between two steps (loam_lanes_map_import): map_import's
+        arguments, uploaded and sorted once and copied on the device into every lane of `lanes`
+        (distinct indices).  aft: one pose for every lane, or an [n, 6] array of one pose guess per
+        listed lane; None = zeros.  Returns the (corner, surf) counts of the points left out.
+        load_map's dict can be splatted in: lanes_map_import(lanes, **load_map(path)); its cube
+        offsets are not needed (the points are binned again)."""
+        lanes = [int(l) for l in np.atleast_1d(lanes)]
+        n = len(lanes)
+        a = np.zeros(6, np.float32) if aft is None else np.ascontiguousarray(aft, np.float32)
+        per_lane = a.ndim == 2
+        if per_lane and a.shape != (n, 6):
+            raise ValueError("aft: one pose, or one pose per listed lane ([n, 6])")
+        m, keep = self._map_in(corner, surf, center, surround_phase, None if per_lane else a, bef)
+        idx = (ctypes.c_uint32 * max(n, 1))(*lanes)
+        poses = a.ctypes.data_as(ctypes.POINTER(Pose6)) if per_lane else None
+        dropped = (ctypes.c_uint64 * 2)(0, 0)
+        _check(lib().loam_lanes_map_import(self.h, n, idx, ctypes.byref(m), poses, dropped))
+        return int(dropped[0]), int(dropped[1])
 
     def lanes_close(self):
         _check(lib().loam_lanes_close(self.h))

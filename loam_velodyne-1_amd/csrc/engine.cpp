@@ -2019,25 +2019,32 @@ extern "C" int loam_map_export(loam_ctx* x, loam_map* out) {
   return map_export_of(x, x->mp1, 0, x->map_frame_count, out);
 }
 
-extern "C" int loam_map_import(loam_ctx* x, const loam_map* in, uint64_t* dropped) {
-  if (!x || !in) return fail(LOAM_E_INVAL, "null argument");
+namespace {
+// what loam_map_import and loam_lanes_map_import (who: the call's name) refuse of `in`
+int map_import_args(const loam_map* in, const std::string& who) {
   const loam_map_cloud* cl[2] = {&in->corner, &in->surf};
   for (int k = 0; k < 2; ++k)
-    if (cl[k]->count > 0 && !cl[k]->pts) return fail(LOAM_E_INVAL, "loam_map_import: a cloud's pts is null");
+    if (cl[k]->count > 0 && !cl[k]->pts) return fail(LOAM_E_INVAL, who + ": a cloud's pts is null");
   if (in->surround_phase < 0 || in->surround_phase > 4)
-    return fail(LOAM_E_INVAL, "loam_map_import: surround_phase must be 0..4");
+    return fail(LOAM_E_INVAL, who + ": surround_phase must be 0..4");
   for (int k = 0; k < 3; ++k)
     if (in->center[k] > (1 << 24) || in->center[k] < -(1 << 24))
-      return fail(LOAM_E_INVAL, "loam_map_import: a center component is beyond 2^24");
+      return fail(LOAM_E_INVAL, who + ": a center component is beyond 2^24");
   const uint64_t kMaxIn = ((uint64_t)1 << 31) - ((uint64_t)1 << 23);
   if (cl[0]->count > kMaxIn || cl[1]->count > kMaxIn || cl[0]->count + cl[1]->count > kMaxIn)
-    return fail(LOAM_E_INVAL, "loam_map_import: more than 2^31 - 2^23 points");
-  int rc = map_drain(x);
-  if (rc) return rc;
-  MpBuffers& b = x->mp1;
+    return fail(LOAM_E_INVAL, who + ": more than 2^31 - 2^23 points");
+  return LOAM_OK;
+}
+
+// The two clouds of `in` uploaded and binned into the scratch of the store b, whose queued work has
+// been drained: the kept points in input order in b.vin with their keys and per-key counts
+// (mp_map_bin_chunk); nothing of the store changes.  Begins the profile interval, fills dropped
+// (when given) and *kept (which may exceed b.map_cap: the caller's LOAM_E_CAPACITY).
+int map_import_bin(loam_ctx* x, MpBuffers& b, const loam_map* in, const std::string& who, uint64_t* dropped, int* kept) {
+  const loam_map_cloud* cl[2] = {&in->corner, &in->surf};
   HIP_TRY(mp_map_ensure(x->mio));
   if (cl[0]->count + cl[1]->count > 0) {
-    rc = ensure_pack_stage(x, "map import");
+    const int rc = ensure_pack_stage(x, "map import");
     if (rc) return rc;
   }
   static_assert(kMapChunkPts <= (int)kPackStagePts, "an import chunk fits one staging buffer");
@@ -2065,14 +2072,31 @@ extern "C" int loam_map_import(loam_ctx* x, const loam_map* in, uint64_t* droppe
   if (he == hipSuccess) he = hipStreamSynchronize(st);
   if (he != hipSuccess) {
     (void)hipStreamSynchronize(st);
-    return fail(LOAM_E_HIP, std::string("loam_map_import: ") + hipGetErrorString(he));
+    return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
   }
   const int* acc = x->mio.tab_h + kMapTabAcc;
   if (dropped) {
     dropped[0] = (uint64_t)acc[1];
     dropped[1] = (uint64_t)acc[2];
   }
-  if (acc[0] > b.map_cap) {
+  *kept = acc[0];
+  return LOAM_OK;
+}
+}  // namespace
+
+extern "C" int loam_map_import(loam_ctx* x, const loam_map* in, uint64_t* dropped) {
+  if (!x || !in) return fail(LOAM_E_INVAL, "null argument");
+  int rc = map_import_args(in, "loam_map_import");
+  if (rc) return rc;
+  rc = map_drain(x);
+  if (rc) return rc;
+  MpBuffers& b = x->mp1;
+  hipStream_t st = x->st;
+  const int cen[3] = {in->center[0], in->center[1], in->center[2]};
+  int kept = 0;
+  rc = map_import_bin(x, b, in, "loam_map_import", dropped, &kept);
+  if (rc) return rc;
+  if (kept > b.map_cap) {
     x->prof.collect();
     return fail(LOAM_E_CAPACITY, "loam_map_import: the points inside the grid exceed map_capacity");
   }
@@ -2081,7 +2105,7 @@ extern "C" int loam_map_import(loam_ctx* x, const loam_map* in, uint64_t* droppe
   float pose12[12];
   std::memcpy(pose12, &in->aft, sizeof(loam_pose6));
   std::memcpy(pose12 + 6, &in->bef, sizeof(loam_pose6));
-  he = mp_map_install(b, x->mio, acc[0], cen, pose12, st, &x->prof);
+  hipError_t he = mp_map_install(b, x->mio, kept, cen, pose12, st, &x->prof);
   if (he == hipSuccess) he = hipStreamSynchronize(st);
   if (he != hipSuccess) return fail(LOAM_E_HIP, std::string("loam_map_import: ") + hipGetErrorString(he));
   x->prof.collect();
@@ -2588,6 +2612,13 @@ extern "C" int loam_lanes_restart(loam_ctx* x, uint32_t lane, uint32_t* wait_ste
     // before the shared init frame nothing of the lane is on the device yet: it takes that frame
     // with the others, after what is left of system_delay (Q1: one step at least)
     *wait_steps = L.sr_inited ? 0u : (uint32_t)std::max(1, (int)x->cfg.system_delay - L.sr_init_count);
+    if (L.mi_h) {  // ... but for a map a loam_lanes_map_import may have put there: cleared here and now
+      HIP_TRY(hipSetDevice(x->device));
+      L.mi_h[kMiList] = (int)lane;
+      HIP_TRY(hipMemcpyAsync(L.mi_d + kMiList, L.mi_h + kMiList, sizeof(int), hipMemcpyHostToDevice, x->st));
+      HIP_TRY(lanes_restart_clear(L, L.mi_d + kMiList, 1, kClearMp, x->st));
+      HIP_TRY(hipStreamSynchronize(x->st));
+    }
   }
   f.phase = 4;  // mapFrameCount = mapFrameNum - 1 (src/laserMapping.cpp:405)
   L.fail[lane] = LOAM_OK;
@@ -2715,6 +2746,74 @@ extern "C" int loam_lanes_map_export(loam_ctx* x, uint32_t lane, loam_map* out) 
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipStreamSynchronize(x->st));
   return map_export_of(x, L.mp, (int)lane, L.life[lane].phase, out);
+}
+
+// One map into n lanes between two steps (loam.h).  The stream is idle (the pull
+// drained it), so the import's scratch (vin, the sort arrays, app_cnt, the idle pool) is free; the
+// map is binned and sorted once into the idle pool's first segment, and one launch copies it into
+// the listed lanes' current pool segments and slot tables.  pool_cur does not move.
+extern "C" int loam_lanes_map_import(loam_ctx* x, uint32_t n, const uint32_t* lane, const loam_map* in,
+                                     const loam_pose6* aft, uint64_t* dropped) {
+  if (!x || !lane || !in) return fail(LOAM_E_INVAL, "null argument");
+  const std::string who = "loam_lanes_map_import";
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
+  if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
+  if (n == 0 || n > (uint32_t)L.S) return fail(LOAM_E_INVAL, who + ": n must be in [1, n_lanes]");
+  std::vector<char> seen;
+  uint32_t bad = 0;
+  const int why = lanes_list_check(lane, n, L.S, L.fail.data(), L.life.data(), seen, &bad);
+  if (why != kLaneListOk) {
+    const std::string at = who + ": lane[" + std::to_string(bad) + "]" +
+                           (why == kLaneListRange ? "" : " = " + std::to_string(lane[bad]));
+    if (why == kLaneListRange) return fail(LOAM_E_INVAL, at + " is out of range");
+    if (why == kLaneListTwice) return fail(LOAM_E_INVAL, at + " is listed twice");
+    if (why == kLaneListFailed) return fail(LOAM_E_INVAL, at + " has failed (loam_lanes_restart first)");
+    return fail(LOAM_E_INVAL, at + " was restarted and waits for its init step: import after the lane's init step");
+  }
+  int rc = map_import_args(in, who);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipStreamSynchronize(x->st));
+  if (!L.mi_h) {
+    const hipError_t ae = lanes_map_import_alloc(L);
+    if (ae != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(LOAM_E_NOMEM, who + ": allocation failed: " + hipGetErrorString(ae));
+    }
+  }
+  MpBuffers& b = L.mp;
+  hipStream_t st = x->st;
+  int kept = 0;
+  rc = map_import_bin(x, b, in, who, dropped, &kept);
+  if (rc) return rc;
+  if (kept > b.map_cap) {
+    x->prof.collect();
+    return fail(LOAM_E_CAPACITY, who + ": the points inside the grid exceed lane_map_capacity");
+  }
+  // everything so far wrote scratch only, and so do the sort and the table; the lanes change in the
+  // one launch behind them
+  for (int k = 0; k < 3; ++k) L.mi_h[kMiCen + k] = in->center[k];
+  std::memcpy(L.mi_h + kMiBef, &in->bef, sizeof(loam_pose6));
+  for (uint32_t i = 0; i < n; ++i) {
+    L.mi_h[kMiList + i] = (int)lane[i];
+    std::memcpy(L.mi_h + kMiList + n + 6 * (size_t)i, aft ? &aft[i] : &in->aft, sizeof(loam_pose6));
+  }
+  float4* sorted = mp_map_idle_pool(b);
+  hipError_t he = hipMemcpyAsync(L.mi_d, L.mi_h, ((size_t)kMiList + 7 * (size_t)n) * sizeof(int), hipMemcpyHostToDevice, st);
+  x->prof.mark("lanes_map_import_h2d");
+  if (he == hipSuccess) he = mp_map_sort(b, kept, sorted, st, &x->prof);
+  if (he == hipSuccess) he = mp_map_slots(b, x->mio, st, &x->prof);
+  if (he == hipSuccess) he = lanes_map_install(L, sorted, kept, x->mio.tab + kMapTabSlots, (int)n, st);
+  x->prof.mark("k_lanes_map_install");
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
+  }
+  x->prof.collect();
+  for (uint32_t i = 0; i < n; ++i) L.life[lane[i]].phase = in->surround_phase;
+  return LOAM_OK;
 }
 
 namespace loam {

@@ -198,7 +198,85 @@ __global__ __launch_bounds__(256) void k_lanes_init(OdBuffers b, FeatView f, con
     b.nfullEnd[p * kOdBufs + dst] = 0;
   }
 }
+
+struct LaneMapDst {
+  float4* pool;    // [S][map_cap] the current pool
+  int4* slots;     // [S][kCubeNum] its slot tables
+  float* state;    // [S][kMpStateFloats]
+  int* istate;     // [S][kMpStateInts]
+  int S, map_cap;
+};
+constexpr int kMapInstallSlotWg = 5;   // workgroups per lane that write its slot table: 4851 int4 in four coalesced passes
+constexpr int kMapInstallPer = 8;      // points per thread of the point workgroups: 8 x 16 bytes in flight per lane of the wave
+constexpr int kMapInstallTile = 256 * kMapInstallPer;
+
+// loam_lanes_map_import: one sorted map into lane list[blockIdx.y]'s current pool segment and slot
+// table.  Workgroups [0, kMapInstallSlotWg) of a lane copy the table (an int4 per cube), workgroup 0
+// also the centre, Aft = pose blockIdx.y and Bef (mi: the call's block, kMi* of lanes.hpp); every
+// other workgroup copies one tile of the points, all its loads issued before its stores.  Source and destination are 16-byte aligned and a
+// wave's 64 lanes touch 1 KiB in a row on both sides.  A lane appears once in the list and no word
+// is shared between lanes: plain stores, no workgroup reads what another writes.
+__global__ __launch_bounds__(256) void k_lanes_map_install(LaneMapDst d, const float4* src, int kept, const int4* table,
+                                                           const int* mi, int n) {
+  const int l = mi[kMiList + blockIdx.y];
+  if (l < 0 || l >= d.S) return;
+  const int tid = threadIdx.x;
+  if (blockIdx.x < kMapInstallSlotWg) {
+    int4* s = d.slots + (size_t)l * kCubeNum;
+    for (int i = blockIdx.x * 256 + tid; i < kCubeNum; i += kMapInstallSlotWg * 256) s[i] = table[i];
+    if (blockIdx.x != 0) return;
+    const float* mf = reinterpret_cast<const float*>(mi);
+    if (tid < 3) d.istate[(size_t)l * kMpStateInts + kMiCenW + tid] = mi[kMiCen + tid];
+    if (tid >= 64 && tid < 70) d.state[(size_t)l * kMpStateFloats + kMpAft + (tid - 64)] = mf[kMiList + n + blockIdx.y * 6 + (tid - 64)];
+    if (tid >= 128 && tid < 134) d.state[(size_t)l * kMpStateFloats + kMpBef + (tid - 128)] = mf[kMiBef + (tid - 128)];
+    return;
+  }
+  const int base = (blockIdx.x - kMapInstallSlotWg) * kMapInstallTile + tid;
+  float4* dst = d.pool + (size_t)l * d.map_cap;
+  static_assert(kMapInstallPer == 8, "eight points per thread, named");
+  // (kept > 0 here: the grid has no point workgroups without points; the lanes past the end load point 0)
+  auto at = [&](int r) { return base + r * 256 < kept ? base + r * 256 : 0; };
+  const float4 v0 = src[at(0)], v1 = src[at(1)], v2 = src[at(2)], v3 = src[at(3)];
+  const float4 v4 = src[at(4)], v5 = src[at(5)], v6 = src[at(6)], v7 = src[at(7)];
+  if (base < kept) dst[base] = v0;
+  if (base + 256 < kept) dst[base + 256] = v1;
+  if (base + 512 < kept) dst[base + 512] = v2;
+  if (base + 768 < kept) dst[base + 768] = v3;
+  if (base + 1024 < kept) dst[base + 1024] = v4;
+  if (base + 1280 < kept) dst[base + 1280] = v5;
+  if (base + 1536 < kept) dst[base + 1536] = v6;
+  if (base + 1792 < kept) dst[base + 1792] = v7;
+}
 }  // namespace
+
+hipError_t lanes_map_import_alloc(Lanes& L) {
+  if (L.mi_h) return hipSuccess;
+  const size_t bytes = ((size_t)kMiList + 7 * (size_t)L.S) * sizeof(int);
+  hipError_t e = hipHostMalloc((void**)&L.mi_h, bytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&L.mi_d, bytes);
+  if (e != hipSuccess) {
+    if (L.mi_h) (void)hipHostFree(L.mi_h);
+    L.mi_h = nullptr;
+    L.mi_d = nullptr;
+  }
+  return e;
+}
+
+hipError_t lanes_map_install(Lanes& L, const float4* src, int kept, const int* table, int n, hipStream_t st) {
+  const MpBuffers& b = L.mp;
+  if (n <= 0 || n > L.S || kept < 0 || kept > b.map_cap) return hipErrorInvalidValue;
+  LaneMapDst d;
+  d.pool = b.pool + (size_t)b.pool_cur * b.P * b.map_cap;
+  d.slots = (int4*)b.slots + (size_t)b.pool_cur * b.P * kCubeNum;
+  d.state = b.state;
+  d.istate = b.istate;
+  d.S = L.S;
+  d.map_cap = b.map_cap;
+  const int tiles = (kept + kMapInstallTile - 1) / kMapInstallTile;
+  hipLaunchKernelGGL(k_lanes_map_install, dim3(kMapInstallSlotWg + tiles, n), dim3(256), 0, st, d, src, kept,
+                     (const int4*)table, L.mi_d, n);
+  return hipGetLastError();
+}
 
 hipError_t lanes_restart_alloc(Lanes& L) {
   if (L.rs_h) return hipSuccess;
@@ -364,6 +442,8 @@ void lanes_free(Lanes& L) {
   if (L.out_h) (void)hipHostFree(L.out_h);
   if (L.rs_h) (void)hipHostFree(L.rs_h);
   if (L.rs_d) (void)hipFree(L.rs_d);
+  if (L.mi_h) (void)hipHostFree(L.mi_h);
+  if (L.mi_d) (void)hipFree(L.mi_d);
   L = Lanes();
 }
 

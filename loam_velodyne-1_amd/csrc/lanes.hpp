@@ -48,6 +48,8 @@ struct LaneLife {
   int phase = 4;   // laserMapping's mapFrameCount of this lane (loam_lanes_map_export's surround_phase)
 };
 enum { kLaneRuns = 0, kLaneWaits, kLaneInits };
+// words of loam_lanes_map_import's block: centre[3], Bef[6], then the list and the poses
+enum { kMiCen = 0, kMiBef = 3, kMiList = 9 };
 // what k_lanes_restart clears of a lane
 enum { kClearOd = 1, kClearMp = 2, kClearImu = 4 };
 
@@ -74,6 +76,10 @@ struct Lanes {
   // front of it, then the lanes whose init frame it is
   int* rs_h = nullptr;         // pinned [2S]
   int* rs_d = nullptr;         // device [2S]
+  // loam_lanes_map_import's block of a call (allocated by the first import): the centre and Bef,
+  // the n lane indices, then their n Aft poses of 6 floats (kMi*)
+  int* mi_h = nullptr;         // pinned [kMiList + 7S]
+  int* mi_d = nullptr;         // device [kMiList + 7S]
   // the protocol: a step pushed and not yet pulled; what that step published; whether the last
   // pulled step left registered clouds
   bool in_flight = false, step_ran = false, have_reg = false;
@@ -114,6 +120,34 @@ hipError_t lanes_restart_clear(Lanes& L, const int* list_d, int n, int what, hip
 // list_d end the step as the odometry's init frame leaves a context: Last[dst] = the raw lessSharp
 // / lessFlat clouds, transform zero, transformSum zero or the IMU start pitch / roll, istate zero
 hipError_t lanes_init_frame(Lanes& L, const FeatView& f, const int* list_d, int n, int dst, hipStream_t st);
+
+
+// loam_lanes_map_import's argument check of the lane list (host only): 0, or which rule lane[*bad]
+// breaks.  n in [1, S] is the caller's to check; lane[] is read below n only, and fail / wait (S
+// entries: a lane's sticky failure, LaneLife::wait) only at indices below S
+enum { kLaneListOk = 0, kLaneListRange, kLaneListTwice, kLaneListFailed, kLaneListWaits };
+inline int lanes_list_check(const uint32_t* lane, uint32_t n, int S, const int* fail, const LaneLife* life,
+                            std::vector<char>& seen, uint32_t* bad) {
+  seen.assign((size_t)S, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    *bad = i;
+    const uint32_t l = lane[i];
+    if (l >= (uint32_t)S) return kLaneListRange;
+    if (seen[l]) return kLaneListTwice;
+    seen[l] = 1;
+    if (fail[l] != LOAM_OK) return kLaneListFailed;
+    if (life[l].wait >= 0) return kLaneListWaits;
+  }
+  return kLaneListOk;
+}
+
+// the import lists' buffers (the first loam_lanes_map_import)
+hipError_t lanes_map_import_alloc(Lanes& L);
+// k_lanes_map_install: one launch that copies `kept` sorted points (src) and their slot table
+// (table, [kCubeNum] int4) into the current pool segment and slot table of each of the n lanes
+// of L.mi_d's block, and writes each lane's centre, Aft and Bef from that block.  src and table are
+// not part of any lane's live data.
+hipError_t lanes_map_install(Lanes& L, const float4* src, int kept, const int* table, int n, hipStream_t st);
 
 }  // namespace loam
 #endif

@@ -2897,13 +2897,12 @@ __global__ __launch_bounds__(kMapSortThreads) void k_mp_map_scatter(const uint16
   }
 }
 
-// the imported store's slot table (the exclusive prefix of the per-key counts, kind-major as the
-// sort placed the points), centre and poses
+// the slot table of the sorted points: the exclusive prefix of the per-key counts, kind-major as the
+// sort placed them, into nw ([kCubeNum][4]: offC, cntC, offS, cntS); every thread of the workgroup
 template <int NT>
-__global__ __launch_bounds__(NT) void k_mp_map_install(MpBuffers b, const int* cnt, MapPose ps) {
+LOAM_D void map_slots_of(const int* cnt, int* nw) {
   constexpr int N = kMapKeys, E = (N + NT - 1) / NT;
   const int tid = threadIdx.x;
-  int* nw = slot_table(b, 1 - b.pool_cur, 0);
   __shared__ int nn[N];
   __shared__ int scratch[NT / 64 + 1];
   for (int x = tid; x < N; x += NT) nn[x] = cnt[x];
@@ -2924,11 +2923,24 @@ __global__ __launch_bounds__(NT) void k_mp_map_install(MpBuffers b, const int* c
     nw[s * 4 + 2 * kind] = nn[x];
     nw[s * 4 + 1 + 2 * kind] = (x + 1 < N ? nn[x + 1] : run) - nn[x];
   }
+}
+
+// the imported store's slot table, centre and poses (loam_map_import: instance 0, the idle pool)
+template <int NT>
+__global__ __launch_bounds__(NT) void k_mp_map_install(MpBuffers b, const int* cnt, MapPose ps) {
+  const int tid = threadIdx.x;
+  map_slots_of<NT>(cnt, slot_table(b, 1 - b.pool_cur, 0));
   if (tid < 3) b.istate[kMiCenW + tid] = ps.cen[tid];
   if (tid >= 64 && tid < 76) {
     const int k = tid - 64;
     b.state[(k < 6 ? kMpAft : kMpBef - 6) + k] = ps.v[k];
   }
+}
+
+// the same table on its own, for a caller that installs it elsewhere (loam_lanes_map_import)
+template <int NT>
+__global__ __launch_bounds__(NT) void k_mp_map_slots(const int* cnt, int* nw) {
+  map_slots_of<NT>(cnt, nw);
 }
 
 }  // namespace
@@ -3003,37 +3015,47 @@ hipError_t mp_map_bin_result(MapIo& io, hipStream_t st) {
   return hipMemcpyAsync(io.tab_h + kMapTabAcc, io.tab + kMapTabAcc, 8 * sizeof(int), hipMemcpyDeviceToHost, st);
 }
 
-hipError_t mp_map_install(MpBuffers& b, MapIo& io, int kept, const int* cen, const float* pose12, hipStream_t st,
-                          Prof* prof) {
+hipError_t mp_map_sort(MpBuffers& b, int kept, float4* dst, hipStream_t st, Prof* prof) {
   if (kept < 0 || kept > b.map_cap) return hipErrorInvalidValue;
   const int ntiles = (kept + kMapSortTile - 1) / kMapSortTile;
   // the histograms live in vg.vals_alt (max(map_cap, cap_stack) words, mp_alloc): 128 per 4096 points
   const size_t words = std::max((size_t)b.P * b.map_cap, (size_t)b.P * b.cap_stack);
   if ((size_t)ntiles * kMapDigits > words) return hipErrorInvalidValue;
+  if (kept == 0) return hipSuccess;
   uint16_t *k0 = (uint16_t*)b.vg.keys, *k1 = (uint16_t*)b.vg.keys_alt;
   int* hist = (int*)b.vg.vals_alt;
-  float4* npool = b.pool + (size_t)(1 - b.pool_cur) * b.P * b.map_cap;
-  if (kept > 0) {
-    hipLaunchKernelGGL(k_mp_map_hist<0>, dim3(ntiles), dim3(kMapSortThreads), 0, st, k0, kept, hist, ntiles);
-    if (prof) prof->mark("k_mp_map_hist");
-    hipLaunchKernelGGL(k_mp_map_scan<1024>, dim3(1), dim3(1024), 0, st, hist, ntiles * kMapDigits);
-    if (prof) prof->mark("k_mp_map_scan");
-    hipLaunchKernelGGL(k_mp_map_scatter<0>, dim3(ntiles), dim3(kMapSortThreads), 0, st, k0, (const uint32_t*)nullptr,
-                       kept, hist, ntiles, k1, b.vg.vals, (const float4*)nullptr, (float4*)nullptr);
-    if (prof) prof->mark("k_mp_map_scatter");
-    hipLaunchKernelGGL(k_mp_map_hist<1>, dim3(ntiles), dim3(kMapSortThreads), 0, st, k1, kept, hist, ntiles);
-    if (prof) prof->mark("k_mp_map_hist");
-    hipLaunchKernelGGL(k_mp_map_scan<1024>, dim3(1), dim3(1024), 0, st, hist, ntiles * kMapDigits);
-    if (prof) prof->mark("k_mp_map_scan");
-    hipLaunchKernelGGL(k_mp_map_scatter<1>, dim3(ntiles), dim3(kMapSortThreads), 0, st, k1, b.vg.vals, kept, hist, ntiles,
-                       (uint16_t*)nullptr, (uint32_t*)nullptr, b.vin, npool);
-    if (prof) prof->mark("k_mp_map_scatter");
-  }
+  hipLaunchKernelGGL(k_mp_map_hist<0>, dim3(ntiles), dim3(kMapSortThreads), 0, st, k0, kept, hist, ntiles);
+  if (prof) prof->mark("k_mp_map_hist");
+  hipLaunchKernelGGL(k_mp_map_scan<1024>, dim3(1), dim3(1024), 0, st, hist, ntiles * kMapDigits);
+  if (prof) prof->mark("k_mp_map_scan");
+  hipLaunchKernelGGL(k_mp_map_scatter<0>, dim3(ntiles), dim3(kMapSortThreads), 0, st, k0, (const uint32_t*)nullptr,
+                     kept, hist, ntiles, k1, b.vg.vals, (const float4*)nullptr, (float4*)nullptr);
+  if (prof) prof->mark("k_mp_map_scatter");
+  hipLaunchKernelGGL(k_mp_map_hist<1>, dim3(ntiles), dim3(kMapSortThreads), 0, st, k1, kept, hist, ntiles);
+  if (prof) prof->mark("k_mp_map_hist");
+  hipLaunchKernelGGL(k_mp_map_scan<1024>, dim3(1), dim3(1024), 0, st, hist, ntiles * kMapDigits);
+  if (prof) prof->mark("k_mp_map_scan");
+  hipLaunchKernelGGL(k_mp_map_scatter<1>, dim3(ntiles), dim3(kMapSortThreads), 0, st, k1, b.vg.vals, kept, hist, ntiles,
+                     (uint16_t*)nullptr, (uint32_t*)nullptr, b.vin, dst);
+  if (prof) prof->mark("k_mp_map_scatter");
+  return hipGetLastError();
+}
+
+hipError_t mp_map_install(MpBuffers& b, MapIo& io, int kept, const int* cen, const float* pose12, hipStream_t st,
+                          Prof* prof) {
+  hipError_t e = mp_map_sort(b, kept, mp_map_idle_pool(b), st, prof);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_mp_map_install<1024>, dim3(1), dim3(1024), 0, st, b, b.app_cnt, map_pose(cen, pose12));
   if (prof) prof->mark("k_mp_map_install");
-  const hipError_t e = hipGetLastError();
+  e = hipGetLastError();
   if (e == hipSuccess) b.pool_cur = 1 - b.pool_cur;
   return e;
+}
+
+hipError_t mp_map_slots(MpBuffers& b, MapIo& io, hipStream_t st, Prof* prof) {
+  hipLaunchKernelGGL(k_mp_map_slots<1024>, dim3(1), dim3(1024), 0, st, b.app_cnt, io.tab + kMapTabSlots);
+  if (prof) prof->mark("k_mp_map_slots");
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------- localization: host side

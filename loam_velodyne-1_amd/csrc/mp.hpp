@@ -195,8 +195,9 @@ constexpr int kMapChunkPts = 1 << 21;             // points of one import chunk 
 constexpr int kMapBinTile = 1024;                 // points per workgroup of the chunk kernels
 constexpr int kMapChunkTiles = kMapChunkPts / kMapBinTile;
 constexpr int kMapTabTile = kMapTabSrc + kMapKeys + 2;  // [kMapChunkTiles] a chunk's kept points per tile, scanned in place
-constexpr int kMapTabInts = kMapTabTile + kMapChunkTiles;
-static_assert(kMapTabHead % 4 == 0 && kMapTabTile % 4 == 0, "table regions");
+constexpr int kMapTabSlots = kMapTabTile + kMapChunkTiles;  // [kCubeNum][4] the sorted points' slot table (lanes import)
+constexpr int kMapTabInts = kMapTabSlots + 4 * kCubeNum;
+static_assert(kMapTabHead % 4 == 0 && kMapTabTile % 4 == 0 && kMapTabSlots % 4 == 0, "table regions");
 struct MapIo {
   int* tab = nullptr;    // device [kMapTabInts]
   int* tab_h = nullptr;  // pinned [kMapTabHead]
@@ -218,10 +219,17 @@ hipError_t mp_map_bin_chunk(MpBuffers& b, MapIo& io, const float4* pts, int n, i
                             hipStream_t st, Prof* prof);
 // import: the accumulators into io.tab_h + kMapTabAcc (the caller synchronises st)
 hipError_t mp_map_bin_result(MapIo& io, hipStream_t st);
-// import: the kept points (<= map_cap) sorted stably by key into the idle pool, its slot table, the
-// centre and the Bef / Aft poses (pose12: aft then bef); on success the store switches to that pool
+// import: the kept points (<= map_cap) sorted stably by key into dst (map_cap points, not vin)
+hipError_t mp_map_sort(MpBuffers& b, int kept, float4* dst, hipStream_t st, Prof* prof);
+// the idle pool from instance 0's segment on (free between two frames, as vin)
+inline float4* mp_map_idle_pool(const MpBuffers& b) { return b.pool + (size_t)(1 - b.pool_cur) * b.P * b.map_cap; }
+// import: mp_map_sort into the idle pool, its slot table, the centre and the Bef / Aft poses of
+// instance 0 (pose12: aft then bef); on success the store switches to that pool
 hipError_t mp_map_install(MpBuffers& b, MapIo& io, int kept, const int* cen, const float* pose12, hipStream_t st,
                           Prof* prof);
+// import: the slot table of the sorted points into io.tab + kMapTabSlots (k_mp_map_slots); nothing
+// of the store changes (loam_lanes_map_import copies the points and the table into the lanes)
+hipError_t mp_map_slots(MpBuffers& b, MapIo& io, hipStream_t st, Prof* prof);
 
 // ---- multi-hypothesis localization in a streaming store (loam_map_localize) ----
 // n candidate (Aft, Bef) poses, one sweep: each candidate's laserMapping L-M against the store of `s`

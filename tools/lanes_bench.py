@@ -2,7 +2,8 @@
 stepped by loam_chain_sweep from one thread, through the C-ABI on one GPU.
 
   python tools/lanes_bench.py [--s 1,16,64] [--sweeps 27] [--map-cap 131072] [--yard-max 1024]
-                              [--profile-s 64] [--imu] [--restart K,M] [--occupancy N] [--out FILE]
+                              [--profile-s 64] [--imu] [--restart K,M] [--occupancy N] [--map-import N]
+                              [--out FILE]
 
 Per S: S lanes over eight distinct VLP-16 synthetic streams laid out cyclically.  The wall time of
 lanes_step (push + pull), and of the push alone (host packing + enqueue), median and range over the
@@ -30,7 +31,18 @@ A restarted lane goes on with its stream's next sweeps (as a fresh sequence).
 --occupancy N (instead of the above): a directory of N synthetic recordings of 10..40 sweeps over
 S = 16 lanes, (a) recycled: a lane whose recording has ended is restarted onto the next one, (b)
 retired and left dead: waves of 16 recordings, each wave a loam_lanes_open ... loam_lanes_close that
-lasts as long as its longest recording.  Total sweeps per second both ways, open / close included."""
+lasts as long as its longest recording.  Total sweeps per second both ways, open / close included.
+
+--map-import N (instead of the above): per S and for two maps (the map a context
+builds over stream 1 in --sweeps sweeps, and N synthetic points inside the grid, half corner half
+surf), in one process: the wall time of one loam_lanes_map_import into all S lanes and into lane 0
+alone, of loam_map_import into one streaming context, and of the parent's only way to give S
+sequences the map, min(S, --yard-max) contexts (made as the yardstick's) each receiving
+loam_map_import (scaled by S / contexts when fewer).  Every figure is a median with its range over
+seven calls after two warm-up calls; the sides alternate call by call.  Then the same calls under
+loam_set_profiling for the device time per launch of every import kernel, k_lanes_map_install's
+bytes written (n kept 16 + n 4851 16) over its device time, and a hipMemcpyDtoD of as many bytes
+timed with events in the same process (median of seven after two warm-up copies)."""
 import argparse
 import importlib
 import json
@@ -254,6 +266,107 @@ def run_occupancy(n_rec, streams, map_cap, S=16):
                 recycled_over_left_dead=round(waves_s / recycled_s, 3))
 
 
+def _dtod_ms(nbytes, reps=7, warm=2):
+    """hipMemcpyDtoD of nbytes between two fresh device buffers: event times in ms"""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    vp = ctypes.c_void_p
+
+    def ok(rc):
+        if rc != 0:
+            raise RuntimeError(f"HIP error {rc}")
+    a, b, e0, e1 = vp(), vp(), vp(), vp()
+    ok(hip.hipMalloc(ctypes.byref(a), ctypes.c_size_t(nbytes)))
+    ok(hip.hipMalloc(ctypes.byref(b), ctypes.c_size_t(nbytes)))
+    ok(hip.hipMemset(a, 1, ctypes.c_size_t(nbytes)))
+    ok(hip.hipEventCreate(ctypes.byref(e0)))
+    ok(hip.hipEventCreate(ctypes.byref(e1)))
+    ts = []
+    for r in range(warm + reps):
+        ok(hip.hipEventRecord(e0, None))
+        ok(hip.hipMemcpyDtoDAsync(b, a, ctypes.c_size_t(nbytes), None))
+        ok(hip.hipEventRecord(e1, None))
+        ok(hip.hipEventSynchronize(e1))
+        ms = ctypes.c_float(0)
+        ok(hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1))
+        if r >= warm:
+            ts.append(ms.value)
+    for ev in (e0, e1):
+        ok(hip.hipEventDestroy(ev))
+    ok(hip.hipFree(a))
+    ok(hip.hipFree(b))
+    return ts
+
+
+def run_map_import(S, maps, map_cap, yard_max, reps=7, warm=2):
+    """one JSON line per map: see the module text"""
+    ny = min(S, yard_max)
+    eng = loam.Engine(loam.default_config(system_delay=1))
+    eng.lanes_open(S, map_cap)
+    yard = []
+    for _ in range(ny):
+        e = loam.Engine(loam.default_config(system_delay=1, map_capacity=map_cap))
+        e.set_tuning(batch_streams=0)
+        yard.append(e)
+    every = list(range(S))
+    out = []
+    for name, m in maps:
+        kw = dict(corner=m["corner"], surf=m["surf"], center=m["center"], surround_phase=4)
+        wall = {"lanes_all": [], "lanes_one": [], "context_one": [], "contexts_all": []}
+
+        def timed(key, f, r):
+            t0 = time.perf_counter()
+            f()
+            if r >= warm:
+                wall[key].append((time.perf_counter() - t0) * 1e3)
+        dropped = None
+        for r in range(warm + reps):  # (every call ends in its own synchronisation)
+            timed("lanes_all", lambda: eng.lanes_map_import(every, **kw), r)
+            timed("contexts_all", lambda: [e.map_import(**kw) for e in yard], r)
+            timed("lanes_one", lambda: eng.lanes_map_import([0], **kw), r)
+            timed("context_one", lambda: yard[0].map_import(**kw), r)
+        dropped = eng.lanes_map_import(every, **kw)
+        lm, cm = eng.lanes_map_export(S - 1), yard[-1].map_export()
+        same = all(np.array_equal(lm[k], cm[k]) for k in ("corner", "surf", "corner_offset", "surf_offset"))
+        kept = int(lm["corner"].shape[0] + lm["surf"].shape[0])
+        # device time per launch, in runs of their own (the events cost host time)
+        dev = {}
+        for key, f in (("lanes_all", lambda: eng.lanes_map_import(every, **kw)),
+                       ("lanes_one", lambda: eng.lanes_map_import([0], **kw))):
+            eng.set_profiling(True)
+            for _ in range(reps):
+                f()
+            dev[key] = {k: [round(v[0] / v[1], 4), v[1]] for k, v in sorted(eng.kernel_times().items()) if v[1]}
+            eng.set_profiling(False)
+        yard[0].set_profiling(True)
+        for _ in range(reps):
+            yard[0].map_import(**kw)
+        dev["context_one"] = {k: [round(v[0] / v[1], 4), v[1]] for k, v in sorted(yard[0].kernel_times().items()) if v[1]}
+        yard[0].set_profiling(False)
+        line = dict(map_import=name, S=S, map_cap=map_cap, points_in=int(m["corner"].shape[0] + m["surf"].shape[0]),
+                    kept=kept, dropped=list(dropped), lane_equals_context=bool(same), contexts=ny,
+                    contexts_scaled=ny != S, wall_ms={k: spread(v) for k, v in wall.items()},
+                    device_ms_per_launch_and_launches=dev)
+        line["contexts_over_lanes"] = round(line["wall_ms"]["contexts_all"]["median"] * (S / ny) /
+                                            line["wall_ms"]["lanes_all"]["median"], 2)
+        line["lanes_one_minus_context_one_ms"] = round(line["wall_ms"]["lanes_one"]["median"] -
+                                                       line["wall_ms"]["context_one"]["median"], 4)
+        for key in ("lanes_all", "lanes_one"):
+            n = S if key == "lanes_all" else 1
+            nbytes = n * (kept + 4851) * 16
+            ms = dev[key].get("k_lanes_map_install", [0, 0])[0]
+            copy = spread(_dtod_ms(nbytes))
+            line[f"install_{key}"] = dict(bytes_written=nbytes, device_ms=ms,
+                                          gb_per_s=round(nbytes / ms / 1e6, 1) if ms else None, dtod_ms=copy,
+                                          dtod_gb_per_s=round(nbytes / copy["median"] / 1e6, 1))
+        out.append(line)
+    for e in yard:
+        e.close()
+    eng.lanes_close()
+    eng.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--s", default="1,16,64")
@@ -264,6 +377,7 @@ def main():
     ap.add_argument("--imu", action="store_true")
     ap.add_argument("--restart", default=None, help="K,M: restart K lanes (0: S / 4) before every M-th step")
     ap.add_argument("--occupancy", type=int, default=0, help="recordings of 10..40 sweeps over 16 lanes")
+    ap.add_argument("--map-import", type=int, default=0, help="points of the synthetic map (and the stream map)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     K = 40 if a.occupancy else a.sweeps
@@ -283,6 +397,20 @@ def main():
 
     if a.occupancy:
         emit(run_occupancy(a.occupancy, streams, a.map_cap))
+        return
+    if a.map_import:
+        e = loam.Engine(loam.default_config(system_delay=1))
+        for k in range(K):
+            e.chain_sweep(streams[0][k], stamp=0.1 * k)
+        stream_map = e.map_export()
+        e.close()
+        rng = np.random.default_rng(0)
+        pts = rng.uniform(-100, 100, (a.map_import, 4)).astype(np.float32)
+        synth = dict(corner=pts[:a.map_import // 2], surf=pts[a.map_import // 2:], center=(10, 5, 10))
+        for S in [int(v) for v in a.s.split(",") if v]:
+            for line in run_map_import(S, [("stream", stream_map), (f"synthetic{a.map_import}", synth)], a.map_cap,
+                                       a.yard_max):
+                emit(line)
         return
     if a.restart:
         k_lanes, every = [int(v) for v in a.restart.split(",")]
