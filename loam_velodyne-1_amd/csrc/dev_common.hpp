@@ -361,6 +361,32 @@ LOAM_D int wave_incl_scan_x(int v) {
   return (int)s;
 }
 
+// Stable rank of a lane among the wave's valid lanes that hold the same key (a ring ID below
+// 2^nb, nb <= 6 and wave-uniform): one ballot per key bit, the lane's peers are the valid lanes
+// that agree with it on every bit.  Returns the number of peers in lower lanes, `peers` their
+// count (the lane itself included); the values of an invalid lane mean nothing.  No loop over the
+// distinct keys (VLP-16's firing order puts all 16 rings in every wave) and no readlane ->
+// compare -> exec chain.
+LOAM_D int wave_key_rank(int key, bool valid, int nb, int& peers) {
+  uint64_t m = __ballot(valid);
+#pragma unroll
+  for (int b = 0; b < 6; ++b) {
+    if (b < nb) {
+      const bool bit = (key >> b) & 1;
+      const uint64_t bal = __ballot(bit);
+      m &= bit ? bal : ~bal;
+    }
+  }
+  peers = __popcll(m);
+  return __popcll(m & lanemask_lt());
+}
+// bits that tell R keys apart (R >= 1)
+LOAM_HD int key_bits(int R) {
+  int nb = 0;
+  while ((1 << nb) < R) ++nb;
+  return nb;
+}
+
 LOAM_D int wave_incl_max(int v) {
   for (int o = 1; o < 64; o <<= 1) {
     int w = __shfl_up(v, o, 64);

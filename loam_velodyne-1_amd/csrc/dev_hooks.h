@@ -113,6 +113,16 @@ int loam_dev_od_nn_run(loam_dev_od_nn* h, const loam_dev_od_nn_job* job, uint64_
 
 int loam_dev_od_nn_destroy(loam_dev_od_nn* h);
 
+/* Scan registration's ring ID (sr.hip) of n caller points (sensor frame: x, y, z, -) under a ring
+ * model (n_rings in [2, 64], ring_model LOAM_RING_*, the linear model's two angles; what loam_create
+ * takes from its loam_config): ring [n] from the production ring_of (tangent thresholds, falling
+ * back to the exact evaluation), exact [n] from ring_of_exact alone, fast [n] 1 where the thresholds
+ * decided.  Rings outside 0 .. n_rings - 1 are those of dropped points.  n in 1 .. LOAM_DEV_SR_RING_MAX.
+ * LOAM_E_HIP without a GPU, LOAM_E_INVAL for bad arguments, LOAM_E_NOMEM. */
+#define LOAM_DEV_SR_RING_MAX (1 << 22)
+int loam_dev_sr_ring_of(int device, int32_t n_rings, int32_t ring_model, float ring_lo_deg, float ring_hi_deg,
+                        const float* pts, int32_t n, int32_t* ring, int32_t* exact, int32_t* fast);
+
 #ifdef __cplusplus
 }
 #endif

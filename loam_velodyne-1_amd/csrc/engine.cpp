@@ -121,6 +121,7 @@ struct loam_ctx {
   int sr_init_count = 0;
   bool sr_inited = false;
   SrBuffers sr1;        // one sweep
+  SrRingTab ring_tab;   // the ring model's tangent thresholds (sr_params)
   SrBuffers odin;       // odometry input feature set (host topics uploaded here)
   OdBuffers od1;        // one odometry problem
   bool od_inited = false;
@@ -361,6 +362,7 @@ SrParams sr_params(const loam_ctx* c) {
   p.ring_model = (int)c->cfg.ring_model;
   p.ring_lo = c->cfg.ring_lo_deg;
   p.ring_hi = c->cfg.ring_hi_deg;
+  c->ring_tab.fill(p);
   return p;
 }
 
@@ -457,6 +459,7 @@ int loam_create(loam_ctx** out, const loam_config* cfg, int device) {
     loam_destroy(x);
     return fail(LOAM_E_HIP, std::string("event creation failed: ") + hipGetErrorString(he));
   }
+  if (he == hipSuccess) he = sr_ring_tab_alloc(x->ring_tab, sr_params(x));
   if (he == hipSuccess) he = sr_alloc(x->sr1, 1, x->cap, x->R);
   if (he == hipSuccess) he = sr_alloc(x->odin, 1, x->cap, x->R);
   if (he == hipSuccess) he = od_alloc(x->od1, 1, x->R, x->cap, (int)c.od_max_iter);
@@ -491,6 +494,7 @@ void loam_destroy(loam_ctx* x) {
   if (x->st2) (void)hipStreamSynchronize(x->st2);  // (a pipelined step's mapping set runs there)
   if (x->st3) (void)hipStreamSynchronize(x->st3);
   if (x->st4) (void)hipStreamSynchronize(x->st4);
+  sr_ring_tab_free(x->ring_tab);
   sr_free(x->sr1);
   sr_free(x->odin);
   od_free(x->od1);

@@ -25,7 +25,7 @@ enum : int {
   ERR_VG_BITS = 32,     // a VoxelGrid segment's voxel keys exceed the bits its sort was given
 };
 
-constexpr int kSrThreads = 512;     // ring-sort workgroup (one per sweep)
+constexpr int kSrThreads = 512;     // ring-sort workgroup (one per sweep, or per sub-tile of a kRingTile tile)
 constexpr int kSelThreads = 256;    // per-ring selection workgroup
 constexpr int kRingCap = 4096;      // max ring span (points) handled in LDS by one workgroup
 constexpr int kBigSlots = 8;        // workgroups (scratch slots) of the global-memory selection
@@ -187,6 +187,11 @@ struct SrParams {
   int R;
   int ring_model;
   float ring_lo, ring_hi;
+  // ring ID from tangent thresholds (SrRingTab, sr.hip ring_of): per interval between two ring
+  // boundaries (tan above the lower, tan below the upper, ring bits, -); ring_n = 0: none
+  const float4* ring_tab = nullptr;
+  int ring_n = 0;
+  float ring_a0 = 0.0f, ring_ainv = 0.0f;  // interval guess: (degrees - ring_a0) * ring_ainv
   loamimu::SrQueue* imu = nullptr;  // device IMU queue of sweep 0 (streaming), nullptr = no IMU
   double time_scan = 0.0;           // timeScanCur: the sweep's stamp
   // lanes, all four or none: imu is then a queue per sweep, and sweep s is
@@ -291,6 +296,22 @@ struct Staging {
 // the thread-local message loam_last_error() returns (engine.cpp)
 void set_last_error(const std::string& msg);
 
+// The ring model's threshold table, built once per context from ring_id itself (sr.hip).
+struct SrRingTab {
+  float4* dev = nullptr;
+  int n = 0;
+  float a0 = 0.0f, ainv = 0.0f;
+  void fill(SrParams& p) const {
+    p.ring_tab = dev;
+    p.ring_n = dev ? n : 0;
+    p.ring_a0 = a0;
+    p.ring_ainv = ainv;
+  }
+};
+// p: R, ring_model, ring_lo, ring_hi.  A model that cannot be tabulated gives n = 0 (every point
+// then takes the exact evaluation); an error only for a failed allocation or copy.
+hipError_t sr_ring_tab_alloc(SrRingTab& t, const SrParams& p);
+void sr_ring_tab_free(SrRingTab& t);
 hipError_t sr_alloc(SrBuffers& b, int S, int cap, int R);  // on failure: freed, b empty
 // S sweeps packed back to back in src (sweep s at off[s], n[s] points) into raw at stride cap
 // (loam_batch_feed: one host-to-device copy per chunk of sweeps instead of one per sweep)

@@ -22,19 +22,42 @@
 //
 // HBM traffic per sweep (algorithmic): 16 B/pt raw read, 16 B/pt ring-sorted
 // write + read, 16 B per feature point written.
+#include <cmath>
 #include <type_traits>
+#include <vector>
 
 #include "dev_common.hpp"
+#include "dev_hooks.h"
 #include "engine.hpp"
 
 using namespace loamdev;
 
 namespace loam {
 
+// Phase stamps of k_sr_ring_fused, compiled in only by the diagnostic build
+// (tools/build_variant.sh NAME -DLOAM_SR_PHASES, read by tools/sr_phases.py): per workgroup that
+// scatters a tile, the 100 MHz clock (s_memrealtime) at its start and after each barrier-delimited
+// phase, summed over the workgroups: [0] workgroups, [1] ticket, [2] raw loads issued + the sweep-end
+// scans and orientations, [3] ring ID + orientation + counts, [4] publish + ballot ranks, [5] slot
+// prefix + the wait for the sweep's other tiles, [6] ring bases, [7] scatter issued.
+#ifdef LOAM_SR_PHASES
+__device__ unsigned long long g_sr_ph[8];
+#define SR_PH(k)                                                                  \
+  do {                                                                            \
+    if (threadIdx.x == 0) {                                                       \
+      const unsigned long long now = __builtin_amdgcn_s_memrealtime();            \
+      ph_t[k] = now - ph_last;                                                    \
+      ph_last = now;                                                              \
+    }                                                                             \
+  } while (0)
+#else
+#define SR_PH(k) ((void)0)
+#endif
+
 namespace {
 
 
-LOAM_D int ring_id(const SrParams& p, float angle) {
+LOAM_HD int ring_id(const SrParams& p, float angle) {
   if (p.ring_model == LOAM_RING_LINEAR) {
     const float step = (p.ring_hi - p.ring_lo) / (float)(p.R - 1);
     const float angleID = (angle - p.ring_lo) / step;
@@ -47,11 +70,47 @@ LOAM_D int ring_id(const SrParams& p, float angle) {
 // The reference computes the vertical angle in double (:241-247).  The float evaluation is within
 // 1e-4 degrees of it, so whenever a +-1e-3 degree bracket around it maps to one ring the double
 // evaluation cannot land elsewhere; only points that close to a ring boundary pay for it.
-LOAM_D int ring_of(const SrParams& p, float px, float py, float pz) {
+LOAM_D int ring_of_exact(const SrParams& p, float px, float py, float pz) {
   const float af = atanf(py / sqrtf(px * px + pz * pz)) * 57.2957795f;
   const int lo = ring_id(p, af - 1e-3f), hi = ring_id(p, af + 1e-3f);
   if (lo == hi) return lo;
   return ring_id(p, (float)(atan(D(py) / sqrt(D(px * px + pz * pz))) * 180 / M_PI));
+}
+
+// The ring from the tangent of the vertical angle, without atan, sqrt or division.  ring_id is a
+// step function of the float angle; sr_ring_tab_build (below) finds every float at which it
+// changes and stores, per interval between two neighbouring boundaries b0 < b1, the pair
+// (tan(b0 + 1e-3 deg) rounded up, tan(b1 - 1e-3 deg) rounded down) and the interval's ring.  With
+// t = py * rsq(r2) (relative error below 2^-22, which moves the angle by less than 1e-5 degrees,
+// inside the 1e-4 the bracket of ring_of_exact already allows for), a t strictly inside the pair
+// puts the reference's double angle more than ~1e-3 degrees from both boundaries: the ring is the
+// interval's.  The interval is guessed from an odd polynomial for atan (good to 0.01 degrees over
+// +-25); the comparison alone decides, so a wrong guess only costs the exact evaluation.
+// Everything else goes there too: t within 1e-3 degrees of a boundary, beyond the table, not
+// finite, r2 zero, tiny or infinite, or no table (a ring model the host could not tabulate).
+// tab: the workgroup's LDS copy of p.ring_tab (ring_tab_load).
+#ifndef LOAM_SR_RING_TAB
+#define LOAM_SR_RING_TAB 1  // (0: every point takes ring_of_exact, for A/B builds)
+#endif
+LOAM_D int ring_of(const SrParams& p, const float4* tab, float px, float py, float pz, bool* fast = nullptr) {
+  const float r2 = px * px + pz * pz;
+  if (fast) *fast = false;
+  if (LOAM_SR_RING_TAB && p.ring_n > 0 && r2 >= 1e-30f && r2 <= 3e38f) {
+    const float t = py * __builtin_amdgcn_rsqf(r2);
+    const float t2 = t * t;
+    const float a = t * fmaf(t2, fmaf(t2, fmaf(t2, -1.0f / 7, 0.2f), -1.0f / 3), 1.0f) * 57.2957795f;
+    const float g = fminf(fmaxf((a - p.ring_a0) * p.ring_ainv, 0.0f), (float)(p.ring_n - 1));
+    const float4 e = tab[(int)g];
+    if (t > e.x && t < e.y) {
+      if (fast) *fast = true;
+      return __float_as_int(e.z);
+    }
+  }
+  return ring_of_exact(p, px, py, pz);
+}
+constexpr int kRingTabMax = 64;  // intervals (65 boundaries: the linear model's 64 rings)
+LOAM_D void ring_tab_load(const SrParams& p, float4* tab) {  // a barrier before the first ring_of
+  if ((int)threadIdx.x < p.ring_n) tab[threadIdx.x] = p.ring_tab[threadIdx.x];
 }
 
 using loamimu::kNoOri;
@@ -71,12 +130,15 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
   float* tori = b.tmp_ori + (size_t)s * b.cap;
   uint8_t* tsid = b.tmp_sid + (size_t)s * b.cap;
   const int R = p.R, ntiles = (n + kSrThreads - 1) / kSrThreads;
+  const int nb = key_bits(R);
   int* tc = b.tilecnt + (size_t)s * b.ntiles() * R;
   __shared__ int sh_first, sh_last, sh_F, sh_total;
   __shared__ float sh_start, sh_end;
   __shared__ int sh_cnt[64];
   __shared__ int sh_wcnt[kSrThreads / 64][64];
   __shared__ int sh_base[64];
+  __shared__ float4 sh_rtab[kRingTabMax];
+  ring_tab_load(p, sh_rtab);
   if (tid == 0) { sh_first = 0x7fffffff; sh_last = -1; sh_F = 0x7fffffff; }
   __syncthreads();
   int f = 0x7fffffff, l = -1;
@@ -114,7 +176,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
       float ori = 0.0f;
       if (finite3(q)) {
         const float px = q.y, py = q.z, pz = q.x;
-        int scanID = ring_of(p, px, py, pz);
+        int scanID = ring_of(p, sh_rtab, px, py, pz);
         if (scanID >= 0 && scanID <= R - 1) {
           sid = (uint8_t)scanID;
           ori = -atan2f_fdlibm(px, pz);
@@ -209,16 +271,9 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
     float fs[6];
     if (lane < R) sh_wcnt[w][lane] = 0;
     __builtin_amdgcn_wave_barrier();
-    int rank = 0;
-    uint64_t mval = __ballot(valid);
-    while (mval) {
-      const int leader = __ffsll((unsigned long long)mval) - 1;
-      const int rl = __builtin_amdgcn_readlane(sid, leader);
-      const uint64_t mm = __ballot(valid && sid == rl);
-      if (valid && sid == rl) rank = __popcll(mm & lanemask_lt());
-      if (lane == leader) sh_wcnt[w][rl] = __popcll(mm);
-      mval &= ~mm;
-    }
+    int peers;
+    const int rank = wave_key_rank(sid, valid, nb, peers);
+    if (valid && rank == 0) sh_wcnt[w][sid] = peers;
     __syncthreads();
     if (valid) {
       int pos = sh_base[sid] + tc[t * R + sid] + rank;
@@ -338,6 +393,8 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
     }
     if (lane == 0) sh_last = l;
   }
+  __shared__ float4 sh_rtab[kRingTabMax];
+  ring_tab_load(p, sh_rtab);
   if (tid < R) sh_cnt[tid] = 0;
   if (tid == 0) sh_F = 0x7fffffff;
   __syncthreads();
@@ -383,7 +440,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
       float ori = 0.0f;
       if (finite3(q[e])) {
         const float px = q[e].y, py = q[e].z, pz = q[e].x;
-        const int scanID = ring_of(p, px, py, pz);
+        const int scanID = ring_of(p, sh_rtab, px, py, pz);
         if (scanID >= 0 && scanID <= R - 1) {
           sid = (uint8_t)scanID;
           ori = -atan2f_fdlibm(px, pz);
@@ -433,6 +490,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
   static_assert(kSlots <= 64 && (kSlots & (kSlots - 1)) == 0, "slot scan width");
   const int s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int n = b.raw_n[s], R = p.R, nt = (n + kRingTile - 1) / kRingTile;
+  const int nb = key_bits(R);
   if (t >= (nt > 0 ? nt : 1)) return;
   const bool imu = IMU && p.imu_lane[s].has != 0;
   __shared__ int sh_later;  // (IMU) a later tile has a ring-filtered point
@@ -477,16 +535,9 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
 #pragma unroll
   for (int e = 0; e < kRingE; ++e) {
     const bool valid = sid[e] != 255;
-    rank[e] = 0;
-    uint64_t mval = __ballot(valid);
-    while (mval) {
-      const int leader = __ffsll((unsigned long long)mval) - 1;
-      const int rl = __builtin_amdgcn_readlane(sid[e], leader);
-      const uint64_t mm = __ballot(valid && sid[e] == rl);
-      if (valid && sid[e] == rl) rank[e] = __popcll(mm & lanemask_lt());
-      if (lane == leader) sh_wcnt[rl][e * kW + w] = __popcll(mm);
-      mval &= ~mm;
-    }
+    int peers;
+    rank[e] = wave_key_rank(sid[e], valid, nb, peers);
+    if (valid && rank[e] == 0) sh_wcnt[sid[e]][e * kW + w] = peers;
   }
   __syncthreads();
   if (tid == 0) {
@@ -634,10 +685,15 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
   __shared__ float sh_start, sh_end_raw;
   __shared__ int sh_cnt[64], sh_tot[64], sh_pre[64], sh_base[64];
   __shared__ int sh_wcnt[64][kSlots];
+#ifdef LOAM_SR_PHASES
+  unsigned long long ph_t[8] = {0}, ph_last = __builtin_amdgcn_s_memrealtime();
+#endif
   if (tid == 0) sh_ticket = atomicAdd(&b.ring_sync[0], 1);
   __syncthreads();
+  SR_PH(1);
   const int s = sh_ticket / rtiles, t = sh_ticket % rtiles;
   const int n = b.raw_n[s], R = p.R, nt = (n + kRingTile - 1) / kRingTile;
+  const int nb = key_bits(R);
   if (t == 0) {  // the sweep's error bits and ring bounds start here (tile 0 alone writes err in this launch)
     if (tid < 2 * R) b.ring_se[s * 2 * R + tid] = 0;
     if (tid == 0) b.err[s] = 0;
@@ -684,10 +740,13 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
       }
     }
   }
+  __shared__ float4 sh_rtab[kRingTabMax];
+  ring_tab_load(p, sh_rtab);
   if (tid < R) sh_cnt[tid] = 0;
   if (tid == 0) sh_F = 0x7fffffff;
   for (int k = tid; k < 64 * kSlots; k += kSrThreads) (&sh_wcnt[0][0])[k] = 0;
   __syncthreads();
+  SR_PH(2);
   const float startOri = sh_start;
   float endOri = 0.0f;
   if (sh_last >= 0) {
@@ -710,7 +769,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
     ori[e] = 0.0f;
     if (i < n && finite3(q[e])) {
       const float px = q[e].y, py = q[e].z, pz = q[e].x;
-      const int scanID = ring_of(p, px, py, pz);
+      const int scanID = ring_of(p, sh_rtab, px, py, pz);
       if (scanID >= 0 && scanID <= R - 1) {
         sid[e] = scanID;
         ori[e] = -atan2f_fdlibm(px, pz);
@@ -722,6 +781,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
   Floc = wave_min_i(Floc);
   if (lane == 0 && Floc != 0x7fffffff) atomicMin(&sh_F, Floc);
   __syncthreads();
+  SR_PH(3);
   // published with coherent single-word stores: a reader waits on each word itself (the launch
   // presets them to -1), so no fence orders them (an agent-scope fence writes back / invalidates
   // the XCD's whole L2)
@@ -731,19 +791,13 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
 #pragma unroll
   for (int e = 0; e < kRingE; ++e) {
     const bool valid = sid[e] != 255;
-    rank[e] = 0;
-    uint64_t mval = __ballot(valid);
-    while (mval) {
-      const int leader = __ffsll((unsigned long long)mval) - 1;
-      const int rl = __builtin_amdgcn_readlane(sid[e], leader);
-      const uint64_t mm = __ballot(valid && sid[e] == rl);
-      if (valid && sid[e] == rl) rank[e] = __popcll(mm & lanemask_lt());
-      if (lane == leader) sh_wcnt[rl][e * kW + w] = __popcll(mm);
-      mval &= ~mm;
-    }
+    int peers;
+    rank[e] = wave_key_rank(sid[e], valid, nb, peers);
+    if (valid && rank[e] == 0) sh_wcnt[sid[e]][e * kW + w] = peers;
   }
   if (tid < R) { sh_tot[tid] = 0; sh_pre[tid] = 0; }
   __syncthreads();
+  SR_PH(4);
   // per ring, exclusive prefix over the slots: kSlots lanes per ring, groups aligned to kSlots
   for (int k = tid; k < R * kSlots; k += kSrThreads) {
     const int r = k / kSlots, j = k % kSlots;
@@ -777,12 +831,14 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
   __syncthreads();
   if (lane == 0 && F != 0x7fffffff) atomicMin(&sh_F, F);
   __syncthreads();
+  SR_PH(5);
   if (tid == 0) {
     int run = 0;
     for (int r = 0; r < R; ++r) { sh_base[r] = run; run += sh_tot[r]; }
     if (t == 0) b.n_full[s] = run;
   }
   __syncthreads();
+  SR_PH(6);
   F = sh_F;
 #pragma unroll
   for (int e = 0; e < kRingE; ++e) {
@@ -794,6 +850,13 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
       b.full[(size_t)s * b.cap + pos] = make_float4(q[e].y, q[e].z, q[e].x, (float)(sid[e] + 0.1 * D(relTime)));
     }
   }
+#ifdef LOAM_SR_PHASES
+  SR_PH(7);
+  if (tid == 0) {
+    atomicAdd(&g_sr_ph[0], 1ull);
+    for (int k = 1; k < 8; ++k) atomicAdd(&g_sr_ph[k], ph_t[k]);
+  }
+#endif
 }
 
 // ---------------------------------------------------------------- curvature + marks
@@ -801,6 +864,14 @@ constexpr int kFeatTile = 256;  // threads
 constexpr int kFeatE = 4;  // points per thread
 constexpr int kFeatSpan = kFeatTile * kFeatE;
 
+// A point of the LDS tile as a whole float4: one ds_read_b128 (4 LDS cycles per wave instruction).
+// With .w unused the compiler narrows the read to ds_read_b96, which takes 8 (round 10:
+// k_sr_features 0.44 -> 0.39 ms/step at 1024 problems); the empty asm keeps .w live.
+LOAM_D float4 lds_point(const float4* p) {
+  float4 v = *p;
+  asm volatile("" : "+v"(v.w));
+  return v;
+}
 __global__ __launch_bounds__(kFeatTile) void k_sr_features(SrBuffers b, SrParams p) {
   const int s = blockIdx.y, tid = threadIdx.x;
   if ((blockIdx.x | blockIdx.y) == 0 && tid < 2) b.sel_list[tid] = 0;  // (the selection's routing lists)
@@ -819,7 +890,7 @@ __global__ __launch_bounds__(kFeatTile) void k_sr_features(SrBuffers b, SrParams
     const int k = i0 - 6 + t;
     int8_t e = 0;
     if (k >= 5 && k <= n - 7) {
-      const float4 a = sp[t], c = sp[t + 1];
+      const float4 a = lds_point(sp + t), c = lds_point(sp + t + 1);
       float dX = c.x - a.x, dY = c.y - a.y, dZ = c.z - a.z;
       float diff = dX * dX + dY * dY + dZ * dZ;
       if (D(diff) > 0.1) {
@@ -849,7 +920,10 @@ __global__ __launch_bounds__(kFeatTile) void k_sr_features(SrBuffers b, SrParams
     const size_t gi = (size_t)s * b.cap + i;
     float cv = 0.0f;
     if (i >= 5 && i < n - 5) {  // :359-378
-      const float4* q = sp + li;
+      float4 qv[11];
+#pragma unroll
+      for (int k = 0; k < 11; ++k) qv[k] = lds_point(sp + li - 5 + k);
+      const float4* q = qv + 5;
       float dX = q[-5].x + q[-4].x + q[-3].x + q[-2].x + q[-1].x - 10 * q[0].x + q[1].x + q[2].x +
                  q[3].x + q[4].x + q[5].x;
       float dY = q[-5].y + q[-4].y + q[-3].y + q[-2].y + q[-1].y - 10 * q[0].y + q[1].y + q[2].y +
@@ -869,7 +943,7 @@ __global__ __launch_bounds__(kFeatTile) void k_sr_features(SrBuffers b, SrParams
     for (int k = 0; k <= 5; ++k) pk |= (evt[li + k] == 1);
     for (int k = 1; k <= 6; ++k) pk |= (evt[li - k] == 2);
     if (i >= 5 && i <= n - 7) {  // :440-451
-      const float4 a = sp[li - 1], c = sp[li], e = sp[li + 1];
+      const float4 a = lds_point(sp + li - 1), c = lds_point(sp + li), e = lds_point(sp + li + 1);
       float dX = e.x - c.x, dY = e.y - c.y, dZ = e.z - c.z;
       float diff = dX * dX + dY * dY + dZ * dZ;
       float dX2 = c.x - a.x, dY2 = c.y - a.y, dZ2 = c.z - a.z;
@@ -880,7 +954,7 @@ __global__ __launch_bounds__(kFeatTile) void k_sr_features(SrBuffers b, SrParams
     // bit 1: the neighbour walk of :495-520 stops between i-1 and i
     int gap = 0;
     if (i >= 1) {
-      const float4 a = sp[li], c = sp[li - 1];
+      const float4 a = lds_point(sp + li), c = lds_point(sp + li - 1);
       const float ex = a.x - c.x, ey = a.y - c.y, ez = a.z - c.z;
       gap = D(ex * ex + ey * ey + ez * ez) > 0.05 ? 1 : 0;
     }
@@ -2038,6 +2112,105 @@ hipError_t sr_alloc(SrBuffers& b, int S, int cap, int R) {
   return A.err;
 }
 
+// The intervals of ring_of's table, from ring_id itself: every float angle in (-89, 89) degrees at
+// which ring_id changes (a scan at 1/128 degree, then bisection down to neighbouring floats), the
+// inner intervals from the first to the last whose ring is a valid one, each with the tangents
+// 1e-3 degrees inside its two boundaries (computed in double, rounded inward to float and one
+// more float inward for the double's own error) and the ring as bits.  Empty when the model
+// cannot be tabulated: a degenerate linear model, two changes within 1/128 degree, more than
+// kRingTabMax intervals, or intervals so uneven that the kernel's linear guess misses their
+// midpoints (every point then takes ring_of_exact, as before the table existed).
+static std::vector<float4> sr_ring_tab_build(const SrParams& p, float& a0, float& ainv) {
+  std::vector<float4> none;
+  if (p.R < 1) return none;
+  if (p.ring_model == LOAM_RING_LINEAR) {
+    const float step = (p.ring_hi - p.ring_lo) / (float)(p.R - 1);
+    if (!(step >= 0.01f) || !(fabsf(p.ring_lo) <= 1e4f) || !(fabsf(p.ring_hi) <= 1e4f)) return none;
+  }
+  constexpr int G = 128;
+  std::vector<float> last_old, first_new;  // per boundary: the neighbouring floats around the change
+  std::vector<int> val;                    // val[i]: the ring between boundary i - 1 and boundary i
+  float a = -89.0f;
+  int va = ring_id(p, a);
+  val.push_back(va);
+  for (int i = 1; i <= 178 * G; ++i) {
+    const float c = -89.0f + (float)i / G;
+    const int vc = ring_id(p, c);
+    if (vc != va) {
+      float lo = a, hi = c;
+      for (;;) {
+        const float mid = lo + (hi - lo) * 0.5f;
+        if (!(mid > lo && mid < hi)) break;
+        if (ring_id(p, mid) == va) lo = mid; else hi = mid;
+      }
+      if (ring_id(p, hi) != vc) return none;
+      last_old.push_back(lo);
+      first_new.push_back(hi);
+      val.push_back(vc);
+    }
+    a = c;
+    va = vc;
+  }
+  const int nbnd = (int)first_new.size();
+  int i0 = -1, i1 = -1;  // inner intervals are 1 .. nbnd - 1
+  for (int i = 1; i <= nbnd - 1; ++i)
+    if (val[i] >= 0 && val[i] <= p.R - 1) {
+      if (i0 < 0) i0 = i;
+      i1 = i;
+    }
+  if (i0 < 0 || i1 - i0 + 1 > kRingTabMax) return none;
+  const int n = i1 - i0 + 1;
+  auto tan_deg = [](double deg) { return tan(deg * M_PI / 180.0); };
+  std::vector<float4> tab(n);
+  for (int k = 0; k < n; ++k) {
+    const int i = i0 + k;
+    const double dlo = tan_deg(D(first_new[i - 1]) + 1e-3), dhi = tan_deg(D(last_old[i]) - 1e-3);
+    float flo = (float)dlo, fhi = (float)dhi;
+    if (D(flo) < dlo) flo = nextafterf(flo, INFINITY);
+    if (D(fhi) > dhi) fhi = nextafterf(fhi, -INFINITY);
+    flo = nextafterf(flo, INFINITY);
+    fhi = nextafterf(fhi, -INFINITY);
+    tab[k] = make_float4(flo, fhi, __builtin_bit_cast(float, val[i]), 0.0f);
+  }
+  // the guess's line through the boundaries: even spacing from the first one, or (the linear model,
+  // whose ring 0 reaches 1.5 steps down because (int) truncates towards zero) from the second
+  for (int skip = 0; skip < 2 && skip < n; ++skip) {
+    const float top = first_new[i1], w = (top - first_new[i0 - 1 + skip]) / (float)(n - skip);
+    a0 = top - (float)n * w;
+    ainv = 1.0f / w;
+    bool ok = w > 0.0f;
+    for (int k = 0; k < n && ok; ++k) {
+      const float mid = 0.5f * (first_new[i0 + k - 1] + first_new[i0 + k]);
+      ok = (int)fminf(fmaxf((mid - a0) * ainv, 0.0f), (float)(n - 1)) == k;
+    }
+    if (ok) return tab;
+  }
+  return none;
+}
+
+hipError_t sr_ring_tab_alloc(SrRingTab& t, const SrParams& p) {
+  t = SrRingTab();
+  const std::vector<float4> tab = sr_ring_tab_build(p, t.a0, t.ainv);
+  if (tab.empty()) return hipSuccess;
+  hipError_t e = hipMalloc((void**)&t.dev, tab.size() * sizeof(float4));
+  if (e != hipSuccess) {
+    t.dev = nullptr;
+    return e;
+  }
+  e = hipMemcpy(t.dev, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    sr_ring_tab_free(t);
+    return e;
+  }
+  t.n = (int)tab.size();
+  return hipSuccess;
+}
+
+void sr_ring_tab_free(SrRingTab& t) {
+  if (t.dev) HIPCHK(hipFree(t.dev));
+  t = SrRingTab();
+}
+
 void sr_free(SrBuffers& b) {
   void* ptrs[] = {b.raw, b.raw_n, b.tmp_ori, b.tmp_sid, b.tilecnt, b.tileF, b.ring_sync, b.sweep_ori, b.full, b.n_full, b.curv,
                   b.picked, b.sortind, b.label, b.ring_se, b.st_sharp, b.st_lsharp, b.st_flat,
@@ -2109,5 +2282,70 @@ void sr_launch(const SrBuffers& b, const SrParams& p, hipStream_t st, Prof* prof
   mark("k_sr_compact");
 }
 
+// ---------------------------------------------------------------- diagnostic hook (dev_hooks.h)
+namespace {
+__global__ __launch_bounds__(256) void k_dev_sr_ring_of(SrParams p, const float4* pts, int n, int* ring, int* exact,
+                                                         int* fast) {
+  __shared__ float4 sh_rtab[kRingTabMax];
+  ring_tab_load(p, sh_rtab);
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float4 q = pts[i];
+  const float px = q.y, py = q.z, pz = q.x;  // the axis swap of :225-229
+  bool f;
+  ring[i] = ring_of(p, sh_rtab, px, py, pz, &f);
+  exact[i] = ring_of_exact(p, px, py, pz);
+  fast[i] = f ? 1 : 0;
+}
+}  // namespace
+
 }  // namespace loam
 
+extern "C" int loam_dev_sr_ring_of(int device, int32_t n_rings, int32_t ring_model, float ring_lo_deg,
+                                   float ring_hi_deg, const float* pts, int32_t n, int32_t* ring, int32_t* exact,
+                                   int32_t* fast) {
+  using namespace loam;
+  if (!pts || !ring || !exact || !fast || n < 1 || n > LOAM_DEV_SR_RING_MAX) return LOAM_E_INVAL;
+  if (n_rings < 2 || n_rings > 64 || (ring_model != LOAM_RING_VLP16 && ring_model != LOAM_RING_LINEAR)) return LOAM_E_INVAL;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return LOAM_E_HIP;  // (no CPU path, as loam_create)
+  if (device < 0 || device >= ndev) return LOAM_E_INVAL;
+  if (hipSetDevice(device) != hipSuccess) return LOAM_E_HIP;
+  SrParams p;
+  p.R = n_rings;
+  p.ring_model = ring_model;
+  p.ring_lo = ring_lo_deg;
+  p.ring_hi = ring_hi_deg;
+  SrRingTab tab;
+  float4* dpts = nullptr;
+  int* dout = nullptr;
+  hipError_t e = sr_ring_tab_alloc(tab, p);
+  if (e == hipSuccess) e = hipMalloc((void**)&dpts, (size_t)n * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc((void**)&dout, 3 * (size_t)n * sizeof(int));
+  const bool nomem = e == hipErrorOutOfMemory;
+  if (e == hipSuccess) e = hipMemcpy(dpts, pts, (size_t)n * sizeof(float4), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    tab.fill(p);
+    hipLaunchKernelGGL(k_dev_sr_ring_of, dim3((n + 255) / 256), dim3(256), 0, nullptr, p, dpts, n, dout, dout + n,
+                       dout + 2 * (size_t)n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(ring, dout, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(exact, dout + n, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(fast, dout + 2 * (size_t)n, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
+  if (dpts) (void)hipFree(dpts);
+  if (dout) (void)hipFree(dout);
+  sr_ring_tab_free(tab);
+  return e == hipSuccess ? LOAM_OK : (nomem ? LOAM_E_NOMEM : LOAM_E_HIP);
+}
+
+#ifdef LOAM_SR_PHASES
+// the phase sums of k_sr_ring_fused (g_sr_ph above), then zeroed; diagnostic build only
+extern "C" int loam_debug_phases_sr(unsigned long long* out) {
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(loam::g_sr_ph), sizeof(loam::g_sr_ph)) != hipSuccess) return -1;
+  const unsigned long long zero[8] = {0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(loam::g_sr_ph), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
+}
+#endif
