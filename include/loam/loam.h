@@ -522,6 +522,46 @@ int loam_lanes_restart(loam_ctx *ctx, uint32_t lane, uint32_t *wait_steps);
 int loam_lanes_map_import(loam_ctx *ctx, uint32_t n, const uint32_t *lane /* [n] */,
                           const loam_map *in, const loam_pose6 *aft /* [n] or NULL */,
                           uint64_t dropped[2]);
+/* /laser_cloud_surround of every lane whose last pulled frame publishes it, in one call. */
+typedef struct {
+  loam_point *pts;      /* caller-owned; NULL = the points are not wanted */
+  uint64_t capacity;    /* points pts holds */
+  uint64_t count;       /* points of all publishing lanes (written, or required on LOAM_E_CAPACITY) */
+  uint32_t *offset;     /* caller-owned [n_lanes + 1] or NULL: lane l = pts[offset[l] .. offset[l+1]) */
+  int32_t *published;   /* caller-owned [n_lanes] or NULL: 1 = lane l's last frame publishes the topic */
+} loam_lanes_cloud;
+/* loam_mapping_surround for the lanes (src/laserMapping.cpp:1038-1058).
+ * When a lane is due: lane l is due after a pulled step on which the lane mapped (mapped = 1, status
+ * = LOAM_OK) and its own mapFrameCount wrapped (its surround_phase went 4 -> 0): the lane's 1st
+ * mapping frame since open, since a restart or since a surround_phase = 4 import, and every 5th
+ * after that.  A lane is not due on its wait steps, on its init step, while it has failed or
+ * retired, inside system_delay, or on a step that did not map.
+ * Equality with a context: for a due lane the cloud is, bit for bit and in point order, what
+ * loam_mapping_surround returns on the context that lane equals (a fresh context fed through
+ * loam_imu + loam_chain_sweep; after a restart a fresh system_delay = 0 context; after
+ * loam_lanes_map_import a context that received loam_map_import at that point): the in-bounds cubes
+ * of the 5 x 5 x 5 neighbourhood of the frame's centre cube in (i, j, k) loop order, each cube's
+ * corner points then its surf points from the store the frame left, through one VoxelGrid of leaf
+ * 0.2.  A lane that is not due has published[l] = 0 and an empty range.
+ * The result is valid from the pull of a step until the next loam_lanes_push /
+ * loam_lanes_push_stamped.  loam_lanes_restart and loam_lanes_map_import drop the flag of the lanes
+ * they touch (as loam_map_import does for a context); no other lane's flag changes.
+ * The clouds are computed on demand: the call waits for nothing but its own work and changes
+ * nothing in any lane (later steps, registered clouds and exported maps are bit-identical to a run
+ * that never called it); it may be repeated, and repeated calls return the same bits.  One launch
+ * sequence serves every due lane, the counts reach the host in one copy, and the points come back
+ * packed in lane order through the download staging loam_batch_features and loam_map_export share.
+ * When nothing is due (before the first pull too): LOAM_OK, every published = 0, every offset = 0,
+ * count = 0, and nothing is launched.
+ * pts == NULL is the sizes-only query; count, offset and published are always filled when given.
+ * LOAM_E_CAPACITY (count > capacity) writes no point and fills count, offset and published, so the
+ * call can be repeated with more room.
+ * LOAM_E_INVAL, and nothing of out is written: a null ctx / out, lanes not open, a step in flight.
+ * LOAM_E_HIP for a failed HIP call.  LOAM_E_NOMEM when the first call's allocation (two lane lists,
+ * and the shared download staging if no call made it before) fails.  No allocation is sized by the
+ * call: the scratch is the lanes' own VoxelGrid input / output arrays, idle between a pull and the
+ * next push (loam_lanes_map_export uses them the same way). */
+int loam_lanes_surround(loam_ctx *ctx, loam_lanes_cloud *out);
 /* Frees the lanes' working set (waits for a step in flight).  LOAM_E_INVAL when not open. */
 int loam_lanes_close(loam_ctx *ctx);
 

@@ -180,13 +180,19 @@ _LANE_DTYPE = np.dtype([(n, np.float32, (6,)) if t is Pose6 else (n, np.uint32 i
                         for n, t in LaneOut._fields_])
 
 
+class LanesCloud(ctypes.Structure):
+    """include/loam/loam.h loam_lanes_cloud: /laser_cloud_surround of every publishing lane, packed"""
+    _fields_ = [("pts", ctypes.c_void_p), ("capacity", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                ("offset", ctypes.c_void_p), ("published", ctypes.c_void_p)]
+
+
 EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_error", "loam_imu",
            "loam_scan_registration", "loam_odometry", "loam_mapping", "loam_mapping_surround",
            "loam_maintenance", "loam_chain_sweep",
            "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_map_localize", "loam_map_score", "loam_get_stats",
            "loam_lanes_open", "loam_lanes_push", "loam_lanes_pull", "loam_lanes_registered", "loam_lanes_map_export",
            "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
-           "loam_lanes_restart", "loam_lanes_map_import",
+           "loam_lanes_restart", "loam_lanes_map_import", "loam_lanes_surround",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -247,6 +253,7 @@ def lib():
         L.loam_lanes_restart.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32)]
         L.loam_lanes_map_import.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), P(Map), P(Pose6),
                                             P(ctypes.c_uint64)]
+        L.loam_lanes_surround.argtypes = [PP, P(LanesCloud)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -638,6 +645,23 @@ class Engine:
         dropped = (ctypes.c_uint64 * 2)(0, 0)
         _check(lib().loam_lanes_map_import(self.h, n, idx, ctypes.byref(m), poses, dropped))
         return int(dropped[0]), int(dropped[1])
+
+    def lanes_surround(self):
+        """/laser_cloud_surround of every lane from the last pulled step (loam_lanes_surround): a
+        list with one entry per lane, an (n, 4) float32 array where the lane's frame publishes the
+        topic (its 1st mapping frame and every 5th after it) and None where it does not.  Valid
+        until the next lanes_push; the sizes-only call first, then one call with room."""
+        S = self.n_lanes
+        off = np.zeros(S + 1, np.uint32)
+        pub = np.zeros(S, np.int32)
+        c = LanesCloud()
+        c.offset, c.published = off.ctypes.data, pub.ctypes.data
+        _check(lib().loam_lanes_surround(self.h, ctypes.byref(c)))  # sizes only
+        pts = np.empty((int(c.count), 4), np.float32)
+        if pts.shape[0]:
+            c.pts, c.capacity = pts.ctypes.data, pts.shape[0]
+            _check(lib().loam_lanes_surround(self.h, ctypes.byref(c)))
+        return [pts[off[l]:off[l + 1]].copy() if pub[l] else None for l in range(S)]
 
     def lanes_close(self):
         _check(lib().loam_lanes_close(self.h))

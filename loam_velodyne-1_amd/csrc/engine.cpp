@@ -2386,7 +2386,10 @@ hipError_t lanes_enqueue(loam_ctx* x, Prof* pf, bool imu, int n_init) {
       mp_frame(L.mp, in, st, pf);
       L.step_mapped = 1;
       for (int l = 0; l < S; ++l)  // :1038-1040, for the lanes this was a mapping frame for
-        if (L.life[l].kind == kLaneRuns && ++L.life[l].phase >= 5) L.life[l].phase = 0;
+        if (L.life[l].kind == kLaneRuns && ++L.life[l].phase >= 5) {
+          L.life[l].phase = 0;
+          L.life[l].due = kDuePushed;  // (/laser_cloud_surround, once the pull has seen the lane's status)
+        }
       if (n_init) {  // (skip_frame_num = 0) an init frame does not map: the lane's store is empty again
         T(lanes_restart_clear(L, L.rs_d + S, n_init, kClearMp, st));
         x->prof.mark("k_lanes_restart");
@@ -2448,6 +2451,7 @@ int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud
   LanesImu& I = L.imu;
   I.step_imu = false;
   L.have_reg = false;
+  for (int l = 0; l < S; ++l) L.life[l].due = kDueNo;  // (the last step's /laser_cloud_surround)
   if (!L.sr_inited) {  // src/scanRegistration.cpp:213-219 (Q1): the sweeps are not looked at
     L.sr_init_count++;
     if (L.sr_init_count >= (int)x->cfg.system_delay) L.sr_inited = true;
@@ -2625,6 +2629,7 @@ extern "C" int loam_lanes_restart(loam_ctx* x, uint32_t lane, uint32_t* wait_ste
     }
   }
   f.phase = 4;  // mapFrameCount = mapFrameNum - 1 (src/laserMapping.cpp:405)
+  f.due = kDueNo;
   L.fail[lane] = LOAM_OK;
   L.fail_new[lane] = LOAM_OK;
   L.nreg[lane] = 0;
@@ -2715,6 +2720,9 @@ extern "C" int loam_lanes_pull(loam_ctx* x, loam_lane_out* out) {
     }
     if (L.imu.step_imu) std::memcpy(&L.imu_trans[(size_t)l * 12], L.imu.trans_h + (size_t)l * 12, 12 * sizeof(float));
   }
+  // /laser_cloud_surround: a lane whose phase this step wrapped publishes when the frame mapped it
+  for (int l = 0; l < S; ++l)
+    L.life[l].due = L.life[l].due == kDuePushed && out[l].status == LOAM_OK && out[l].mapped ? kDueYes : kDueNo;
   L.pulled = true;
   L.have_reg = L.step_mapped != 0;
   return LOAM_OK;
@@ -2816,7 +2824,96 @@ extern "C" int loam_lanes_map_import(loam_ctx* x, uint32_t n, const uint32_t* la
     return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
   }
   x->prof.collect();
-  for (uint32_t i = 0; i < n; ++i) L.life[lane[i]].phase = in->surround_phase;
+  for (uint32_t i = 0; i < n; ++i) {  // (as loam_map_import: a pending surround publication is dropped)
+    L.life[lane[i]].phase = in->surround_phase;
+    L.life[lane[i]].due = kDueNo;
+  }
+  return LOAM_OK;
+}
+
+// /laser_cloud_surround of every due lane (loam.h).  The stream is idle (the pull
+// drained it) and the lanes' vin / vout / VoxelGrid arrays are free until the next push: one launch
+// sequence gathers, filters and packs the due lanes' clouds there, the counts come back in one copy
+// behind one synchronisation, and the packed points leave through the shared download staging.
+extern "C" int loam_lanes_surround(loam_ctx* x, loam_lanes_cloud* out) {
+  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_surround: lanes are not open");
+  if (L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_surround: a step is in flight (loam_lanes_pull first)");
+  const int S = L.S;
+  int n = 0;
+  for (int l = 0; l < S; ++l) n += L.life[l].due == kDueYes;
+  auto fill = [&](const int* cnt) {  // cnt: the due lanes' counts by lane (null: nothing is due)
+    uint64_t run = 0;
+    for (int l = 0; l < S; ++l) {
+      const bool due = cnt && L.life[l].due == kDueYes;
+      if (out->offset) out->offset[l] = (uint32_t)run;
+      if (out->published) out->published[l] = due ? 1 : 0;
+      if (due) run += (uint64_t)cnt[l];
+    }
+    if (out->offset) out->offset[S] = (uint32_t)run;
+    out->count = run;
+  };
+  if (n == 0) {
+    fill(nullptr);
+    return LOAM_OK;
+  }
+  HIP_TRY(hipSetDevice(x->device));
+  const bool want = out->pts != nullptr;
+  if (lanes_surround_alloc(L) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LOAM_E_NOMEM, "loam_lanes_surround: allocation failed");
+  }
+  if (want) {
+    const int rc = ensure_pack_stage(x, "surround download");
+    if (rc) return rc;
+  }
+  n = 0;
+  for (int l = 0; l < S; ++l)
+    if (L.life[l].due == kDueYes) L.su_h[n++] = l;
+  hipStream_t st = x->st;
+  x->prof.begin(st);
+  hipError_t he = lanes_surround_run(L, n, want, st, x->prof.on ? &x->prof : nullptr);
+  const hipError_t se = hipStreamSynchronize(st);
+  if (he == hipSuccess) he = se;
+  if (he == hipSuccess) he = L.mp.take_error();
+  if (he != hipSuccess) return fail(LOAM_E_HIP, std::string("loam_lanes_surround: ") + hipGetErrorString(he));
+  std::vector<int> cnt((size_t)S, 0);
+  for (int i = 0; i < n; ++i) cnt[L.su_h[i]] = lanes_surround_count(L, L.su_h[i]);
+  fill(cnt.data());
+  const uint64_t total = out->count;
+  if (!want || total == 0) {
+    x->prof.collect();
+    return LOAM_OK;
+  }
+  if (total > out->capacity) {
+    x->prof.collect();
+    return fail(LOAM_E_CAPACITY, "loam_lanes_surround: capacity is too small (count holds the required size)");
+  }
+  // the packed runs (vin from 0 on) in chunks of one pinned buffer: chunk k is DMA'd into buffer
+  // k & 1 while the host copies chunk k - 1 into the caller's array (as loam_map_export)
+  const float4* packed = L.mp.vin;
+  const size_t nchunk = (size_t)((total + kPackStagePts - 1) / kPackStagePts);
+  auto enqueue = [&](size_t k) -> hipError_t {
+    const size_t a = k * kPackStagePts, m = std::min(kPackStagePts, (size_t)total - a);
+    hipError_t e = hipMemcpyAsync(x->pack_pin[k & 1], packed + a, m * sizeof(float4), hipMemcpyDeviceToHost, st);
+    x->prof.mark("lanes_surround_d2h");
+    if (e == hipSuccess) e = hipEventRecord(x->pack_done[k & 1], st);
+    return e;
+  };
+  for (size_t k = 0; k < nchunk && k < 2 && he == hipSuccess; ++k) he = enqueue(k);
+  for (size_t k = 0; k < nchunk && he == hipSuccess; ++k) {
+    const size_t a = k * kPackStagePts, m = std::min(kPackStagePts, (size_t)total - a);
+    he = hipEventSynchronize(x->pack_done[k & 1]);
+    if (he != hipSuccess) break;
+    copy_wide(out->pts + a, x->pack_pin[k & 1], m * sizeof(float4));
+    if (k + 2 < nchunk) he = enqueue(k + 2);
+  }
+  if (he != hipSuccess) {  // (drain what was enqueued before reporting)
+    (void)hipStreamSynchronize(st);
+    return fail(LOAM_E_HIP, std::string("loam_lanes_surround: ") + hipGetErrorString(he));
+  }
+  x->prof.collect();
   return LOAM_OK;
 }
 

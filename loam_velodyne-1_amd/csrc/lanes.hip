@@ -247,7 +247,171 @@ __global__ __launch_bounds__(256) void k_lanes_map_install(LaneMapDst d, const f
   if (base + 1536 < kept) dst[base + 1536] = v6;
   if (base + 1792 < kept) dst[base + 1792] = v7;
 }
+
+struct LaneSur {
+  const float4* pool;  // [S][map_cap] the current pool
+  const int4* slots;   // [S][kCubeNum] its slot tables
+  const int* istate;   // [S][kMpStateInts]
+  float4* vin;         // [S][map_cap] lane l's VoxelGrid input at l * map_cap
+  const float4* vout;  // [S][map_cap] ... and its output
+  int *vseg_b, *vseg_e, *vseg_cnt;  // segment l = lane l
+  float* vseg_leaf;
+  int* vg_lin;         // the VoxelGrid's input list: the due lanes
+  int* vg_counts;      // VgScratch::counts
+  int S, map_cap;
+};
+constexpr int kSurWg = 16;   // workgroups per due lane (a 16k-point neighbourhood: one tile each)
+constexpr int kSurPer = 4;   // points per thread and tile: 4 x 16 bytes in flight per lane of the wave
+constexpr int kSurTile = 256 * kSurPer;
+constexpr int kSurCubes = 125;  // the 5 x 5 x 5 neighbourhood (kMaxValid)
+
+// loam_lanes_surround's gather: k_mp_surround for lane list[blockIdx.y], over kSurWg workgroups.
+// Every workgroup of a lane derives the lane's 125 neighbourhood entries itself (thread t = cube
+// (i, j, k) of the reference's loop order, an out-of-bounds cube an empty entry) and two block
+// scans give each entry's first point and first tile; the (cube, tile) pieces are then dealt round
+// robin to the lane's workgroups.  A piece is kSurTile points of one cube, corner points then surf
+// points: four loads per thread issued before the four stores, a wave's 64 lanes 1 KiB in a row on
+// both sides.  Workgroup 0 of a lane writes its segment (vseg_b / vseg_e / vseg_leaf = 0.2, the
+// leaf of downSizeFilterCorner) and its entry of the VoxelGrid's input list; workgroup (0, 0) the
+// cascade's counters.  No word is shared between lanes and none is read that another workgroup
+// writes: plain stores.  Every index is checked against map_cap (a store whose last update
+// overflowed is a failed lane and never listed).
+__global__ __launch_bounds__(256) void k_lanes_surround(LaneSur s, const int* list, int n) {
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
+    s.vg_counts[0] = 0;
+    s.vg_counts[1] = 0;
+    s.vg_counts[2] = n;
+  }
+  const int l = list[blockIdx.y];
+  if (l < 0 || l >= s.S) return;
+  __shared__ int4 sh_slot[kSurCubes];
+  __shared__ int sh_pre[kSurCubes], sh_tpre[kSurCubes], sh_scan[8];
+  const int* ist = s.istate + (size_t)l * kMpStateInts;
+  int4 e = make_int4(0, 0, 0, 0);
+  if (tid < kSurCubes) {
+    const int i = ist[kMiCubeI] - 2 + tid / 25, j = ist[kMiCubeJ] - 2 + (tid / 5) % 5, k = ist[kMiCubeK] - 2 + tid % 5;
+    if (i >= 0 && i < kCubeW && j >= 0 && j < kCubeH && k >= 0 && k < kCubeD)
+      e = s.slots[(size_t)l * kCubeNum + (i + kCubeW * j + kCubeW * kCubeH * k)];
+    e.y = min(max(e.y, 0), s.map_cap);
+    e.w = min(max(e.w, 0), s.map_cap);
+  }
+  const int pts = e.y + e.w, tiles = (pts + kSurTile - 1) / kSurTile;
+  int total, ntiles;
+  const int pre = loamdev::block_excl_scan<256>(pts, sh_scan, total);
+  const int tpre = loamdev::block_excl_scan<256>(tiles, sh_scan, ntiles);
+  if (tid < kSurCubes) {
+    sh_slot[tid] = e;
+    sh_pre[tid] = pre;
+    sh_tpre[tid] = tpre;
+  }
+  __syncthreads();
+  if (blockIdx.x == 0 && tid == 0) {
+    s.vseg_b[l] = l * s.map_cap;
+    s.vseg_e[l] = l * s.map_cap + min(total, s.map_cap);
+    s.vseg_leaf[l] = 0.2f;
+    s.vg_lin[blockIdx.y] = l;
+  }
+  const float4* pool = s.pool + (size_t)l * s.map_cap;
+  float4* dst = s.vin + (size_t)l * s.map_cap;
+  static_assert(kSurPer == 4, "four points per thread, named");
+  for (int p = blockIdx.x; p < ntiles; p += gridDim.x) {
+    int c = 0;  // the last entry whose first tile is at or before p (it has tiles)
+    for (int step = 64; step > 0; step >>= 1)
+      if (c + step < kSurCubes && sh_tpre[c + step] <= p) c += step;
+    const int4 q = sh_slot[c];
+    const int cnt = q.y + q.w, t0 = (p - sh_tpre[c]) * kSurTile + tid, d0 = sh_pre[c];
+    // (the lanes past the piece's end load point 0 and store nothing)
+    auto src = [&](int t) { return t < q.y ? q.x + t : q.z + (t - q.y); };
+    auto ok = [&](int t) { return t < cnt && d0 + t < s.map_cap && src(t) >= 0 && src(t) < s.map_cap; };
+    const bool k0 = ok(t0), k1 = ok(t0 + 256), k2 = ok(t0 + 512), k3 = ok(t0 + 768);
+    const float4 v0 = pool[k0 ? src(t0) : 0], v1 = pool[k1 ? src(t0 + 256) : 0];
+    const float4 v2 = pool[k2 ? src(t0 + 512) : 0], v3 = pool[k3 ? src(t0 + 768) : 0];
+    if (k0) dst[d0 + t0] = v0;
+    if (k1) dst[d0 + t0 + 256] = v1;
+    if (k2) dst[d0 + t0 + 512] = v2;
+    if (k3) dst[d0 + t0 + 768] = v3;
+  }
+}
+
+// loam_lanes_surround's pack, behind the VoxelGrid: lane list[blockIdx.y]'s output run (vout + l *
+// map_cap, vseg_cnt[l] points) to its place behind the runs of the list's earlier lanes, from
+// vin[0] on (vin is free again).  Every workgroup sums the earlier lanes' counts itself (a block
+// scan over the list); the copy is k_lanes_surround's, four loads before four stores.
+__global__ __launch_bounds__(256) void k_lanes_surround_pack(LaneSur s, const int* list) {
+  const int tid = threadIdx.x;
+  const int l = list[blockIdx.y];
+  if (l < 0 || l >= s.S) return;
+  __shared__ int sh_scan[8];
+  auto count = [&](int lane) { return lane < 0 || lane >= s.S ? 0 : min(max(s.vseg_cnt[lane], 0), s.map_cap); };
+  int part = 0, off;
+  for (int i = tid; i < (int)blockIdx.y; i += 256) part += count(list[i]);
+  (void)loamdev::block_excl_scan<256>(part, sh_scan, off);
+  const int m = count(l);
+  const float4* src = s.vout + (size_t)l * s.map_cap;
+  float4* dst = s.vin + off;  // (off + m <= the listed lanes' map_cap together)
+  for (int t0 = blockIdx.x * kSurTile + tid; t0 - tid < m; t0 += gridDim.x * kSurTile) {
+    const bool k0 = t0 < m, k1 = t0 + 256 < m, k2 = t0 + 512 < m, k3 = t0 + 768 < m;
+    const float4 v0 = src[k0 ? t0 : 0], v1 = src[k1 ? t0 + 256 : 0], v2 = src[k2 ? t0 + 512 : 0], v3 = src[k3 ? t0 + 768 : 0];
+    if (k0) dst[t0] = v0;
+    if (k1) dst[t0 + 256] = v1;
+    if (k2) dst[t0 + 512] = v2;
+    if (k3) dst[t0 + 768] = v3;
+  }
+}
 }  // namespace
+
+hipError_t lanes_surround_alloc(Lanes& L) {
+  if (L.su_h) return hipSuccess;
+  hipError_t e = hipHostMalloc((void**)&L.su_h, (size_t)2 * L.S * sizeof(int), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&L.su_d, (size_t)L.S * sizeof(int));
+  if (e != hipSuccess) {
+    if (L.su_h) (void)hipHostFree(L.su_h);
+    L.su_h = nullptr;
+    L.su_d = nullptr;
+  }
+  return e;
+}
+
+hipError_t lanes_surround_run(Lanes& L, int n, bool pack, hipStream_t st, Prof* prof) {
+  MpBuffers& b = L.mp;
+  if (n <= 0 || n > L.S) return hipErrorInvalidValue;
+  auto mark = [&](const char* name) { if (prof) prof->mark(name); };
+  hipError_t e = hipMemcpyAsync(L.su_d, L.su_h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  mark("lanes_surround_h2d");
+  LaneSur s;
+  s.pool = b.pool + (size_t)b.pool_cur * b.P * b.map_cap;
+  s.slots = (const int4*)b.slots + (size_t)b.pool_cur * b.P * kCubeNum;
+  s.istate = b.istate;
+  s.vin = b.vin;
+  s.vout = b.vout;
+  s.vseg_b = b.vseg_b; s.vseg_e = b.vseg_e; s.vseg_cnt = b.vseg_cnt; s.vseg_leaf = b.vseg_leaf;
+  s.vg_lin = b.vg_lin;
+  s.vg_counts = b.vg.counts;
+  s.S = L.S;
+  s.map_cap = b.map_cap;
+  hipLaunchKernelGGL(k_lanes_surround, dim3(kSurWg, n), dim3(256), 0, st, s, (const int*)L.su_d, n);
+  mark("k_lanes_surround");
+  // one VoxelGrid over the due lanes' segments (segment id = lane), walked through the list
+  VgJob j = b.vg.job();
+  j.in = b.vin; j.out = b.vout; j.begin = b.vseg_b; j.end = b.vseg_e; j.leaf = b.vseg_leaf;
+  j.out_count = b.vseg_cnt; j.nseg = n; j.total = b.P * b.map_cap;
+  j.zeroed = true;  // (by k_lanes_surround)
+  j.list = b.vg_lin; j.list_n = b.vg.counts + 2;
+  e = vg_route_surround(j, st);
+  if (e != hipSuccess) return e;
+  mark("vg_lanes_surround");
+  if (pack) {
+    hipLaunchKernelGGL(k_lanes_surround_pack, dim3(kSurWg, n), dim3(256), 0, st, s, (const int*)L.su_d);
+    mark("k_lanes_surround_pack");
+  }
+  e = hipGetLastError();
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(L.su_h + L.S, b.vseg_cnt, (size_t)L.S * sizeof(int), hipMemcpyDeviceToHost, st);
+  mark("lanes_surround_counts_d2h");
+  return e;
+}
 
 hipError_t lanes_map_import_alloc(Lanes& L) {
   if (L.mi_h) return hipSuccess;
@@ -444,6 +608,8 @@ void lanes_free(Lanes& L) {
   if (L.rs_d) (void)hipFree(L.rs_d);
   if (L.mi_h) (void)hipHostFree(L.mi_h);
   if (L.mi_d) (void)hipFree(L.mi_d);
+  if (L.su_h) (void)hipHostFree(L.su_h);
+  if (L.su_d) (void)hipFree(L.su_d);
   L = Lanes();
 }
 

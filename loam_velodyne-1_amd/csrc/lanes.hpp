@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "engine.hpp"
@@ -41,11 +42,16 @@ struct LanesImu {
   size_t up_bytes = 0;               // what the last IMU step uploaded
 };
 
+// LaneLife::due: set where the pushed step wraps the lane's phase (kDuePushed), confirmed by the pull
+// against the lane's status (kDueYes: what loam_lanes_surround serves), dropped by the next push, by
+// loam_lanes_restart and by loam_lanes_map_import
+enum { kDueNo = 0, kDuePushed, kDueYes };
 // a lane's own life cycle (loam_lanes_restart); the host owns it
 struct LaneLife {
   int wait = -1;   // -1: the lane follows the shared counters; >= 0: restarted, its init frame is the step after `wait` more
   int kind = 0;    // the step in flight: kLaneRuns, kLaneWaits (an empty problem, LOAM_E_NOT_READY) or kLaneInits
   int phase = 4;   // laserMapping's mapFrameCount of this lane (loam_lanes_map_export's surround_phase)
+  int due = kDueNo;  // /laser_cloud_surround of the lane's last frame (loam_lanes_surround)
 };
 enum { kLaneRuns = 0, kLaneWaits, kLaneInits };
 // words of loam_lanes_map_import's block: centre[3], Bef[6], then the list and the poses
@@ -80,6 +86,10 @@ struct Lanes {
   // the n lane indices, then their n Aft poses of 6 floats (kMi*)
   int* mi_h = nullptr;         // pinned [kMiList + 7S]
   int* mi_d = nullptr;         // device [kMiList + 7S]
+  // loam_lanes_surround's lists of a call (allocated by the first call): the due lanes up, every
+  // lane's VoxelGrid output count down
+  int* su_h = nullptr;         // pinned [2S]: the due list, then the counts by lane
+  int* su_d = nullptr;         // device [S]: the due list
   // the protocol: a step pushed and not yet pulled; what that step published; whether the last
   // pulled step left registered clouds
   bool in_flight = false, step_ran = false, have_reg = false;
@@ -148,6 +158,21 @@ hipError_t lanes_map_import_alloc(Lanes& L);
 // of L.mi_d's block, and writes each lane's centre, Aft and Bef from that block.  src and table are
 // not part of any lane's live data.
 hipError_t lanes_map_install(Lanes& L, const float4* src, int kept, const int* table, int n, hipStream_t st);
+
+
+// the surround lists' buffers (the first loam_lanes_surround)
+hipError_t lanes_surround_alloc(Lanes& L);
+// /laser_cloud_surround of the n due lanes listed in L.su_h (ascending): the list's upload,
+// k_lanes_surround (each lane's 5x5x5 cube neighbourhood gathered from its current pool into its part
+// of vin, its VoxelGrid segment and list entry), one VoxelGrid over the listed segments (lane l's
+// output at vout + l * map_cap, its count at vseg_cnt[l]), with `pack` k_lanes_surround_pack (the
+// outputs back to back in list order from vin[0] on), and every lane's count into L.su_h + S.  The
+// caller synchronises st, then reads the counts (lanes_surround_count).  Only scratch is written.
+hipError_t lanes_surround_run(Lanes& L, int n, bool pack, hipStream_t st, Prof* prof);
+// a lane's output count as the pack kernel reads it
+inline int lanes_surround_count(const Lanes& L, int lane) {
+  return std::min(std::max(L.su_h[L.S + lane], 0), L.mp.map_cap);
+}
 
 }  // namespace loam
 #endif

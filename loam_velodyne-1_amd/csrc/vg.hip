@@ -880,8 +880,12 @@ hipError_t vg_route_cubes(VgJob jv, hipStream_t st, int P, int vg_merge, const i
   return vg_run<kVgCubes>(jv, st, P <= 4 ? 12288 : 2048);
 }
 
-// the surround map (:1042-1047): one segment
-hipError_t vg_route_surround(const VgJob& j, hipStream_t st) { return vg_run<kVgSurround>(j, st, 12288); }
+// the surround map (:1042-1047): one segment (a streaming context, the diagnostic hook), or one per
+// due lane through the job's list (loam_lanes_surround); the first tier by the number of segments
+// as the stack and cube routes choose it by P
+hipError_t vg_route_surround(const VgJob& j, hipStream_t st) {
+  return vg_run<kVgSurround>(j, st, j.nseg <= 4 ? 12288 : 2048);
+}
 
 // ---------------------------------------------------------------- scratch
 hipError_t vg_scratch_alloc(VgScratch& s, size_t sort_points, size_t segments, int split_parents,

@@ -104,6 +104,7 @@ hipError_t vg_route_stack(const VgJob& js, hipStream_t st, int P, int stack_max,
                           const VgSplit* vgs);
 hipError_t vg_route_cubes(VgJob jv, hipStream_t st, int P, int vg_merge, const int* nold, const int* mlist,
                           const int* mlist_n, int* skip);
+// (the surround map: one segment, or the due lanes' segments through j.list; first tier by j.nseg)
 hipError_t vg_route_surround(const VgJob& j, hipStream_t st);
 
 }  // namespace loam

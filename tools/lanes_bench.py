@@ -3,7 +3,7 @@ stepped by loam_chain_sweep from one thread, through the C-ABI on one GPU (DESIG
 
   python tools/lanes_bench.py [--s 1,16,64] [--sweeps 27] [--map-cap 131072] [--yard-max 1024]
                               [--profile-s 64] [--imu] [--restart K,M] [--occupancy N] [--map-import N]
-                              [--out FILE]
+                              [--surround] [--out FILE]
 
 Per S: S lanes over eight distinct VLP-16 synthetic streams laid out cyclically.  The wall time of
 lanes_step (push + pull), and of the push alone (host packing + enqueue), median and range over the
@@ -42,7 +42,20 @@ loam_map_import (scaled by S / contexts when fewer).  Every figure is a median w
 seven calls after two warm-up calls; the sides alternate call by call.  Then the same calls under
 loam_set_profiling for the device time per launch of every import kernel, k_lanes_map_install's
 bytes written (n kept 16 + n 4851 16) over its device time, and a hipMemcpyDtoD of as many bytes
-timed with events in the same process (median of seven after two warm-up copies)."""
+timed with events in the same process (median of seven after two warm-up copies).
+
+--surround (instead of the above): per S, S lanes over 23 sweeps (system_delay = 1:
+sweep 22 is the 11th mapping frame, on which every lane publishes /laser_cloud_surround), then the
+wall time of one loam_lanes_surround call with room for every lane's cloud, the median and range of
+seven calls after two warm-up calls.  The baseline in the same process: min(S, --yard-max) streaming
+contexts that hold the same maps and are due on the same frame (each was fed its lane's sweeps
+through loam_chain_sweep for the odometry's state, received loam_map_import of its lane's export in
+front of the last sweep and then ran that one mapping frame), each calling loam_mapping_surround
+one after the other into its own preallocated array, timed the same way, the sides alternating call
+by call.  Both sides go through ctypes with nothing allocated
+inside the timed region.  Every lane's cloud is compared with its context's bit for bit.  Then
+seven more calls of loam_lanes_surround under loam_set_profiling for its device time per call and
+kernel (loam_mapping_surround records none)."""
 import argparse
 import importlib
 import json
@@ -367,6 +380,81 @@ def run_map_import(S, maps, map_cap, yard_max, reps=7, warm=2):
     return out
 
 
+def run_surround(S, streams, map_cap, yard_max, reps=7, warm=2):
+    """one JSON line: see the module text"""
+    import ctypes
+    K = 23
+    L = loam.lib()
+    ny = min(S, yard_max)
+    eng = loam.Engine(loam.default_config(system_delay=1))
+    eng.lanes_open(S, map_cap)
+    yard = []
+    for _ in range(ny):
+        e = loam.Engine(loam.default_config(system_delay=1, map_capacity=map_cap))
+        e.set_tuning(batch_streams=0)
+        yard.append(e)
+    for k in range(K):
+        if k == K - 1:  # each context takes its lane's map (surround_phase 4 here) in front of the last frame
+            for l, e in enumerate(yard):
+                m = eng.lanes_map_export(l)
+                if m["surround_phase"] != 4:
+                    raise RuntimeError("the last frame is not the lanes' publishing frame")
+                e.map_import(**{f: m[f] for f in ("corner", "surf", "center", "surround_phase", "aft", "bef")})
+        o = eng.lanes_step([streams[l % N_STREAMS][k] for l in range(S)], stamp=0.1 * k)
+        for l, e in enumerate(yard):
+            e.chain_sweep(streams[l % N_STREAMS][k], stamp=0.1 * k)
+    if not (np.all(o["status"] == 0) and np.all(o["mapped"] == 1)):
+        raise RuntimeError("the last step did not map every lane")
+    ref = eng.lanes_surround()
+    if any(c is None for c in ref):
+        raise RuntimeError("a lane is not due on the last step")
+    total = sum(c.shape[0] for c in ref)
+    pts = np.zeros((total, 4), np.float32)
+    off = np.zeros(S + 1, np.uint32)
+    pub = np.zeros(S, np.int32)
+    lc = loam.LanesCloud(pts.ctypes.data, total, 0, off.ctypes.data, pub.ctypes.data)
+    outs = [np.zeros((ref[l].shape[0], 4), np.float32) for l in range(ny)]
+    cos = [loam.CloudOut(a.ctypes.data, 0, a.shape[0]) for a in outs]
+    flag = ctypes.c_int(0)
+
+    def lanes_call():
+        if L.loam_lanes_surround(eng.h, ctypes.byref(lc)) != 0:
+            raise RuntimeError(L.loam_last_error().decode())
+
+    def contexts_call():
+        for e, c in zip(yard, cos):
+            if L.loam_mapping_surround(e.h, ctypes.byref(c), ctypes.byref(flag)) != 0 or not flag.value:
+                raise RuntimeError("a context did not publish: " + L.loam_last_error().decode())
+
+    wall = {"lanes": [], "contexts": []}
+    for r in range(warm + reps):
+        for key, f in (("lanes", lanes_call), ("contexts", contexts_call)):
+            t0 = time.perf_counter()
+            f()
+            if r >= warm:
+                wall[key].append((time.perf_counter() - t0) * 1e3)
+    same = all(np.array_equal(pts[off[l]:off[l + 1]].view(np.uint32), outs[l].view(np.uint32)) for l in range(ny))
+    # (loam_mapping_surround records no per-kernel times: the lanes' call alone)
+    eng.set_profiling(True)
+    for _ in range(reps):
+        lanes_call()
+    dev = {k: round(v[0] / reps, 4) for k, v in sorted(eng.kernel_times().items()) if v[1]}
+    eng.set_profiling(False)
+    for e in yard:
+        e.close()
+    eng.lanes_close()
+    eng.close()
+    line = dict(surround=True, S=S, map_cap=map_cap, sweeps=K, points_out=int(total),
+                points_out_per_lane=[int(min(c.shape[0] for c in ref)), int(max(c.shape[0] for c in ref))],
+                contexts=ny, contexts_scaled=ny != S, lanes_equal_contexts=bool(same),
+                wall_ms={k: spread(v) for k, v in wall.items()}, device_ms_per_call=dev)
+    lm, cm = line["wall_ms"]["lanes"], line["wall_ms"]["contexts"]
+    line["contexts_over_lanes"] = round(cm["median"] * (S / ny) / lm["median"], 2)
+    # the call beats the serial contexts by more than the spread of the repetitions
+    line["lanes_max_below_contexts_min"] = bool(lm["max"] < cm["min"] * (S / ny))
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--s", default="1,16,64")
@@ -378,9 +466,10 @@ def main():
     ap.add_argument("--restart", default=None, help="K,M: restart K lanes (0: S / 4) before every M-th step")
     ap.add_argument("--occupancy", type=int, default=0, help="recordings of 10..40 sweeps over 16 lanes")
     ap.add_argument("--map-import", type=int, default=0, help="points of the synthetic map (and the stream map)")
+    ap.add_argument("--surround", action="store_true", help="loam_lanes_surround against serial contexts")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    K = 40 if a.occupancy else a.sweeps
+    K = 40 if a.occupancy else 23 if a.surround else a.sweeps
     streams = [sg.stream_sweeps(K, 1 + i) for i in range(N_STREAMS)]
     imu = imu_schedules(K) if a.imu else None
     pts = int(np.mean([sw.shape[0] for sw in streams[0]]))
@@ -397,6 +486,10 @@ def main():
 
     if a.occupancy:
         emit(run_occupancy(a.occupancy, streams, a.map_cap))
+        return
+    if a.surround:
+        for S in [int(v) for v in a.s.split(",") if v]:
+            emit(run_surround(S, streams, a.map_cap, a.yard_max))
         return
     if a.map_import:
         e = loam.Engine(loam.default_config(system_delay=1))
