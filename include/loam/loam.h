@@ -562,6 +562,59 @@ typedef struct {
  * call: the scratch is the lanes' own VoxelGrid input / output arrays, idle between a pull and the
  * next push (loam_lanes_map_export uses them the same way). */
 int loam_lanes_surround(loam_ctx *ctx, loam_lanes_cloud *out);
+
+/* ---- shared lanes: every lane localizes in the context's one map, which a step only reads ----
+ * Opens n_lanes lanes whose laserMapping refines against the context's streaming map (the store
+ * loam_map_import / loam_mapping / loam_chain_sweep maintain), which a lanes step only reads.
+ * No per-lane store exists.  lane_from_capacity = FromMap points one lane may gather per frame
+ * (the points of its FOV-tested 5 x 5 x 5 valid cubes; 48 bytes each and 24 per hash bucket, DESIGN.md
+ * §30, against 152 per point of lane_map_capacity).
+ * Scan registration, the odometry, the IMU queues, the restart phase rule and every call not named
+ * below work as on loam_lanes_open's lanes.  A context holds one set of lanes of one mode at a time.
+ * A lane's mapping frame.  Let M be the context's map as loam_map_export would give it at the push
+ * and (Aft, Bef) the lane's poses before the step.  The lane's aft, bef, mp_iters and registered
+ * cloud are, bit for bit and in point order, what loam_mapping returns on a context that has just
+ * received loam_map_import(M with aft = Aft, bef = Bef), has received the lane's IMU messages, and is
+ * given the lane's od_sum, corner_last, surf_last and full_end.  Nothing is inserted, downsampled,
+ * compacted or recentred: no bit of the map, its grid centre or the context's own Bef / Aft changes.
+ *   - A lane whose centre cube is within 3 of a grid edge (a sequential frame would recentre the
+ *     grid first) is not evaluated: mapped = 1, mp_iters = 0, n_registered = 0, Aft / Bef as they
+ *     were, LOAM_LOC_OFFGRID in loam_lanes_localize_info.  Remedy: loam_map_import with another centre.
+ *   - LOAM_LOC_NO_LM is the reference's own branch (src/laserMapping.cpp:706): the poses are left
+ *     alone and the cloud is registered with transformTobeMapped.
+ *   - A lane whose valid cubes hold more than lane_from_capacity points fails with the sticky
+ *     LOAM_E_CAPACITY (found on the device: a push waits for nothing); no other lane is affected.  A
+ *     map whose last update overflowed map_capacity fails every lane's mapping frame the same way.
+ * The map may change between steps: loam_map_import, loam_mapping and loam_chain_sweep on this
+ * context are allowed whenever no step is in flight, and the next step reads the store they left
+ * (it waits on the device for a deferred map update).  One context can keep mapping while its lanes
+ * localize in that map.
+ * loam_lanes_map_import, loam_lanes_map_export and loam_lanes_surround are LOAM_E_INVAL on shared
+ * lanes (there is no lane map): use loam_map_import, loam_map_export and loam_mapping_surround.
+ * Errors: loam_lanes_open's, with lane_from_capacity in [1024, 2^28] and the 2^31 limits on n_lanes
+ * x lane_from_capacity and n_lanes x (max_points + 120 n_rings).  LOAM_E_NOMEM frees everything. */
+int loam_lanes_open_shared(loam_ctx *ctx, uint32_t n_lanes, uint32_t lane_from_capacity);
+
+/* Aft / Bef of the listed lanes (bef NULL = zeros), between two steps; shared lanes only.  One
+ * kernel launch writes every listed lane's poses.  The two uses:
+ *   - at start or after a restart: bef = zeros, aft = the guess of the lane's pose in the map;
+ *   - re-seeding a running lane (a better pose from loam_map_localize / loam_map_score): bef = the
+ *     lane's last od_sum, so that only later odometry increments are applied on top of aft.
+ * LOAM_E_INVAL, and nothing changes in any lane: a null ctx / lane / aft, lanes not open or opened
+ * with loam_lanes_open, a step in flight, n == 0 or n > n_lanes, a lane index >= n_lanes, a lane
+ * listed twice, a failed lane, a lane between loam_lanes_restart and the pull of its init step (the
+ * restart's deferred clear would overwrite the pose).  LOAM_E_NOMEM when the first call's allocation
+ * (two blocks of 13 n_lanes words) fails. */
+int loam_lanes_set_pose(loam_ctx *ctx, uint32_t n, const uint32_t *lane, const loam_pose6 *aft, const loam_pose6 *bef);
+
+/* loam_localize_result of every lane's mapping frame of the last pulled step; shared lanes only.
+ * For a lane without IMU messages out[l] equals, field for field, loam_map_localize(n = 1, aft =
+ * Aft, bef = Bef) with the lane's od_sum, corner_last and surf_last on a context holding M.
+ * LOAM_LOC_NONE with zeros: the lane ran no mapping frame on that step (a step that did not map,
+ * a wait or init step of a restarted lane, inside system_delay) or has failed.
+ * LOAM_E_INVAL: a null argument, lanes not open or not shared, a step in flight, before the first pull. */
+#define LOAM_LOC_NONE (LOAM_LOC_OFFGRID + 1)   /* = 3, behind loam_map_localize's statuses: the lane ran no mapping frame on that step */
+int loam_lanes_localize_info(loam_ctx *ctx, loam_localize_result *out /* [n_lanes] */);
 /* Frees the lanes' working set (waits for a step in flight).  LOAM_E_INVAL when not open. */
 int loam_lanes_close(loam_ctx *ctx);
 

@@ -150,6 +150,9 @@ class LocalizeResult(ctypes.Structure):
 
 
 LOCALIZE_KEYS = tuple(n for n, _ in LocalizeResult._fields_)
+LOC_NONE = 3  # LOAM_LOC_NONE (loam_lanes_localize_info): the lane ran no mapping frame on that step
+_LOC_DTYPE = np.dtype([(n, np.float32, (6,)) if t is Pose6 else (n, np.uint32 if t is ctypes.c_uint32 else np.int32)
+                       for n, t in LocalizeResult._fields_])
 
 SCORE_MAX = 65536  # LOAM_SCORE_MAX: poses of one loam_map_score call
 
@@ -193,6 +196,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_lanes_open", "loam_lanes_push", "loam_lanes_pull", "loam_lanes_registered", "loam_lanes_map_export",
            "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
            "loam_lanes_restart", "loam_lanes_map_import", "loam_lanes_surround",
+           "loam_lanes_open_shared", "loam_lanes_set_pose", "loam_lanes_localize_info",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -254,6 +258,9 @@ def lib():
         L.loam_lanes_map_import.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), P(Map), P(Pose6),
                                             P(ctypes.c_uint64)]
         L.loam_lanes_surround.argtypes = [PP, P(LanesCloud)]
+        L.loam_lanes_open_shared.argtypes = [PP, ctypes.c_uint32, ctypes.c_uint32]
+        L.loam_lanes_set_pose.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), P(Pose6), P(Pose6)]
+        L.loam_lanes_localize_info.argtypes = [PP, P(LocalizeResult)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -662,6 +669,42 @@ class Engine:
             c.pts, c.capacity = pts.ctypes.data, pts.shape[0]
             _check(lib().loam_lanes_surround(self.h, ctypes.byref(c)))
         return [pts[off[l]:off[l + 1]].copy() if pub[l] else None for l in range(S)]
+
+    def lanes_open_shared(self, n, from_capacity):
+        """n lanes that localize in this context's own map, which their steps only read
+        (loam_lanes_open_shared): no lane holds a map; from_capacity = the map points one lane's
+        frame may gather from its valid cubes.  map_import / mapping / chain_sweep on this Engine
+        change the map between steps; lanes_set_pose gives a lane its pose in it."""
+        _check(lib().loam_lanes_open_shared(self.h, int(n), int(from_capacity)))
+        self.n_lanes = int(n)
+
+    def lanes_set_pose(self, lanes, aft, bef=None):
+        """Aft / Bef of the listed shared lanes between two steps (loam_lanes_set_pose): aft one pose
+        or an [n, 6] array of one per listed lane, bef likewise (None = zeros).  At start or after
+        a restart: bef = None, aft = the pose guess.  Re-seeding a running lane: bef = the lane's
+        last od_sum, aft = the better pose."""
+        lanes = [int(l) for l in np.atleast_1d(lanes)]
+        n = len(lanes)
+        P = ctypes.POINTER(Pose6)
+
+        def poses(v):
+            a = np.ascontiguousarray(v, np.float32)
+            a = np.ascontiguousarray(np.broadcast_to(a, (n, 6))) if a.ndim == 1 else a
+            if a.shape != (n, 6):
+                raise ValueError("one pose, or one pose per listed lane ([n, 6])")
+            return a
+        a = poses(aft)
+        b = None if bef is None else poses(bef)
+        idx = (ctypes.c_uint32 * max(n, 1))(*lanes)
+        _check(lib().loam_lanes_set_pose(self.h, n, idx, a.ctypes.data_as(P), None if b is None else b.ctypes.data_as(P)))
+
+    def lanes_localize_info(self):
+        """every shared lane's mapping frame of the last pulled step as map_localize reports a
+        candidate (loam_lanes_localize_info): a structured array of n_lanes records with
+        LOCALIZE_KEYS' fields; status LOC_NONE (and zeros) where the lane ran no mapping frame"""
+        rec = np.zeros(self.n_lanes, _LOC_DTYPE)
+        _check(lib().loam_lanes_localize_info(self.h, rec.ctypes.data_as(ctypes.POINTER(LocalizeResult))))
+        return rec
 
     def lanes_close(self):
         _check(lib().loam_lanes_close(self.h))

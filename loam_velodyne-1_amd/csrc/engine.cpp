@@ -2383,7 +2383,9 @@ hipError_t lanes_enqueue(loam_ctx* x, Prof* pf, bool imu, int n_init) {
       in.ncorner = o.nlast + nxt * 2; in.nsurf = o.nlast + nxt * 2 + 1; in.nfull = o.nfullEnd + nxt;
       in.ncorner_stride = in.nsurf_stride = 2 * kOdBufs; in.nfull_stride = kOdBufs;
       in.pose = o.state + kOdSum; in.pose_stride = kOdStateFloats;
-      mp_frame(L.mp, in, st, pf);
+      // shared lanes: loam_map_localize's sequence over the lanes against the context's store, read only
+      if (L.shared) mp_lanes_shared_frame(L.mp, x->mp1, in, L.loc_d, st, pf);
+      else mp_frame(L.mp, in, st, pf);
       L.step_mapped = 1;
       for (int l = 0; l < S; ++l)  // :1038-1040, for the lanes this was a mapping frame for
         if (L.life[l].kind == kLaneRuns && ++L.life[l].phase >= 5) {
@@ -2396,7 +2398,7 @@ hipError_t lanes_enqueue(loam_ctx* x, Prof* pf, bool imu, int n_init) {
       }
     }
   }
-  T(lanes_out(L, st));
+  T(lanes_out(L, st, L.shared && L.step_mapped));
   x->prof.mark("k_lanes_out");
   T(hipGetLastError());
   return e;
@@ -2426,6 +2428,83 @@ extern "C" int loam_lanes_open(loam_ctx* x, uint32_t n_lanes, uint32_t lane_map_
   Lanes& L = x->lanes;
   L.od.tune = L.mp.tune = lanes_tuning(x->tune);
   L.od_frame_count = (int)x->cfg.skip_frame_num;  // frameCount = skipFrameNum (src/laserOdometry.cpp:407)
+  return LOAM_OK;
+}
+
+// Shared lanes (loam.h): the lanes' mapping working set holds no store, a mapping
+// step reads x->mp1's.
+extern "C" int loam_lanes_open_shared(loam_ctx* x, uint32_t n_lanes, uint32_t lane_from_capacity) {
+  if (!x) return fail(LOAM_E_INVAL, "null argument");
+  const std::string who = "loam_lanes_open_shared";
+  if (x->lanes.S) return fail(LOAM_E_INVAL, who + ": lanes are open (loam_lanes_close first)");
+  const uint64_t cap_stack = (uint64_t)x->cap + (uint64_t)kLessSharpPerRing * x->R;
+  switch (lanes_shared_check(n_lanes, lane_from_capacity, cap_stack)) {
+    case kSharedLanes: return fail(LOAM_E_INVAL, who + ": n_lanes must be in [1, LOAM_LANES_MAX]");
+    case kSharedFromCap: return fail(LOAM_E_INVAL, who + ": lane_from_capacity must be in [1024, 2^28] points");
+    case kSharedFromProduct: return fail(LOAM_E_INVAL, who + ": n_lanes x lane_from_capacity reaches 2^31 points");
+    case kSharedStackProduct:
+      return fail(LOAM_E_INVAL, who + ": n_lanes x stack capacity (max_points + 120 n_rings) reaches 2^31 points");
+    default: break;
+  }
+  HIP_TRY(hipSetDevice(x->device));
+  const hipError_t he = lanes_alloc(x->lanes, (int)n_lanes, x->cap, x->R, (int)lane_from_capacity,
+                                    (int)x->cfg.od_max_iter, (int)x->cfg.mp_max_iter, /*shared=*/true);
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LOAM_E_NOMEM, who + ": allocation failed: " + hipGetErrorString(he));
+  }
+  Lanes& L = x->lanes;
+  L.od.tune = L.mp.tune = lanes_tuning(x->tune);
+  L.od_frame_count = (int)x->cfg.skip_frame_num;  // frameCount = skipFrameNum (src/laserOdometry.cpp:407)
+  return LOAM_OK;
+}
+
+extern "C" int loam_lanes_set_pose(loam_ctx* x, uint32_t n, const uint32_t* lane, const loam_pose6* aft,
+                                   const loam_pose6* bef) {
+  if (!x || !lane || !aft) return fail(LOAM_E_INVAL, "null argument");
+  const std::string who = "loam_lanes_set_pose";
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
+  if (!L.shared) return fail(LOAM_E_INVAL, who + ": the lanes have their own maps (loam_lanes_open); use loam_lanes_map_import");
+  if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
+  if (n == 0 || n > (uint32_t)L.S) return fail(LOAM_E_INVAL, who + ": n must be in [1, n_lanes]");
+  std::vector<char> seen;
+  uint32_t bad = 0;
+  const int why = lanes_list_check(lane, n, L.S, L.fail.data(), L.life.data(), seen, &bad);
+  if (why != kLaneListOk) {
+    const std::string at = who + ": lane[" + std::to_string(bad) + "] = " + std::to_string(lane[bad]);
+    if (why == kLaneListRange) return fail(LOAM_E_INVAL, at + " is out of range");
+    if (why == kLaneListTwice) return fail(LOAM_E_INVAL, at + " is listed twice");
+    if (why == kLaneListFailed) return fail(LOAM_E_INVAL, at + " has failed (loam_lanes_restart first)");
+    return fail(LOAM_E_INVAL, at + " waits for its init step (the restart's clear would overwrite the pose)");
+  }
+  HIP_TRY(hipSetDevice(x->device));
+  if (lanes_set_pose_alloc(L) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LOAM_E_NOMEM, who + ": allocation failed");
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    L.sp_h[i] = (int)lane[i];
+    std::memcpy(L.sp_h + n + (size_t)i * 12, &aft[i], sizeof(loam_pose6));
+    if (bef) std::memcpy(L.sp_h + n + (size_t)i * 12 + 6, &bef[i], sizeof(loam_pose6));
+    else std::memset(L.sp_h + n + (size_t)i * 12 + 6, 0, sizeof(loam_pose6));
+  }
+  hipError_t he = lanes_set_pose(L, (int)n, x->st);
+  const hipError_t se = hipStreamSynchronize(x->st);
+  if (he == hipSuccess) he = se;
+  if (he != hipSuccess) return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
+  return LOAM_OK;
+}
+
+extern "C" int loam_lanes_localize_info(loam_ctx* x, loam_localize_result* out) {
+  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
+  const std::string who = "loam_lanes_localize_info";
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
+  if (!L.shared) return fail(LOAM_E_INVAL, who + ": the lanes have their own maps (loam_lanes_open)");
+  if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
+  if (!L.pulled) return fail(LOAM_E_INVAL, who + ": no step was pulled");
+  std::memcpy(out, L.loc_info.data(), (size_t)L.S * sizeof(loam_localize_result));
   return LOAM_OK;
 }
 
@@ -2627,6 +2706,13 @@ extern "C" int loam_lanes_restart(loam_ctx* x, uint32_t lane, uint32_t* wait_ste
       HIP_TRY(lanes_restart_clear(L, L.mi_d + kMiList, 1, kClearMp, x->st));
       HIP_TRY(hipStreamSynchronize(x->st));
     }
+    if (L.sp_h) {  // ... and for the poses a loam_lanes_set_pose may have put there (shared lanes)
+      HIP_TRY(hipSetDevice(x->device));
+      L.sp_h[0] = (int)lane;
+      HIP_TRY(hipMemcpyAsync(L.sp_d, L.sp_h, sizeof(int), hipMemcpyHostToDevice, x->st));
+      HIP_TRY(lanes_restart_clear(L, L.sp_d, 1, kClearMp, x->st));
+      HIP_TRY(hipStreamSynchronize(x->st));
+    }
   }
   f.phase = 4;  // mapFrameCount = mapFrameNum - 1 (src/laserMapping.cpp:405)
   f.due = kDueNo;
@@ -2665,6 +2751,12 @@ extern "C" int loam_lanes_pull(loam_ctx* x, loam_lane_out* out) {
   if (!L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_pull: no step was pushed");
   const int S = L.S;
   L.imu_trans.assign((size_t)S * 12, 0.0f);
+  if (L.shared) {  // (LOAM_LOC_NONE with zeros until a lane's mapping frame is found below)
+    loam_localize_result none;
+    std::memset(&none, 0, sizeof(none));
+    none.status = LOAM_LOC_NONE;
+    L.loc_info.assign((size_t)S, none);
+  }
   if (!L.step_ran) {  // inside system_delay: nothing was enqueued
     L.in_flight = false;
     L.pulled = true;
@@ -2717,6 +2809,20 @@ extern "C" int loam_lanes_pull(loam_ctx* x, loam_lane_out* out) {
       L.nreg[l] = q.n_registered;
       // laserMapping's queue pointer walks inside transformUpdate, i.e. only when the L-M ran
       if (L.imu.step_imu && L.imu.mp_have[l] && w[kLoLmRan]) L.imu.mp[l].front = L.imu.mp_front[l];
+      if (L.shared) {
+        const int* r = L.loc_h + (size_t)l * kLocResWords;
+        loam_localize_result& o = L.loc_info[l];
+        std::memcpy(&o.aft, r + kLrAft, sizeof(loam_pose6));
+        o.status = r[kLrStatus];
+        o.iters = r[kLrIters];
+        o.degenerate_steps = r[kLrDegSteps];
+        o.rows_last = (uint32_t)r[kLrRowsLast];
+        o.rows_sum = (uint32_t)r[kLrRowsSum];
+        o.stack_corner = (uint32_t)r[kLrStackC];
+        o.stack_surf = (uint32_t)r[kLrStackS];
+        o.map_corner = (uint32_t)r[kLrMapC];
+        o.map_surf = (uint32_t)r[kLrMapS];
+      }
     }
     if (L.imu.step_imu) std::memcpy(&L.imu_trans[(size_t)l * 12], L.imu.trans_h + (size_t)l * 12, 12 * sizeof(float));
   }
@@ -2752,6 +2858,8 @@ extern "C" int loam_lanes_map_export(loam_ctx* x, uint32_t lane, loam_map* out) 
   if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
   Lanes& L = x->lanes;
   if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_map_export: lanes are not open");
+  if (L.shared)
+    return fail(LOAM_E_INVAL, "loam_lanes_map_export: shared lanes have no lane map (loam_map_export gives the context's)");
   if (lane >= (uint32_t)L.S) return fail(LOAM_E_INVAL, "loam_lanes_map_export: lane index out of range");
   if (L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_map_export: a step is in flight (loam_lanes_pull first)");
   if (L.fail[lane] != LOAM_OK) return fail(LOAM_E_INVAL, "loam_lanes_map_export: the lane has failed");
@@ -2770,6 +2878,9 @@ extern "C" int loam_lanes_map_import(loam_ctx* x, uint32_t n, const uint32_t* la
   const std::string who = "loam_lanes_map_import";
   Lanes& L = x->lanes;
   if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
+  if (L.shared)
+    return fail(LOAM_E_INVAL, who + ": shared lanes have no lane map (loam_map_import changes the context's, "
+                                    "loam_lanes_set_pose a lane's poses)");
   if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
   if (n == 0 || n > (uint32_t)L.S) return fail(LOAM_E_INVAL, who + ": n must be in [1, n_lanes]");
   std::vector<char> seen;
@@ -2839,6 +2950,8 @@ extern "C" int loam_lanes_surround(loam_ctx* x, loam_lanes_cloud* out) {
   if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
   Lanes& L = x->lanes;
   if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_surround: lanes are not open");
+  if (L.shared)
+    return fail(LOAM_E_INVAL, "loam_lanes_surround: shared lanes have no lane map (loam_mapping_surround gives the context's)");
   if (L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_surround: a step is in flight (loam_lanes_pull first)");
   const int S = L.S;
   int n = 0;

@@ -12,10 +12,12 @@ struct LaneOutSrc {
   const float* mp_state;  // [S][kMpStateFloats]
   const int* mp_istate;   // [S][kMpStateInts]
   const int* nreg;        // [S]
+  const int* loc;         // [S][kLocResWords] shared lanes on a mapping step, else null
 };
 
 // 32 lanes of a wave per lane of the step, one word each: the three error words, the two iteration
 // counts, the registered cloud's size, transformSum, Aft, Bef, and whether mapping's L-M ran
+// (shared lanes: a lane whose result block says LOAM_LOC_OFFGRID was not evaluated and registers nothing)
 __global__ __launch_bounds__(256) void k_lanes_out(LaneOutSrc s, int* out, int S) {
   const int gid = blockIdx.x * 256 + threadIdx.x;
   const int l = gid >> 5, w = gid & 31;
@@ -28,7 +30,7 @@ __global__ __launch_bounds__(256) void k_lanes_out(LaneOutSrc s, int* out, int S
   else if (w == kLoMpErr) v = mi[kMiErr];
   else if (w == kLoOdIters) v = oi[kIsIters];
   else if (w == kLoMpIters) v = mi[kMiIters];
-  else if (w == kLoNReg) v = s.nreg[l];
+  else if (w == kLoNReg) v = s.loc && s.loc[(size_t)l * kLocResWords + kLrStatus] == LOAM_LOC_OFFGRID ? 0 : s.nreg[l];
   else if (w < kLoAft) v = __float_as_int(s.od_state[(size_t)l * kOdStateFloats + kOdSum + (w - kLoOdSum)]);
   else if (w < kLoBef) v = __float_as_int(s.mp_state[(size_t)l * kMpStateFloats + kMpAft + (w - kLoAft)]);
   else if (w == kLoLmRan) v = mi[kMiLmRan];
@@ -136,7 +138,7 @@ __global__ __launch_bounds__(256) void k_lanes_restart(LaneClear c, const int* l
   const int l = list[blockIdx.y];
   if (l < 0 || l >= c.S) return;
   const int tid = threadIdx.x;
-  if (what & kClearMp) {
+  if ((what & kClearMp) && c.slots) {  // (shared lanes have no store: slots is null)
     const int4 z = make_int4(0, 0, 0, 0);
     for (int pool = 0; pool < 2; ++pool) {
       int4* s = c.slots + ((size_t)pool * c.S + l) * kCubeNum;
@@ -197,6 +199,19 @@ __global__ __launch_bounds__(256) void k_lanes_init(OdBuffers b, FeatView f, con
     b.nlast[(p * kOdBufs + dst) * 2 + 1] = cf;
     b.nfullEnd[p * kOdBufs + dst] = 0;
   }
+}
+
+// loam_lanes_set_pose: 16 threads per listed lane, one word each.  blk: the n lane indices, then n
+// x 12 floats (Aft, Bef).  A lane appears once in the list and no word is shared between lanes:
+// plain stores.
+__global__ __launch_bounds__(256) void k_lanes_set_pose(float* mp_state, const int* blk, int n, int S) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  const int i = gid >> 4, w = gid & 15;
+  if (i >= n || w >= 12) return;
+  const int l = blk[i];
+  if (l < 0 || l >= S) return;
+  const float v = reinterpret_cast<const float*>(blk)[n + i * 12 + w];
+  mp_state[(size_t)l * kMpStateFloats + (w < 6 ? kMpAft + w : kMpBef + (w - 6))] = v;
 }
 
 struct LaneMapDst {
@@ -413,6 +428,27 @@ hipError_t lanes_surround_run(Lanes& L, int n, bool pack, hipStream_t st, Prof* 
   return e;
 }
 
+hipError_t lanes_set_pose_alloc(Lanes& L) {
+  if (L.sp_h) return hipSuccess;
+  const size_t bytes = (size_t)13 * L.S * sizeof(int);
+  hipError_t e = hipHostMalloc((void**)&L.sp_h, bytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&L.sp_d, bytes);
+  if (e != hipSuccess) {
+    if (L.sp_h) (void)hipHostFree(L.sp_h);
+    L.sp_h = nullptr;
+    L.sp_d = nullptr;
+  }
+  return e;
+}
+
+hipError_t lanes_set_pose(Lanes& L, int n, hipStream_t st) {
+  if (n <= 0 || n > L.S) return hipErrorInvalidValue;
+  hipError_t e = hipMemcpyAsync(L.sp_d, L.sp_h, (size_t)13 * n * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_lanes_set_pose, dim3((n * 16 + 255) / 256), dim3(256), 0, st, L.mp.state, (const int*)L.sp_d, n, L.S);
+  return hipGetLastError();
+}
+
 hipError_t lanes_map_import_alloc(Lanes& L) {
   if (L.mi_h) return hipSuccess;
   const size_t bytes = ((size_t)kMiList + 7 * (size_t)L.S) * sizeof(int);
@@ -492,10 +528,13 @@ Tuning lanes_tuning(Tuning t) {
   return t;
 }
 
-hipError_t lanes_alloc(Lanes& L, int S, int cap, int R, int map_cap, int od_max_iter, int mp_max_iter) {
+hipError_t lanes_alloc(Lanes& L, int S, int cap, int R, int map_cap, int od_max_iter, int mp_max_iter, bool shared) {
   hipError_t e = sr_alloc(L.sr, S, cap, R);
   if (e == hipSuccess) e = od_alloc(L.od, S, R, cap, od_max_iter);
-  if (e == hipSuccess) e = mp_alloc(L.mp, S, R, cap, map_cap, mp_max_iter);
+  if (e == hipSuccess && !shared) e = mp_alloc(L.mp, S, R, cap, map_cap, mp_max_iter);
+  if (e == hipSuccess && shared) e = mp_alloc_shared(L.mp, S, R, cap, map_cap, mp_max_iter);
+  if (e == hipSuccess && shared) e = hipMalloc((void**)&L.loc_d, (size_t)S * kLocResWords * sizeof(int));
+  if (e == hipSuccess && shared) e = hipHostMalloc((void**)&L.loc_h, (size_t)S * kLocResWords * sizeof(int), hipHostMallocDefault);
   const size_t pts = (size_t)S * cap;
   if (e == hipSuccess) e = hipHostMalloc((void**)&L.stage_h, pts * sizeof(float4), hipHostMallocDefault);
   if (e == hipSuccess) e = hipMalloc((void**)&L.stage_d, pts * sizeof(float4));
@@ -511,6 +550,8 @@ hipError_t lanes_alloc(Lanes& L, int S, int cap, int R, int map_cap, int od_max_
     return e;
   }
   L.S = S;
+  L.shared = shared;
+  L.loc_info.assign(shared ? S : 0, loam_localize_result());
   L.fail.assign(S, LOAM_OK);
   L.fail_new.assign(S, LOAM_OK);
   L.nreg.assign(S, 0);
@@ -610,11 +651,16 @@ void lanes_free(Lanes& L) {
   if (L.mi_d) (void)hipFree(L.mi_d);
   if (L.su_h) (void)hipHostFree(L.su_h);
   if (L.su_d) (void)hipFree(L.su_d);
+  if (L.sp_h) (void)hipHostFree(L.sp_h);
+  if (L.sp_d) (void)hipFree(L.sp_d);
+  if (L.loc_h) (void)hipHostFree(L.loc_h);
+  if (L.loc_d) (void)hipFree(L.loc_d);
   L = Lanes();
 }
 
-hipError_t lanes_out(const Lanes& L, hipStream_t st) {
+hipError_t lanes_out(const Lanes& L, hipStream_t st, bool loc) {
   LaneOutSrc s;
+  s.loc = loc ? L.loc_d : nullptr;
   s.sr_err = L.sr.err;
   s.od_state = L.od.state;
   s.od_istate = L.od.istate;
@@ -625,6 +671,8 @@ hipError_t lanes_out(const Lanes& L, hipStream_t st) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess)
     e = hipMemcpyAsync(L.out_h, L.out_d, (size_t)L.S * kLaneOutWords * sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && loc)
+    e = hipMemcpyAsync(L.loc_h, L.loc_d, (size_t)L.S * kLocResWords * sizeof(int), hipMemcpyDeviceToHost, st);
   return e;
 }
 

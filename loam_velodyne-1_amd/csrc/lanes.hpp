@@ -61,9 +61,12 @@ enum { kClearOd = 1, kClearMp = 2, kClearImu = 4 };
 
 struct Lanes {
   int S = 0;           // 0: not open
+  // loam_lanes_open_shared: mp is a working set without a store (mp_alloc_shared,
+  // mp.map_cap = lane_from_capacity) and a mapping frame reads the context's streaming store
+  bool shared = false;
   SrBuffers sr;        // S sweeps
   OdBuffers od;        // S problems; Last buffers 0 and 1 alternate, as the streaming path's
-  MpBuffers mp;        // S stores
+  MpBuffers mp;        // S stores (shared lanes: S working sets, no store)
   // the step's sweeps: packed back to back in pinned memory, copied to the device staging in
   // chunks, scattered to sr.raw's stride by one kernel (as loam_batch_feed)
   float4* stage_h = nullptr;  // pinned [S * cap]
@@ -90,6 +93,15 @@ struct Lanes {
   // lane's VoxelGrid output count down
   int* su_h = nullptr;         // pinned [2S]: the due list, then the counts by lane
   int* su_d = nullptr;         // device [S]: the due list
+  // loam_lanes_set_pose's block of a call (allocated by the first call): the n lane indices, then
+  // their n (Aft, Bef) pairs of 12 floats
+  int* sp_h = nullptr;         // pinned [13S]
+  int* sp_d = nullptr;         // device [13S]
+  // shared lanes: every lane's k_mp_loc_result block of a mapping step, its pinned copy, and what
+  // loam_lanes_localize_info hands out (filled by the pull)
+  int* loc_d = nullptr;        // device [S][kLocResWords]
+  int* loc_h = nullptr;        // pinned copy
+  std::vector<loam_localize_result> loc_info;  // [S]
   // the protocol: a step pushed and not yet pulled; what that step published; whether the last
   // pulled step left registered clouds
   bool in_flight = false, step_ran = false, have_reg = false;
@@ -106,10 +118,14 @@ struct Lanes {
 // (the persistent one-problem kernels and the per-query moments; loam.h, loam_lanes_open)
 Tuning lanes_tuning(Tuning t);
 // the working set for S lanes (sweeps of cap points, R rings); on failure everything is freed
-hipError_t lanes_alloc(Lanes& L, int S, int cap, int R, int map_cap, int od_max_iter, int mp_max_iter);
+// shared: map_cap is lane_from_capacity and no lane gets a store (Lanes::shared)
+hipError_t lanes_alloc(Lanes& L, int S, int cap, int R, int map_cap, int od_max_iter, int mp_max_iter,
+                       bool shared = false);
 void lanes_free(Lanes& L);
 // k_lanes_out: every lane's block into out_d, then its copy into out_h
-hipError_t lanes_out(const Lanes& L, hipStream_t st);
+// loc (shared lanes, a mapping step): the step's k_mp_loc_result blocks are in loc_d: a
+// LOAM_LOC_OFFGRID lane reports no registered point, and the blocks are copied into loc_h
+hipError_t lanes_out(const Lanes& L, hipStream_t st, bool loc = false);
 // the IMU side's buffers (the first loam_lanes_imu); on failure they are freed and imu.on stays false
 hipError_t lanes_imu_alloc(Lanes& L);
 void lanes_imu_free(Lanes& L);
@@ -150,6 +166,24 @@ inline int lanes_list_check(const uint32_t* lane, uint32_t n, int S, const int* 
   }
   return kLaneListOk;
 }
+
+// loam_lanes_open_shared's capacity arithmetic (host only): LOAM_OK, or which limit the arguments
+// break.  cap_stack = max_points + 120 n_rings; the products are the int bases of the lanes' FromMap
+// and stack segments (VgJob::total, MpBuffers' strides)
+enum { kSharedOk = 0, kSharedLanes, kSharedFromCap, kSharedFromProduct, kSharedStackProduct };
+inline int lanes_shared_check(uint32_t n_lanes, uint32_t from_cap, uint64_t cap_stack) {
+  if (n_lanes == 0 || n_lanes > LOAM_LANES_MAX) return kSharedLanes;
+  if (from_cap < 1024 || from_cap > (1u << 28)) return kSharedFromCap;
+  if ((uint64_t)n_lanes * from_cap >= ((uint64_t)1 << 31)) return kSharedFromProduct;
+  if ((uint64_t)n_lanes * cap_stack >= ((uint64_t)1 << 31)) return kSharedStackProduct;
+  return kSharedOk;
+}
+
+// the set-pose block's buffers (the first loam_lanes_set_pose)
+hipError_t lanes_set_pose_alloc(Lanes& L);
+// k_lanes_set_pose: one launch that writes Aft and Bef of the n lanes of L.sp_h's block (uploaded
+// here) into their mapping state; the caller synchronises st before it refills the block
+hipError_t lanes_set_pose(Lanes& L, int n, hipStream_t st);
 
 // the import lists' buffers (the first loam_lanes_map_import)
 hipError_t lanes_map_import_alloc(Lanes& L);

@@ -242,6 +242,13 @@ struct LocStore {
 // of the reference's `while` loops, :454-614) is marked kMiLocOff and gets an empty valid set —
 // then the FOV cube selection and the FromMap prefix from the shared slot table.  Writes w only;
 // head: every candidate's FromMap counts and the store's error word, for the host.
+//
+// kLanes (shared lanes, mp_lanes_shared_frame): instance p is a lane whose Bef / Aft are its kept
+// state (cand and head are null) and whose IMU flag k_lanes_imu has set for this frame.  The host
+// reads no count before the gather, so the guard is the working set's: a lane whose valid cubes hold
+// more than w.map_cap points, and every lane when the store's last update overflowed, gets
+// ERR_CAP_MAP and an empty valid set (nothing is gathered, no L-M runs, the poses stay).
+template <bool kLanes>
 __global__ __launch_bounds__(kMpThreads) void k_mp_loc_prepare(MpBuffers w, MpInput in, LocStore s,
                                                                 const float* cand, int* head) {
   const int p = blockIdx.x, tid = threadIdx.x;
@@ -249,10 +256,11 @@ __global__ __launch_bounds__(kMpThreads) void k_mp_loc_prepare(MpBuffers w, MpIn
   int* ist = w.istate + (size_t)p * kMpStateInts;
   __shared__ int sh_c[3], sh_cen[3], sh_off, sh_scan[16];
   if (tid == 0) {
-    for (int k = 0; k < 6; ++k) {
-      st[kMpAft + k] = cand[(size_t)p * 12 + k];
-      st[kMpBef + k] = cand[(size_t)p * 12 + 6 + k];
-    }
+    if (!kLanes)
+      for (int k = 0; k < 6; ++k) {
+        st[kMpAft + k] = cand[(size_t)p * 12 + k];
+        st[kMpBef + k] = cand[(size_t)p * 12 + 6 + k];
+      }
     prepare_pose(w, in, p);
     const float* T = st + kMpTobe;
     const int cW = s.istate[kMiCenW], cH = s.istate[kMiCenH], cD = s.istate[kMiCenD];
@@ -264,10 +272,10 @@ __global__ __launch_bounds__(kMpThreads) void k_mp_loc_prepare(MpBuffers w, MpIn
     ist[kMiCenW] = cW; ist[kMiCenH] = cH; ist[kMiCenD] = cD;
     ist[kMiShifts] = 0;
     ist[kMiErr] = 0;
-    ist[kMiImu] = 0;  // (no IMU message: transformUpdate without the blend)
+    if (!kLanes) ist[kMiImu] = 0;  // (no IMU message: transformUpdate without the blend)
     ist[kMiDegen] = 0;
     ist[kMiLocOff] = sh_off;
-    if (p == 0) head[2 * gridDim.x] = s.istate[kMiErr];
+    if (!kLanes && p == 0) head[2 * gridDim.x] = s.istate[kMiErr];
   }
   __syncthreads();
   int ind = 0;
@@ -284,7 +292,9 @@ __global__ __launch_bounds__(kMpThreads) void k_mp_loc_prepare(MpBuffers w, MpIn
     vp[xv * 2 + 1] = xs;
   }
   if (tid == 0) {
-    if (accC + accS > s.map_cap) {  // (k_mp_prepare's guard; a valid store never holds more)
+    bool over = accC + accS > s.map_cap;  // (k_mp_prepare's guard; a valid store never holds more)
+    if (kLanes) over = over || accC + accS > w.map_cap || (s.istate[kMiErr] & ERR_CAP_MAP) != 0;
+    if (over) {
       ist[kMiErr] |= ERR_CAP_MAP;
       accC = accS = 0;
       nv = 0;
@@ -294,8 +304,10 @@ __global__ __launch_bounds__(kMpThreads) void k_mp_loc_prepare(MpBuffers w, MpIn
     ist[kMiNValid] = nv;
     w.nfrom[p * 2 + 0] = accC;
     w.nfrom[p * 2 + 1] = accS;
-    head[p * 2 + 0] = accC;
-    head[p * 2 + 1] = accS;
+    if (!kLanes) {
+      head[p * 2 + 0] = accC;
+      head[p * 2 + 1] = accS;
+    }
   }
 }
 
@@ -3219,7 +3231,7 @@ hipError_t mp_localize_prepare(MpLoc& L, const MpBuffers& s, const MpInput& in, 
   w.P = n;
   hipError_t e = hipMemcpyAsync(L.cand, L.cand_h(), (size_t)n * 12 * sizeof(float), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_mp_loc_prepare, dim3(n), dim3(kMpThreads), 0, st, w, in, loc_store(s), L.cand, L.head);
+  hipLaunchKernelGGL(k_mp_loc_prepare<false>, dim3(n), dim3(kMpThreads), 0, st, w, in, loc_store(s), L.cand, L.head);
   if (prof) prof->mark("k_mp_loc_prepare");
   e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -3256,6 +3268,91 @@ hipError_t mp_localize_solve(MpLoc& L, const MpBuffers& s, const MpInput& in, in
   if (e == hipSuccess) e = w.take_error();
   if (e != hipSuccess) return e;
   return hipMemcpyAsync(L.res_h(), L.res, (size_t)n * kLocResWords * sizeof(int), hipMemcpyDeviceToHost, st);
+}
+
+// ---------------------------------------------------------------- shared lanes
+hipError_t mp_alloc_shared(MpBuffers& b, int P, int R, int cap_pts, int from_cap, int max_iter) {
+  DevAlloc A;
+  b.P = P;
+  b.capC = kLessSharpPerRing * R;
+  b.capS = cap_pts;
+  b.cap_stack = b.capC + b.capS;
+  b.map_cap = from_cap;
+  b.max_iter = max_iter;
+  b.tmax = next_pow2(from_cap) > (1 << 20) ? (1 << 20) : next_pow2(from_cap);
+  if (b.tmax < 64) b.tmax = 64;
+  b.pool_cur = 0;
+  const size_t Pm = (size_t)P * from_cap, Ps = (size_t)P * b.cap_stack;
+  // the per-lane part of mp_loc_reserve ...
+  A(&b.state, (size_t)P * kMpStateFloats * sizeof(float));
+  A(&b.istate, (size_t)P * kMpStateInts * sizeof(int));
+  A(&b.valid, (size_t)P * kMaxValid * sizeof(int));
+  A(&b.vpre, (size_t)P * (kMaxValid + 1) * 2 * sizeof(int));
+  A(&b.nfrom, (size_t)P * 2 * sizeof(int));
+  A(&b.hC_T, (size_t)P * sizeof(int));
+  A(&b.hS_T, (size_t)P * sizeof(int));
+  A(&b.stack2, Ps * sizeof(float4));
+  A(&b.stack, Ps * sizeof(float4));
+  A(&b.sseg_b, (size_t)P * 2 * sizeof(int));
+  A(&b.sseg_e, (size_t)P * 2 * sizeof(int));
+  A(&b.sseg_cnt, (size_t)P * 2 * sizeof(int));
+  A(&b.sseg_leaf, (size_t)P * 2 * sizeof(float));
+  if (A.err == hipSuccess) A.err = vg_scratch_alloc(b.vg, Ps, (size_t)P * 2, 2 * P, Ps);
+  A(&b.q_ok, Ps * sizeof(int8_t));
+  A(&b.q_cf, Ps * sizeof(float4));
+  A(&b.q_nn, Ps * 2 * sizeof(int4));
+  A(&b.q_fit, Ps * 4 * sizeof(float4));
+  A(&b.part, (size_t)P * std::max(kMpSmallGrid, kMpFitGridMax) * 28 * sizeof(double));
+  A(&b.rot, (size_t)P * 6 * sizeof(double));
+  A(&b.done, (size_t)P * sizeof(int));
+  A(&b.ls_epoch, sizeof(unsigned long long));  // (k_mp_lm_begin advances it for one instance)
+  // ... of mp_loc_reserve_map ...
+  A(&b.from, Pm * sizeof(float4));
+  A(&b.hC_pts, Pm * sizeof(float4));
+  A(&b.hS_pts, Pm * sizeof(float4));
+  A(&b.hC_start, (size_t)P * (b.tmax + 1) * sizeof(int));
+  A(&b.hS_start, (size_t)P * (b.tmax + 1) * sizeof(int));
+  A(&b.hC_rec, (size_t)P * b.tmax * sizeof(uint32_t));
+  A(&b.hS_rec, (size_t)P * b.tmax * sizeof(uint32_t));
+  A(&b.h_fill, (size_t)2 * P * b.tmax * sizeof(int));
+  // ... and the registered clouds
+  A(&b.reg, (size_t)P * b.capS * sizeof(float4));
+  A(&b.nreg, (size_t)P * sizeof(int));
+  if (A.err == hipSuccess) A.err = hipMemset(b.state, 0, (size_t)P * kMpStateFloats * sizeof(float));
+  if (A.err == hipSuccess) A.err = hipMemset(b.istate, 0, (size_t)P * kMpStateInts * sizeof(int));
+  if (A.err == hipSuccess) A.err = hipMemset(b.done, 0, (size_t)P * sizeof(int));
+  if (A.err == hipSuccess) A.err = hipMemset(b.ls_epoch, 0, sizeof(unsigned long long));
+  if (A.err == hipSuccess) A.err = hipDeviceSynchronize();
+  if (A.err != hipSuccess) mp_free(b);
+  return A.err;
+}
+
+void mp_lanes_shared_frame(MpBuffers& w, MpBuffers& s, const MpInput& in, int* res, hipStream_t st, Prof* prof) {
+  const int P = w.P;
+  auto mark = [&](const char* name) { if (prof) prof->mark(name); };
+  mp_wait_update(s, st);  // (the store's last update, when the streaming path deferred it)
+  const LocStore store = loc_store(s);
+  hipLaunchKernelGGL(k_mp_loc_prepare<true>, dim3(P), dim3(kMpThreads), 0, st, w, in, store, (const float*)nullptr,
+                     (int*)nullptr);
+  mark("k_mp_loc_prepare");
+  hipLaunchKernelGGL(k_mp_stack, dim3(16, P), dim3(256), 0, st, w, in);
+  mark("k_mp_stack");
+  mp_stack_vg(w, P, st, /*stack_max=*/-1);
+  mark("vg_stack");
+  // mp_localize_solve's grid with the capacity in the place of the largest FromMap: a workgroup
+  // whose first tile lies beyond its lane's FromMap returns at once
+  const int tiles = (w.map_cap + 1023) / 1024;
+  const int gx = std::max(1, std::min(tiles, (2048 + P - 1) / P));
+  hipLaunchKernelGGL(k_mp_loc_gather, dim3(gx, P), dim3(256), 0, st, w, store);
+  mark("k_mp_loc_gather");
+  mp_hash_from(w, P, st, /*spread=*/w.map_cap > 8192);
+  mark("k_hash_build_map");
+  mp_lm_loop(w, P, st, prof, /*map_empty=*/false, /*persist=*/false);
+  hipLaunchKernelGGL(k_mp_register, dim3(kMpRegWg, P), dim3(256), 0, st, w, in);
+  mark("k_mp_register");
+  hipLaunchKernelGGL(k_mp_loc_result, dim3((P + 255) / 256), dim3(256), 0, st, w, res);
+  mark("k_mp_loc_result");
+  w.note(hipGetLastError());
 }
 
 // A batch problem ends at cur's solved pose: no call returns its map or its registered clouds, so

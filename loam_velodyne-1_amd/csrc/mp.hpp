@@ -270,5 +270,20 @@ hipError_t mp_localize_prepare(MpLoc& L, const MpBuffers& s, const MpInput& in, 
 hipError_t mp_localize_solve(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, int from_max, int cloud_max,
                              int stack_max, hipStream_t st, Prof* prof);
 
+// ---- shared lanes (loam_lanes_open_shared): every lane's mapping frame against one streaming store ----
+// The lanes' working set: an MpBuffers of P lanes built as MpLoc::w is (no pools, slot tables, cube
+// VoxelGrid or insertion buffers), with from_cap FromMap points per lane (its map_cap), each lane's
+// own state and the registered clouds (reg / nreg).  On failure: freed, b empty.
+hipError_t mp_alloc_shared(MpBuffers& b, int P, int R, int cap_pts, int from_cap, int max_iter);
+// One mapping frame of the P lanes of w against the store of s (instance 0), which is only read:
+// loam_map_localize's launch sequence with the lanes' kept Bef / Aft and IMU flags (k_mp_loc_prepare<true>),
+// every lane's clouds read in place (in: per-lane strides), k_mp_register behind k_mp_lm_end, then
+// every lane's k_mp_loc_result block into res (device, [P][kLocResWords]).  Waits on the device for a
+// deferred update of s.  No launch form depends on a count the host would have to read: stack_max
+// is unknown (-1), the gather's grid covers from_cap, the hash builds take the grid-per-cloud form
+// iff from_cap > 8192 (a cloud beyond k_hash_build's LDS counters is possible), and the L-M never
+// takes the persistent form.
+void mp_lanes_shared_frame(MpBuffers& w, MpBuffers& s, const MpInput& in, int* res, hipStream_t st, Prof* prof);
+
 }  // namespace loam
 #endif

@@ -3,7 +3,7 @@ stepped by loam_chain_sweep from one thread, through the C-ABI on one GPU (DESIG
 
   python tools/lanes_bench.py [--s 1,16,64] [--sweeps 27] [--map-cap 131072] [--yard-max 1024]
                               [--profile-s 64] [--imu] [--restart K,M] [--occupancy N] [--map-import N]
-                              [--surround] [--out FILE]
+                              [--surround] [--shared stream|big [--from-cap F]] [--out FILE]
 
 Per S: S lanes over eight distinct VLP-16 synthetic streams laid out cyclically.  The wall time of
 lanes_step (push + pull), and of the push alone (host packing + enqueue), median and range over the
@@ -55,7 +55,18 @@ one after the other into its own preallocated array, timed the same way, the sid
 by call.  Both sides go through ctypes with nothing allocated
 inside the timed region.  Every lane's cloud is compared with its context's bit for bit.  Then
 seven more calls of loam_lanes_surround under loam_set_profiling for its device time per call and
-kernel (loam_mapping_surround records none)."""
+kernel (loam_mapping_surround records none).
+
+--shared stream|big (instead of the above): per S, a fleet localizing in one map both
+ways in one process, alternating three times: shared lanes (loam_lanes_open_shared, the context
+imports the map, every lane set to the zero pose) and the parent's only way, own-store lanes with the
+map imported into all S lanes (lane_map_capacity = the smallest power of two that holds it).  The
+map: what a context builds over stream 1 in --sweeps sweeps, or tools/localize_bench.py's big map
+(1.5 M uniform points).  Per run: the device memory the open took (hipMemGetInfo before and after),
+the wall time of lanes_step after the warm-up, mapping steps and the others apart, the lanes that
+failed, and on the shared side the largest FromMap a lane gathered.  An open that fails is reported
+(opens = false), not an error.  --profile-s S: one more shared run at that S under
+loam_set_profiling, the device time per kernel and step and per launch."""
 import argparse
 import importlib
 import json
@@ -455,6 +466,125 @@ def run_surround(S, streams, map_cap, yard_max, reps=7, warm=2):
     return line
 
 
+def _mem_free():
+    """free device memory in bytes (hipMemGetInfo)"""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    if hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) != 0:
+        raise RuntimeError("hipMemGetInfo failed")
+    return int(free.value)
+
+
+def shared_big_map(M):
+    """tools/localize_bench.py's big map: 1.5 M uniform points about M's centre"""
+    rng = np.random.default_rng(20261019)
+    half = np.array([546.0, 286.0, 546.0])
+
+    def uniform(n):
+        p = np.empty((n, 4), np.float32)
+        p[:, :3] = (rng.uniform(-1.0, 1.0, (n, 3)) * half).astype(np.float32)
+        p[:, 3] = rng.uniform(0, 16, n).astype(np.float32)
+        return p
+    return dict(M, corner=uniform(388894), surf=uniform(1111106), center=np.array([10, 5, 10], np.int32))
+
+
+def run_fleet(S, streams, K, M, cap, shared, profile=False):
+    """S lanes over K steps in the map M: shared lanes of lane_from_capacity cap in a context that
+    imported M, or own-store lanes of lane_map_capacity cap with M imported into every lane.  The
+    device memory the open (and, own-store, nothing else) took, the wall time of the steps after
+    the warm-up, and every lane's last status."""
+    kw = dict(corner=M["corner"], surf=M["surf"], center=M["center"], surround_phase=4)
+    total = int(M["corner"].shape[0] + M["surf"].shape[0])
+    free_ctx = _mem_free()
+    # (the context's own store holds M on the shared side and stays empty on the other)
+    eng = loam.Engine(loam.default_config(system_delay=1, map_capacity=max(1 << 17, 1 << int(np.ceil(np.log2(total))))
+                                          if shared else 1 << 17))
+    eng.set_tuning(batch_streams=0)
+    if shared:
+        eng.map_import(**kw)
+    free0 = _mem_free()
+    t0 = time.perf_counter()
+    try:
+        (eng.lanes_open_shared if shared else eng.lanes_open)(S, cap)
+    except loam.LoamError as err:
+        eng.close()
+        return dict(opens=False, error=str(err)[:160])
+    open_ms = (time.perf_counter() - t0) * 1e3
+    held = free0 - _mem_free()
+    t0 = time.perf_counter()
+    if shared:
+        eng.lanes_set_pose(list(range(S)), np.zeros(6, np.float32))
+    else:
+        eng.lanes_map_import(list(range(S)), **kw)
+    seed_ms = (time.perf_counter() - t0) * 1e3
+    step = {0: [], 1: []}
+    n_prof = 0
+    status = None
+    frm = 0
+    for k in range(K):
+        raws = [streams[l % N_STREAMS][k] for l in range(S)]
+        if profile and k == 2 + WARM:
+            eng.set_profiling(True)
+        t0 = time.perf_counter()
+        eng.lanes_push(raws, stamp=0.1 * k)
+        o = eng.lanes_pull()
+        t1 = time.perf_counter()
+        status = o["status"]
+        if k >= 2 + WARM:
+            step[int(o["mapped"].max())].append((t1 - t0) * 1e3)
+            n_prof += 1
+        if shared and o["mapped"].max():
+            i = eng.lanes_localize_info()
+            frm = max(frm, int((i["map_corner"].astype(np.int64) + i["map_surf"]).max()))
+    res = dict(opens=True, open_ms=round(open_ms, 1), held_bytes=held, context_bytes=free_ctx - free0,
+               seed_ms=round(seed_ms, 2),
+               step_mapped_ms=spread(step[1]), step_unmapped_ms=spread(step[0]),
+               lanes_failed=int(np.count_nonzero(status != 0)))
+    if shared:
+        res["from_map_max"] = frm
+    if profile:
+        res["device_ms_per_step"] = {k: round(v[0] / n_prof, 4)
+                                     for k, v in sorted(eng.kernel_times().items(), key=lambda kv: -kv[1][0])}
+        res["device_ms_per_launch"] = {k: round(v[0] / v[1], 4) for k, v in sorted(eng.kernel_times().items()) if v[1]}
+        res["profiled_steps"] = n_prof
+        eng.set_profiling(False)
+    eng.lanes_close()
+    eng.close()
+    return res
+
+
+def run_shared(S, streams, K, name, M, from_cap, pairs=3, profile=False):
+    """one JSON line: `pairs` alternating (shared, own-store) runs of S lanes in the map M"""
+    total = int(M["corner"].shape[0] + M["surf"].shape[0])
+    C = 1 << int(np.ceil(np.log2(max(total, 1024))))
+    runs = []
+    grown = []  # own-store capacities at which a lane's store overflowed while it mapped into it
+    for _ in range(pairs):
+        sh = run_fleet(S, streams, K, M, from_cap, True)
+        own = run_fleet(S, streams, K, M, C, False)
+        while own["opens"] and own["lanes_failed"] and C < (1 << 24):  # (the yardstick's maps grow: the next power of two)
+            grown.append(C)
+            C *= 2
+            own = run_fleet(S, streams, K, M, C, False)
+        runs.append(dict(shared=sh, own_store=own))
+        if not own["opens"] or not sh["opens"]:
+            break  # (an open that fails fails every time)
+    line = dict(shared_leg=name, S=S, sweeps=K, map_points=total, lane_map_capacity=C, lane_from_capacity=from_cap,
+                own_store_overflowed_at=grown, pairs=runs)
+    both = [r for r in runs if r["shared"]["opens"] and r["own_store"]["opens"]]
+    if both:
+        line["shared_not_above_own_mapped"] = [bool(r["shared"]["step_mapped_ms"]["median"] <=
+                                                    r["own_store"]["step_mapped_ms"]["median"]) for r in both]
+        saved = both[0]["own_store"]["held_bytes"] - both[0]["shared"]["held_bytes"]
+        line["held_bytes_saved"] = saved
+        line["held_bytes_saved_bound"] = S * 112 * (C - from_cap)
+        line["memory_accepted"] = bool(saved >= S * 112 * (C - from_cap))
+    if profile:
+        line["profile_shared"] = run_fleet(S, streams, K, M, from_cap, True, profile=True)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--s", default="1,16,64")
@@ -467,6 +597,9 @@ def main():
     ap.add_argument("--occupancy", type=int, default=0, help="recordings of 10..40 sweeps over 16 lanes")
     ap.add_argument("--map-import", type=int, default=0, help="points of the synthetic map (and the stream map)")
     ap.add_argument("--surround", action="store_true", help="loam_lanes_surround against serial contexts")
+    ap.add_argument("--shared", default=None, help="stream|big: shared lanes against own-store lanes in that map")
+    ap.add_argument("--from-cap", type=int, default=0,
+                    help="--shared: lane_from_capacity (0: the power of two that holds the stream map, 65536 in the big map)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     K = 40 if a.occupancy else 23 if a.surround else a.sweeps
@@ -486,6 +619,21 @@ def main():
 
     if a.occupancy:
         emit(run_occupancy(a.occupancy, streams, a.map_cap))
+        return
+    if a.shared:
+        e = loam.Engine(loam.default_config(system_delay=1))
+        for k in range(K):
+            e.chain_sweep(streams[0][k], stamp=0.1 * k)
+        M = e.map_export()
+        e.close()
+        M = dict(M, aft=np.zeros(6, np.float32), bef=np.zeros(6, np.float32))
+        if a.shared == "big":
+            M = shared_big_map(M)
+        # (a lane in the stream map sees all of it: the smallest power of two that holds the map)
+        total = int(M["corner"].shape[0] + M["surf"].shape[0])
+        F = a.from_cap or (65536 if a.shared == "big" else 1 << int(np.ceil(np.log2(max(total, 1024)))))
+        for S in [int(v) for v in a.s.split(",") if v]:
+            emit(run_shared(S, streams, K, a.shared, M, F, profile=S == a.profile_s))
         return
     if a.surround:
         for S in [int(v) for v in a.s.split(",") if v]:
