@@ -615,6 +615,30 @@ int loam_lanes_set_pose(loam_ctx *ctx, uint32_t n, const uint32_t *lane, const l
  * LOAM_E_INVAL: a null argument, lanes not open or not shared, a step in flight, before the first pull. */
 #define LOAM_LOC_NONE (LOAM_LOC_OFFGRID + 1)   /* = 3, behind loam_map_localize's statuses: the lane ran no mapping frame on that step */
 int loam_lanes_localize_info(loam_ctx *ctx, loam_localize_result *out /* [n_lanes] */);
+
+/* loam_map_score for the lanes, between two steps, in both lane modes: k pose guesses for each of n
+ * listed lanes in one call, one index of the map and one synchronisation for all of them.
+ * out[i*k + j], i < n, j < k, is bit for bit (all 32 bytes) what loam_map_score(ctx, C, S, max_dist,
+ * 1, &pose[i*k + j], ..) returns on this context, where C / S are lane lane[i]'s
+ * laserCloudCornerLast / laserCloudSurfLast as its last pulled frame left them: what loam_odometry
+ * writes into corner_last / surf_last on the context the lane equals (the raw lessSharp / lessFlat
+ * clouds on the lane's init frame, src/laserOdometry.cpp:427-434, the TransformToEnd clouds on every
+ * later frame, :875-902), whether or not that frame publishes them.  They are read in place on the
+ * device, in their stored order.  A row depends on the map, the lane's clouds, max_dist and its own
+ * pose only: not on n, k, its position in the call, or the run.
+ * The map is the context's streaming map: on shared lanes the map the lanes localize in, on
+ * loam_lanes_open lanes whatever loam_map_import put into the context (the prior map a caller is
+ * about to hand to loam_lanes_map_import with aft = the best guess); a lane's own store is not read.
+ * The call waits for the context's queued work (a deferred map update included), changes nothing
+ * in the context or in any lane, and may be repeated.  An empty map is no error: every count is 0
+ * and every cost is scored * r2.
+ * LOAM_E_INVAL, with out untouched: a null argument, lanes not open, a step in flight, no pulled
+ * step yet on which the odometry was initialised (inside system_delay), n == 0 or n > n_lanes,
+ * k == 0, n x k > LOAM_SCORE_MAX, max_dist not in (0, 1], a lane index >= n_lanes, a lane listed
+ * twice, a failed lane, a lane between loam_lanes_restart and the pull of its init step, a map whose
+ * last update overflowed map_capacity.  LOAM_E_NOMEM / LOAM_E_HIP as loam_map_score. */
+int loam_lanes_score(loam_ctx *ctx, uint32_t n, const uint32_t *lane /* [n] */, float max_dist,
+                     uint32_t k, const loam_pose6 *pose /* [n][k] */, loam_score_result *out /* [n][k] */);
 /* Frees the lanes' working set (waits for a step in flight).  LOAM_E_INVAL when not open. */
 int loam_lanes_close(loam_ctx *ctx);
 

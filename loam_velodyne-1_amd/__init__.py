@@ -196,7 +196,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_lanes_open", "loam_lanes_push", "loam_lanes_pull", "loam_lanes_registered", "loam_lanes_map_export",
            "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
            "loam_lanes_restart", "loam_lanes_map_import", "loam_lanes_surround",
-           "loam_lanes_open_shared", "loam_lanes_set_pose", "loam_lanes_localize_info",
+           "loam_lanes_open_shared", "loam_lanes_set_pose", "loam_lanes_localize_info", "loam_lanes_score",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -261,6 +261,8 @@ def lib():
         L.loam_lanes_open_shared.argtypes = [PP, ctypes.c_uint32, ctypes.c_uint32]
         L.loam_lanes_set_pose.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), P(Pose6), P(Pose6)]
         L.loam_lanes_localize_info.argtypes = [PP, P(LocalizeResult)]
+        L.loam_lanes_score.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), ctypes.c_float, ctypes.c_uint32, P(Pose6),
+                                       P(ScoreResult)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -706,6 +708,39 @@ class Engine:
         _check(lib().loam_lanes_localize_info(self.h, rec.ctypes.data_as(ctypes.POINTER(LocalizeResult))))
         return rec
 
+    def lanes_score(self, lanes, poses, max_dist=1.0):
+        """pose guesses for the listed lanes' own last sweeps scored against the context's whole map
+        in one call (loam_lanes_score): poses (n, k, 6), or (k, 6) used for every listed lane.
+        Returns map_score's dict with arrays of shape (n, k): row [i, j] is what map_score gives
+        lane lanes[i]'s corner_last / surf_last at poses[i, j].  n x k <= SCORE_MAX."""
+        lanes = [int(l) for l in np.atleast_1d(lanes)]
+        n = len(lanes)
+        p = _lane_poses(n, poses)
+        k = p.shape[1]
+        idx = (ctypes.c_uint32 * max(n, 1))(*lanes)
+        rec = np.empty(max(n * k, 1), _SCORE_DTYPE)
+        _check(lib().loam_lanes_score(self.h, n, idx, float(max_dist), k, p.ctypes.data_as(ctypes.POINTER(Pose6)),
+                                      rec.ctypes.data_as(ctypes.POINTER(ScoreResult))))
+        return {key: rec[key][:n * k].reshape(n, k).copy() for key in SCORE_KEYS}
+
+    def lanes_relocalize(self, lanes, poses, od_sum, max_dist=1.0):
+        """re-seeds the listed shared lanes in the map: scores the guesses (lanes_score), takes each
+        lane's best row by score_order and gives it to the lane with lanes_set_pose(aft = the chosen
+        guess, bef = od_sum[lane]), od_sum being the last lanes_pull / lanes_step output's (n_lanes,
+        6) array, so that only later odometry increments are applied on top.  Returns a dict: index
+        (n,) the chosen rows, aft (n, 6) the chosen guesses, score (map_score's keys, (n,) each)."""
+        lanes = [int(l) for l in np.atleast_1d(lanes)]
+        n = len(lanes)
+        p = _lane_poses(n, poses)
+        od_sum = np.asarray(od_sum, np.float32)
+        if od_sum.ndim != 2 or od_sum.shape != (self.n_lanes, 6):
+            raise ValueError("od_sum: the (n_lanes, 6) array of the last pulled step")
+        score = self.lanes_score(lanes, p, max_dist)
+        index = np.array([score_order({key: v[i] for key, v in score.items()})[0] for i in range(n)], np.int64)
+        aft = np.ascontiguousarray(p[np.arange(n), index])
+        self.lanes_set_pose(lanes, aft, np.ascontiguousarray(od_sum[lanes]))
+        return {"index": index, "aft": aft, "score": {key: v[np.arange(n), index] for key, v in score.items()}}
+
     def lanes_close(self):
         _check(lib().loam_lanes_close(self.h))
         self.n_lanes = 0
@@ -778,6 +813,16 @@ class Engine:
         o = score_order(fine, idx)
         return {"index": idx[o], "localize": {k: v[o] for k, v in loc.items()},
                 "coarse": {k: coarse[k][idx][o] for k in SCORE_KEYS}, "fine": {k: v[o] for k, v in fine.items()}}
+
+
+def _lane_poses(n, poses):
+    """lanes_score's poses as a contiguous (n, k, 6) float32 array"""
+    p = np.asarray(poses, np.float32)
+    if p.ndim == 2 and p.shape[1:] == (6,):
+        p = np.broadcast_to(p, (n,) + p.shape)
+    if p.ndim != 3 or p.shape[0] != n or p.shape[1] == 0 or p.shape[2] != 6:
+        raise ValueError("poses: (n, k, 6) with one block per listed lane, or (k, 6) for every lane")
+    return np.ascontiguousarray(p)
 
 
 def score_order(score, index=None):

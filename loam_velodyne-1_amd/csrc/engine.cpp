@@ -2508,6 +2508,112 @@ extern "C" int loam_lanes_localize_info(loam_ctx* x, loam_localize_result* out) 
   return LOAM_OK;
 }
 
+// k pose guesses for each of n listed lanes against the whole streaming map (score.hpp, DESIGN.md
+// §31): loam_map_score's sequence with the lanes' Last clouds read in place.  The lanes' nlast
+// words come down with the map's sizes; the host then knows every listed lane's tiles.
+extern "C" int loam_lanes_score(loam_ctx* x, uint32_t n, const uint32_t* lane, float max_dist, uint32_t k,
+                                const loam_pose6* pose, loam_score_result* out) {
+  if (!x || !lane || !pose || !out) return fail(LOAM_E_INVAL, "null argument");
+  const std::string who = "loam_lanes_score";
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
+  if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
+  if (!L.pulled || !L.od_inited)
+    return fail(LOAM_E_INVAL, who + ": no step was pulled on which the odometry was initialised (no Last clouds yet)");
+  if (n == 0 || n > (uint32_t)L.S) return fail(LOAM_E_INVAL, who + ": n must be in [1, n_lanes]");
+  if (k == 0) return fail(LOAM_E_INVAL, who + ": k must be at least 1");
+  if ((uint64_t)n * (uint64_t)k > (uint64_t)LOAM_SCORE_MAX)
+    return fail(LOAM_E_INVAL, who + ": n x k must not exceed LOAM_SCORE_MAX");
+  if (!(max_dist > 0.0f && max_dist <= 1.0f))
+    return fail(LOAM_E_INVAL, who + ": max_dist must be in (0, 1] (the map index has 1 m cells)");
+  std::vector<char> seen;
+  uint32_t bad = 0;
+  const int why = lanes_list_check(lane, n, L.S, L.fail.data(), L.life.data(), seen, &bad);
+  if (why != kLaneListOk) {
+    const std::string at = who + ": lane[" + std::to_string(bad) + "] = " + std::to_string(lane[bad]);
+    if (why == kLaneListRange) return fail(LOAM_E_INVAL, at + " is out of range");
+    if (why == kLaneListTwice) return fail(LOAM_E_INVAL, at + " is listed twice");
+    if (why == kLaneListFailed) return fail(LOAM_E_INVAL, at + " has failed (loam_lanes_restart first)");
+    return fail(LOAM_E_INVAL, at + " waits for its init step (the restart's clear would overwrite the pose)");
+  }
+  int rc = map_drain(x);
+  if (rc) return rc;
+  MpBuffers& b = x->mp1;
+  MpScore& S = x->score;
+  const OdBuffers& o = L.od;
+  hipError_t he = mp_map_ensure(x->mio);
+  if (he == hipSuccess) he = mp_score_reserve(S, 0);
+  if (he == hipSuccess) he = mp_score_reserve_plan(S, L.S);
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LOAM_E_NOMEM, who + ": working set allocation failed: " + hipGetErrorString(he));
+  }
+  hipStream_t st = x->st;
+  const size_t rows = (size_t)n * k;
+  std::memcpy(S.pose_h(), pose, rows * sizeof(loam_pose6));
+  x->prof.begin(st);
+  he = mp_map_table(b, x->mio, st, &x->prof);
+  if (he == hipSuccess) he = hipMemcpyAsync(S.pose, S.pose_h(), rows * sizeof(loam_pose6), hipMemcpyHostToDevice, st);
+  x->prof.mark("lanes_score_h2d");
+  if (he == hipSuccess)
+    he = hipMemcpyAsync(S.nlast_h(), o.nlast, (size_t)L.S * kOdBufs * 2 * sizeof(int), hipMemcpyDeviceToHost, st);
+  x->prof.mark("lanes_score_d2h");
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    x->prof.collect();
+    return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
+  }
+  const int* T = x->mio.tab_h;
+  const int nC = T[kMapTabOff + kCubeNum], total = T[kMapTabOff + kMapKeys];
+  if ((T[kMapTabInfo + 3] & ERR_CAP_MAP) || nC < 0 || total < nC || total > b.map_cap) {
+    x->prof.collect();
+    return fail(LOAM_E_INVAL, who + ": the last map update exceeded map_capacity, the store is not valid");
+  }
+  std::vector<int32_t> cnt((size_t)2 * n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const int* w = S.nlast_h() + ((size_t)lane[i] * kOdBufs + L.od_last) * 2;
+    cnt[2 * i] = w[0];
+    cnt[2 * i + 1] = w[1];
+  }
+  LaneScoreShape shape;
+  const int plan = lanes_score_plan(n, k, lane, cnt.data(), (uint32_t)L.S, (uint32_t)L.od_last, o.capC, o.capS,
+                                    S.plan_h(), &shape);
+  if (plan != kLanePlanOk) {
+    x->prof.collect();
+    return fail(LOAM_E_HIP, who + ": a lane's Last cloud sizes are not valid (plan code " + std::to_string(plan) + ")");
+  }
+  he = mp_score_reserve_map(S, nC, total - nC, 0, 0, (int)rows);
+  if (he != hipSuccess) {
+    x->prof.collect();
+    return fail(LOAM_E_NOMEM, who + ": index allocation failed (" + std::to_string(total) + " map points): " +
+                                  hipGetErrorString(he));
+  }
+  const bool count = x->prof.on;  // (with profiling the kernel also adds up the points and buckets the searches read)
+  he = mp_lanes_score_run(S, b, x->mio, nC, total, o.lastC, o.lastS, shape, (int)n, (int)k, max_dist * max_dist, count,
+                          st, &x->prof);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    x->prof.collect();
+    return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
+  }
+  x->prof.collect();
+  if (count) {  // work counters beside the kernel times: (count, calls)
+    double queries = 0.0;
+    for (size_t r = 0; r < rows; ++r) queries += (double)S.res_h()[r].corner_scored + (double)S.res_h()[r].surf_scored;
+    const char* names[3] = {"score_nn_candidates", "score_nn_cells", "score_queries"};
+    const double v[3] = {(double)S.work_h()[0], (double)S.work_h()[1], queries};
+    for (int c = 0; c < 3; ++c) {
+      auto& a = x->prof.acc[names[c]];
+      a.first += v[c];
+      a.second += 1;
+    }
+  }
+  std::memcpy(out, S.res_h(), rows * sizeof(loam_score_result));
+  return LOAM_OK;
+}
+
 extern "C" int loam_lanes_close(loam_ctx* x) {
   if (!x) return fail(LOAM_E_INVAL, "null argument");
   if (!x->lanes.S) return fail(LOAM_E_INVAL, "loam_lanes_close: lanes are not open");

@@ -6,6 +6,8 @@
 //             then surf tiles; a lane takes kScorePer points.  The candidate's rotation is
 //             evaluated once per workgroup.  One (counts, fp64 sum) partial per workgroup.
 //  k_mp_score_reduce  one lane per candidate adds its partials in tile order.
+//  k_lanes_score  loam_lanes_score: one workgroup per (listed lane, pose) walks the lane's Last
+//             clouds in place, tile by tile (the tile body is k_mp_score's), and writes the row.
 //
 // Every sum has a fixed order (lane-local over the lane's points, the wave's butterfly, the
 // workgroup's waves, the tiles), so a candidate's result does not depend on the call it is part
@@ -42,42 +44,51 @@ struct ScoreArgs {
   ScorePart* part;      // [candidates of the launch][tiles]
 };
 
-__global__ __launch_bounds__(kScoreThreads) void k_mp_score(ScoreArgs a) {
-  constexpr int kWaves = kScoreThreads / 64;
-  const int tid = threadIdx.x, tile = blockIdx.y;
-  const int kind = tile < a.tiles_c ? 0 : 1;
-  const int n = a.nq[kind], base = (kind ? tile - a.tiles_c : tile) * kScoreTile;
-  const float4* q = a.q[kind];
-  // the lane's points: all loads before the rotation is waited for
-  float4 p[kScorePer];
-  bool use[kScorePer];
+constexpr int kScoreWaves = kScoreThreads / 64;
+
+// the candidate pose's map_rot, once per workgroup: the three cosines by wave 0, the sines by wave 1
+// (the caller's __syncthreads follows)
+__device__ __forceinline__ void score_rot_eval(const float* T, double* rot) {
+  const int tid = threadIdx.x;
+  if (tid < 3) rot[2 * tid] = dcos(T[tid]);
+  else if (tid >= 64 && tid < 67) rot[2 * (tid - 64) + 1] = dsin(T[tid - 64]);
+}
+__device__ __forceinline__ loampose::MapRot score_rot_read(const float* T, const double* rot) {
+  loampose::MapRot R;
+  R.c0 = rot[0]; R.s0 = rot[1]; R.c1 = rot[2]; R.s1 = rot[3]; R.c2 = rot[4]; R.s2 = rot[5];
+  R.t3 = T[3]; R.t4 = T[4]; R.t5 = T[5];
+  return R;
+}
+
+// The tile body k_mp_score and k_lanes_score share.  The lane's kScorePer points of the tile at
+// `base` of the cloud q (n >= 1 points) ...
+__device__ __forceinline__ void score_tile_load(const float4* q, int n, int base, float4* p, bool* use) {
+  const int tid = threadIdx.x;
 #pragma unroll
   for (int r = 0; r < kScorePer; ++r) {
     const int i = base + r * kScoreThreads + tid;
     p[r] = q[min(i, n - 1)];  // (a tile holds at least one point: n >= 1)
     use[r] = i < n && score_finite3(p[r]);
   }
-  // map_rot of the candidate's pose, once per workgroup: the three cosines by wave 0, the sines by wave 1
-  __shared__ double rot[6];
-  __shared__ double wsum[kWaves];
-  __shared__ uint32_t wcnt[kWaves][4];
-  const float* T = a.pose + (size_t)(a.h0 + blockIdx.x) * 6;
-  if (tid < 3) rot[2 * tid] = dcos(T[tid]);
-  else if (tid >= 64 && tid < 67) rot[2 * (tid - 64) + 1] = dsin(T[tid - 64]);
-  __syncthreads();
-  loampose::MapRot R;
-  R.c0 = rot[0]; R.s0 = rot[1]; R.c1 = rot[2]; R.s1 = rot[3]; R.c2 = rot[4]; R.s2 = rot[5];
-  R.t3 = T[3]; R.t4 = T[4]; R.t5 = T[5];
-  const ScoreMap m = {a.start[kind], a.pts[kind], a.tsize[kind]};
+}
+// ... searched at R and summed: lane-local in r order, the wave's butterfly over xor 32 .. 1, then
+// (behind one __syncthreads) the waves in order.  The tile's partial is returned by thread 0 (the
+// other threads' value is not meaningful).  wsum / wcnt: the workgroup's LDS words of this tile; a
+// caller that runs several tiles alternates between two sets, so that no wave writes a set thread 0
+// still reads.
+__device__ __forceinline__ ScorePart score_tile_eval(const float4* p, const bool* use, const ScoreMap& m,
+                                                     const loampose::MapRot& R, float r2, double* wsum,
+                                                     uint32_t (*wcnt)[4]) {
+  const int tid = threadIdx.x;
   double sum = 0.0;
   uint32_t scored = 0, in = 0, cand = 0, cells = 0;
 #pragma unroll
   for (int r = 0; r < kScorePer; ++r) {
     if (!use[r]) continue;
     const float4 w = loampose::point_to_map(R, p[r]);
-    const float d = score_nearest(m, w.x, w.y, w.z, a.r2, cand, cells);
+    const float d = score_nearest(m, w.x, w.y, w.z, r2, cand, cells);
     ++scored;
-    in += d < a.r2 ? 1u : 0u;
+    in += d < r2 ? 1u : 0u;
     sum += (double)d;
   }
   // the wave (every lane is active), then the waves in order
@@ -98,21 +109,108 @@ __global__ __launch_bounds__(kScoreThreads) void k_mp_score(ScoreArgs a) {
     wcnt[wv][3] = cells;
   }
   __syncthreads();
+  ScorePart o;
+  o.sum = 0.0;
+  o.scored = o.in = o.cand = o.cells = 0;
   if (tid == 0) {
-    ScorePart o;
     o.sum = wsum[0];
     o.scored = wcnt[0][0];
     o.in = wcnt[0][1];
     o.cand = wcnt[0][2];
     o.cells = wcnt[0][3];
-    for (int k = 1; k < kWaves; ++k) {
+    for (int k = 1; k < kScoreWaves; ++k) {
       o.sum += wsum[k];
       o.scored += wcnt[k][0];
       o.in += wcnt[k][1];
       o.cand += wcnt[k][2];
       o.cells += wcnt[k][3];
     }
-    a.part[(size_t)blockIdx.x * a.tiles + tile] = o;
+  }
+  return o;
+}
+
+__global__ __launch_bounds__(kScoreThreads) void k_mp_score(ScoreArgs a) {
+  const int tid = threadIdx.x, tile = blockIdx.y;
+  const int kind = tile < a.tiles_c ? 0 : 1;
+  const int n = a.nq[kind], base = (kind ? tile - a.tiles_c : tile) * kScoreTile;
+  // the lane's points: all loads before the rotation is waited for
+  float4 p[kScorePer];
+  bool use[kScorePer];
+  score_tile_load(a.q[kind], n, base, p, use);
+  __shared__ double rot[6];
+  __shared__ double wsum[kScoreWaves];
+  __shared__ uint32_t wcnt[kScoreWaves][4];
+  const float* T = a.pose + (size_t)(a.h0 + blockIdx.x) * 6;
+  score_rot_eval(T, rot);
+  __syncthreads();
+  const loampose::MapRot R = score_rot_read(T, rot);
+  const ScoreMap m = {a.start[kind], a.pts[kind], a.tsize[kind]};
+  const ScorePart o = score_tile_eval(p, use, m, R, a.r2, wsum, wcnt);
+  if (tid == 0) a.part[(size_t)blockIdx.x * a.tiles + tile] = o;
+}
+
+struct LanesScoreArgs {
+  const float4* last[2];      // OdBuffers::lastC / lastS
+  const LaneScorePlan* plan;  // [n] the listed lanes
+  const int* start[2];        // the two indexes
+  const float4* pts[2];
+  const int* tsize;           // [2] their table sizes
+  const float* pose;          // [n k][6]
+  float r2;
+  int k;                      // poses per listed lane
+  loam_score_result* res;     // [n k]
+  unsigned long long* work;   // (profiling, else nullptr) [2]: the map points and buckets read are added
+};
+
+// One workgroup per (listed lane, pose): row = blockIdx.x = i k + j.  It walks lane i's tiles in
+// order, corner tiles first; thread 0 adds the tiles' partials as k_mp_score_reduce does (each
+// cloud's sum from 0.0, in tile order) and writes the row itself: no partial array, no second
+// launch.  The sums' order is k_mp_score's throughout (score_tile_eval), so a row has the bits
+// loam_map_score gives the same clouds and pose.
+__global__ __launch_bounds__(kScoreThreads) void k_lanes_score(LanesScoreArgs a) {
+  const int tid = threadIdx.x;
+  const uint32_t row = blockIdx.x;
+  const LaneScorePlan pl = a.plan[row / (uint32_t)a.k];
+  __shared__ double rot[6];
+  __shared__ double wsum[2][kScoreWaves];
+  __shared__ uint32_t wcnt[2][kScoreWaves][4];
+  const float* T = a.pose + (size_t)row * 6;
+  score_rot_eval(T, rot);
+  __syncthreads();
+  const loampose::MapRot R = score_rot_read(T, rot);
+  loam_score_result o;
+  o.corner_scored = o.surf_scored = o.corner_in = o.surf_in = 0;
+  o.corner_cost = o.surf_cost = 0.0;
+  unsigned long long cand = 0, cells = 0;
+  for (int tile = 0; tile < pl.tiles; ++tile) {
+    const int kind = tile < pl.tiles_c ? 0 : 1;
+    const int n = kind ? pl.nS : pl.nC, base = (kind ? tile - pl.tiles_c : tile) * kScoreTile;
+    const float4* q = a.last[kind] + (kind ? pl.offS : pl.offC);
+    float4 p[kScorePer];
+    bool use[kScorePer];
+    score_tile_load(q, n, base, p, use);
+    const ScoreMap m = {a.start[kind], a.pts[kind], a.tsize[kind]};
+    const ScorePart t = score_tile_eval(p, use, m, R, a.r2, wsum[tile & 1], wcnt[tile & 1]);
+    if (tid == 0) {
+      if (kind == 0) {
+        o.corner_scored += t.scored;
+        o.corner_in += t.in;
+        o.corner_cost += t.sum;
+      } else {
+        o.surf_scored += t.scored;
+        o.surf_in += t.in;
+        o.surf_cost += t.sum;
+      }
+      cand += t.cand;
+      cells += t.cells;
+    }
+  }
+  if (tid == 0) {
+    a.res[row] = o;
+    if (a.work) {  // (integer sums: any order)
+      atomicAdd(&a.work[0], cand);
+      atomicAdd(&a.work[1], cells);
+    }
   }
 }
 
@@ -168,6 +266,8 @@ void mp_score_free(MpScore& S) {
                   (void*)S.cnt, (void*)S.part})
     if (p) (void)hipFree(p);
   if (S.pin) (void)hipHostFree(S.pin);
+  if (S.plan_pin) (void)hipHostFree(S.plan_pin);
+  if (S.plan) (void)hipFree(S.plan);
   S = MpScore();
 }
 
@@ -227,13 +327,11 @@ hipError_t mp_score_reserve_map(MpScore& S, int nC, int nS, int ncorner, int nsu
   return e;
 }
 
-hipError_t mp_score_run(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total, int ncorner, int nsurf, float r2, int n,
-                        bool count, hipStream_t st, Prof* prof) {
-  auto mark = [&](const char* name) { if (prof) prof->mark(name); };
+hipError_t mp_score_index(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total, hipStream_t st, Prof* prof,
+                          ScoreIndex* idx) {
   const int nS = total - nC;
-  if (nC < 0 || nS < 0 || total > S.idx_pts || n < 1 || n > kScoreMax || std::max(ncorner, nsurf) > S.cloud_cap)
-    return hipErrorInvalidValue;
-  // the index: the store in canonical order (corner points, then surf points), then both tables
+  if (nC < 0 || nS < 0 || total > S.idx_pts) return hipErrorInvalidValue;
+  // the store in canonical order (corner points, then surf points), then both tables
   hipError_t e = mp_map_pack(s, io, total, st, prof);
   if (e != hipSuccess) return e;
   {
@@ -256,7 +354,20 @@ hipError_t mp_score_run(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total, 
   hash_build_pair(hc, hs, 1, st, false, true);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  mark("score_index");
+  if (prof) prof->mark("score_index");
+  idx->start[0] = hc.start; idx->start[1] = hs.start;
+  idx->pts[0] = hc.out; idx->pts[1] = hs.out;
+  idx->tsize = S.cnt + 2;
+  return hipSuccess;
+}
+
+hipError_t mp_score_run(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total, int ncorner, int nsurf, float r2, int n,
+                        bool count, hipStream_t st, Prof* prof) {
+  auto mark = [&](const char* name) { if (prof) prof->mark(name); };
+  if (n < 1 || n > kScoreMax || std::max(ncorner, nsurf) > S.cloud_cap) return hipErrorInvalidValue;
+  ScoreIndex ix;
+  hipError_t e = mp_score_index(S, s, io, nC, total, st, prof, &ix);
+  if (e != hipSuccess) return e;
   if (count) {
     e = hipMemsetAsync(S.work, 0, 2 * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
@@ -266,9 +377,9 @@ hipError_t mp_score_run(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total, 
   a.nq[0] = ncorner; a.nq[1] = nsurf;
   a.tiles_c = score_tiles(ncorner);
   a.tiles = a.tiles_c + score_tiles(nsurf);
-  a.start[0] = hc.start; a.start[1] = hs.start;
-  a.pts[0] = hc.out; a.pts[1] = hs.out;
-  a.tsize = S.cnt + 2;
+  a.start[0] = ix.start[0]; a.start[1] = ix.start[1];
+  a.pts[0] = ix.pts[0]; a.pts[1] = ix.pts[1];
+  a.tsize = ix.tsize;
   a.pose = S.pose;
   a.r2 = r2;
   if (a.tiles == 0) {  // two empty clouds: every result is zero
@@ -294,6 +405,69 @@ hipError_t mp_score_run(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total, 
   if (e == hipSuccess && count)
     e = hipMemcpyAsync(S.work_h(), S.work, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
   mark("map_score_d2h");
+  return e;
+}
+
+hipError_t mp_score_reserve_plan(MpScore& S, int lanes) {
+  if (lanes <= S.plan_lanes && S.plan_pin && S.plan) return hipSuccess;
+  if (S.plan_pin) (void)hipHostFree(S.plan_pin);
+  if (S.plan) (void)hipFree(S.plan);
+  S.plan_pin = nullptr;
+  S.plan = nullptr;
+  S.plan_lanes = 0;
+  const size_t bytes = (size_t)lanes * (kOdBufs * 2 * sizeof(int) + sizeof(LaneScorePlan));
+  hipError_t e = hipHostMalloc((void**)&S.plan_pin, bytes, hipHostMallocDefault);
+  if (e != hipSuccess) {
+    S.plan_pin = nullptr;
+    return e;
+  }
+  e = hipMalloc((void**)&S.plan, (size_t)lanes * sizeof(LaneScorePlan));
+  if (e != hipSuccess) {
+    (void)hipHostFree(S.plan_pin);
+    S.plan_pin = nullptr;
+    S.plan = nullptr;
+    return e;
+  }
+  S.plan_lanes = lanes;
+  return hipSuccess;
+}
+
+hipError_t mp_lanes_score_run(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total, const float4* lastC,
+                              const float4* lastS, const LaneScoreShape& shape, int n, int k, float r2, bool count,
+                              hipStream_t st, Prof* prof) {
+  auto mark = [&](const char* name) { if (prof) prof->mark(name); };
+  if (n < 1 || n > S.plan_lanes || k < 1 || (uint64_t)n * (uint64_t)k != shape.grid_x || shape.grid_x > (uint32_t)kScoreMax)
+    return hipErrorInvalidValue;
+  mark("lanes_score_host_wait");  // (the host's planning since the sizes came down)
+  hipError_t e = hipMemcpyAsync(S.plan, S.plan_h(), (size_t)n * sizeof(LaneScorePlan), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  mark("lanes_score_h2d");
+  ScoreIndex ix;
+  e = mp_score_index(S, s, io, nC, total, st, prof, &ix);
+  if (e != hipSuccess) return e;
+  if (count) {
+    e = hipMemsetAsync(S.work, 0, 2 * sizeof(unsigned long long), st);
+    if (e != hipSuccess) return e;
+  }
+  LanesScoreArgs a;
+  a.last[0] = lastC; a.last[1] = lastS;
+  a.plan = S.plan;
+  a.start[0] = ix.start[0]; a.start[1] = ix.start[1];
+  a.pts[0] = ix.pts[0]; a.pts[1] = ix.pts[1];
+  a.tsize = ix.tsize;
+  a.pose = S.pose;
+  a.r2 = r2;
+  a.k = k;
+  a.res = S.res;
+  a.work = count ? S.work : nullptr;
+  hipLaunchKernelGGL(k_lanes_score, dim3(shape.grid_x), dim3(kScoreThreads), 0, st, a);
+  mark("k_lanes_score");
+  e = hipGetLastError();
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(S.res_h(), S.res, (size_t)shape.grid_x * sizeof(loam_score_result), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && count)
+    e = hipMemcpyAsync(S.work_h(), S.work, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+  mark("lanes_score_d2h");
   return e;
 }
 

@@ -14,6 +14,7 @@
 
 #include "dev_common.hpp"
 #include "mp.hpp"
+#include "od.hpp"
 
 namespace loam {
 
@@ -86,6 +87,53 @@ struct ScorePart {
 };
 static_assert(sizeof(ScorePart) == 24, "ScorePart layout");
 
+// ---- loam_lanes_score: k poses for each of n listed lanes, the lanes' Last clouds read in place
+// one listed lane of a call: where its Last clouds lie (elements from OdBuffers::lastC / lastS),
+// their sizes and tiles (corner tiles first, as k_mp_score has them)
+struct LaneScorePlan {
+  uint64_t offC, offS;
+  int32_t nC, nS;
+  int32_t tiles_c, tiles;
+};
+static_assert(sizeof(LaneScorePlan) == 32, "LaneScorePlan layout");
+// the launch: one workgroup per (listed lane, pose) on x (gridDim.y stops at 65 535)
+struct LaneScoreShape {
+  uint32_t grid_x;   // n x k rows
+  uint64_t tiles;    // tile bodies of the launch: k x the listed lanes' tiles
+};
+enum { kLanePlanOk = 0, kLanePlanN, kLanePlanK, kLanePlanRows, kLanePlanCap, kLanePlanLane, kLanePlanCount };
+// loam_lanes_score's launch arithmetic (host only): kLanePlanOk and plan[0..n) / shape, or which
+// limit the arguments break (nothing is written then).  lane[i] < P is listed lane i, cnt[2 i] /
+// cnt[2 i + 1] the corner / surf count of its Last clouds in buffer buf of [kOdBufs][P][capC | capS].
+// Every product is formed in 64 bits; a cloud's last tile must index below 2^31.
+inline int lanes_score_plan(uint32_t n, uint32_t k, const uint32_t* lane, const int32_t* cnt, uint32_t P, uint32_t buf,
+                            int32_t capC, int32_t capS, LaneScorePlan* plan, LaneScoreShape* shape) {
+  if (n == 0 || n > P) return kLanePlanN;
+  if (k == 0) return kLanePlanK;
+  if ((uint64_t)n * (uint64_t)k > (uint64_t)kScoreMax) return kLanePlanRows;
+  const int64_t cap_max = ((int64_t)1 << 31) - kScoreTile;  // (a tile's base + kScoreTile - 1 is an int)
+  if (capC < 0 || capS < 0 || capC >= cap_max || capS >= cap_max || buf >= (uint32_t)kOdBufs) return kLanePlanCap;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (lane[i] >= P) return kLanePlanLane;
+    if (cnt[2 * i] < 0 || cnt[2 * i] > capC || cnt[2 * i + 1] < 0 || cnt[2 * i + 1] > capS) return kLanePlanCount;
+  }
+  uint64_t tiles = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    LaneScorePlan& p = plan[i];
+    const uint64_t slot = (uint64_t)buf * P + lane[i];
+    p.offC = slot * (uint64_t)capC;
+    p.offS = slot * (uint64_t)capS;
+    p.nC = cnt[2 * i];
+    p.nS = cnt[2 * i + 1];
+    p.tiles_c = (int32_t)(((int64_t)p.nC + kScoreTile - 1) / kScoreTile);
+    p.tiles = p.tiles_c + (int32_t)(((int64_t)p.nS + kScoreTile - 1) / kScoreTile);
+    tiles += (uint64_t)p.tiles;
+  }
+  shape->grid_x = n * k;
+  shape->tiles = tiles * (uint64_t)k;
+  return kLanePlanOk;
+}
+
 // the call's working set: allocated on demand, grown, kept until loam_destroy
 struct MpScore {
   int cloud_cap = 0;        // query points per cloud q holds
@@ -105,6 +153,14 @@ struct MpScore {
   int* cnt = nullptr;       // [4] corner, surf counts | their table sizes
   ScorePart* part = nullptr;  // [part_cap] a chunk of candidates x tiles
   size_t part_cap = 0;
+  // loam_lanes_score's plan block (allocated by the first call, regrown when lanes with more lanes
+  // are opened): pinned, the lanes' nlast words as they come down ([plan_lanes][kOdBufs][2]) and
+  // the listed lanes' LaneScorePlan entries as they go up; device, those entries
+  int plan_lanes = 0;
+  char* plan_pin = nullptr;
+  LaneScorePlan* plan = nullptr;  // device [plan_lanes]
+  int* nlast_h() const { return (int*)plan_pin; }
+  LaneScorePlan* plan_h() const { return (LaneScorePlan*)(plan_pin + (size_t)plan_lanes * kOdBufs * 2 * sizeof(int)); }
 };
 void mp_score_free(MpScore& S);
 // the tables, and room for clouds of up to cloud_max points each; then the index for a map of
@@ -119,6 +175,26 @@ hipError_t mp_score_reserve_map(MpScore& S, int nC, int nS, int ncorner, int nsu
 // work counters into S.work_h()): the caller synchronises st, then reads them
 hipError_t mp_score_run(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total, int ncorner, int nsurf, float r2, int n,
                         bool count, hipStream_t st, Prof* prof);
+
+// both kinds' indexes as the scoring kernels read them
+struct ScoreIndex {
+  const int* start[2];
+  const float4* pts[2];
+  const int* tsize;  // [2]
+};
+// the index mp_score_run and mp_lanes_score_run share: the store of s packed into s.vin in
+// canonical order, both kinds hashed into 1 m cells (mp_score_reserve_map made room)
+hipError_t mp_score_index(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total, hipStream_t st, Prof* prof,
+                          ScoreIndex* idx);
+// loam_lanes_score's plan block for `lanes` lanes; frees what it replaces (nothing enqueued reads it)
+hipError_t mp_score_reserve_plan(MpScore& S, int lanes);
+// n listed lanes (their entries in S.plan_h()) x k poses (S.pose, row i k + j) scored on the lanes'
+// Last clouds in place (lastC / lastS: OdBuffers' bases) against the store of s, indexed as
+// mp_score_run does; the n k results into S.res_h(), with `count` the work counters into
+// S.work_h(): the caller synchronises st, then reads them
+hipError_t mp_lanes_score_run(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total, const float4* lastC,
+                              const float4* lastS, const LaneScoreShape& shape, int n, int k, float r2, bool count,
+                              hipStream_t st, Prof* prof);
 
 }  // namespace loam
 #endif

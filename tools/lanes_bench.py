@@ -3,7 +3,8 @@ stepped by loam_chain_sweep from one thread, through the C-ABI on one GPU (DESIG
 
   python tools/lanes_bench.py [--s 1,16,64] [--sweeps 27] [--map-cap 131072] [--yard-max 1024]
                               [--profile-s 64] [--imu] [--restart K,M] [--occupancy N] [--map-import N]
-                              [--surround] [--shared stream|big [--from-cap F]] [--out FILE]
+                              [--surround] [--shared stream|big [--from-cap F]]
+                              [--score stream|big [--k K1,K2]] [--out FILE]
 
 Per S: S lanes over eight distinct VLP-16 synthetic streams laid out cyclically.  The wall time of
 lanes_step (push + pull), and of the push alone (host packing + enqueue), median and range over the
@@ -66,7 +67,16 @@ map: what a context builds over stream 1 in --sweeps sweeps, or tools/localize_b
 the wall time of lanes_step after the warm-up, mapping steps and the others apart, the lanes that
 failed, and on the shared side the largest FromMap a lane gathered.  An open that fails is reported
 (opens = false), not an error.  --profile-s S: one more shared run at that S under
-loam_set_profiling, the device time per kernel and step and per launch."""
+loam_set_profiling, the device time per kernel and step and per launch.
+
+--score stream|big (instead of the above): shared lanes in that map; S from --s and k
+from --k are paired by position (64,1024 with 256,64: the shapes 64 x 256 and 1024 x 64).  Per shape,
+k pose guesses for every lane's last sweep scored both ways on the same context, alternating three
+times: one loam_lanes_score call, and the parent's only way, S loam_map_score calls of k poses each
+with the lane's Last clouds handed in from host memory (obtained from node-call contexts, which is
+not timed).  max_dist 0.5; wall time per way, median and range of 5 after a warm-up; one more call of
+each under loam_set_profiling for the device time per kernel; sampled rows of both ways compared bit
+for bit."""
 import argparse
 import importlib
 import json
@@ -585,6 +595,81 @@ def run_shared(S, streams, K, name, M, from_cap, pairs=3, profile=False):
     return line
 
 
+def _profiled(eng, call):
+    """device ms per kernel and the work counters of one call under loam_set_profiling"""
+    eng.set_profiling(True)
+    before = eng.kernel_times()
+    call()
+    after = eng.kernel_times()
+    eng.set_profiling(False)
+    return {k: round(v[0] - before.get(k, (0.0, 0))[0], 4) for k, v in sorted(after.items())
+            if v[1] != before.get(k, (0.0, 0))[1]}
+
+
+def run_score(S, k, streams, name, M, from_cap, pairs=3, reps=5):
+    """one JSON line: k poses for each of S shared lanes in the map M, loam_lanes_score against S
+    loam_map_score calls on the same context, `pairs` alternating timings"""
+    kw = dict(corner=M["corner"], surf=M["surf"], center=M["center"], surround_phase=4)
+    total = int(M["corner"].shape[0] + M["surf"].shape[0])
+    eng = loam.Engine(loam.default_config(system_delay=1, map_capacity=max(1 << 17, 1 << int(np.ceil(np.log2(total))))))
+    eng.set_tuning(batch_streams=0)
+    eng.map_import(**kw)
+    eng.lanes_open_shared(S, from_cap)
+    eng.lanes_set_pose(list(range(S)), np.zeros(6, np.float32))
+    n_steps = 3
+    for j in range(n_steps):
+        o = eng.lanes_step([streams[l % N_STREAMS][j] for l in range(S)], stamp=0.1 * j)
+    # the yardstick's clouds (not timed): every stream's Last clouds of that step from a node-call context
+    last = []
+    for i in range(min(S, N_STREAMS)):
+        A = loam.Engine(loam.default_config(system_delay=1, skip_frame_num=0))
+        for j in range(n_steps):
+            rc, f = A.scan_registration(streams[i][j], stamp=0.1 * j)
+            if rc == 0:
+                _, _, cl, sl, _ = A.odometry(f, stamp=0.1 * j)
+        A.close()
+        last.append((cl, sl))
+    rng = np.random.default_rng(31)
+    P = (rng.uniform(-1, 1, (k, 6)) * np.array([0.05, 0.05, 0.05, 0.5, 0.5, 0.5])).astype(np.float32)
+    lanes = list(range(S))
+
+    def new():
+        return eng.lanes_score(lanes, P, 0.5)
+
+    def yard():
+        return [eng.map_score(*last[l % N_STREAMS], P, 0.5) for l in lanes]
+
+    def timed(call):
+        call()  # warm-up
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            call()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return spread(ts)
+    runs = [dict(lanes_score_ms=timed(new), map_score_calls_ms=timed(yard)) for _ in range(pairs)]
+    got, want = new(), yard()
+    same = all(np.array_equal(got[key][l].view(np.uint64 if got[key].dtype == np.float64 else np.uint32),
+                              want[l][key].view(np.uint64 if got[key].dtype == np.float64 else np.uint32))
+               for key in loam.SCORE_KEYS for l in sorted({0, S // 2, S - 1}))
+    line = dict(score_leg=name, S=S, k=k, rows=S * k, map_points=total, max_dist=0.5,
+                lanes_failed=int(np.count_nonzero(o["status"] != 0)),
+                query_points_per_lane=int(np.mean([c.shape[0] + s_.shape[0] for c, s_ in last])), pairs=runs,
+                new_below_yardstick=[bool(r["lanes_score_ms"]["median"] < r["map_score_calls_ms"]["median"]) for r in runs],
+                yardstick_over_new=[round(r["map_score_calls_ms"]["median"] / r["lanes_score_ms"]["median"], 2) for r in runs],
+                sampled_rows_equal=bool(same))
+    line["device_ms_lanes_score"] = _profiled(eng, new)
+    line["device_ms_map_score_calls"] = _profiled(eng, yard)
+    dn, dy = line["device_ms_lanes_score"], line["device_ms_map_score_calls"]
+    idx = ("score_index", "k_mp_map_pack", "k_mp_map_table")
+    line["index_ms_new"] = round(sum(dn.get(n, 0.0) for n in idx), 4)
+    line["index_ms_yardstick"] = round(sum(dy.get(n, 0.0) for n in idx), 4)
+    line["index_share_of_yardstick_wall"] = round(line["index_ms_yardstick"] / runs[-1]["map_score_calls_ms"]["median"], 3)
+    eng.lanes_close()
+    eng.close()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--s", default="1,16,64")
@@ -600,8 +685,11 @@ def main():
     ap.add_argument("--shared", default=None, help="stream|big: shared lanes against own-store lanes in that map")
     ap.add_argument("--from-cap", type=int, default=0,
                     help="--shared: lane_from_capacity (0: the power of two that holds the stream map, 65536 in the big map)")
+    ap.add_argument("--score", default=None, help="stream|big: loam_lanes_score against S loam_map_score calls in that map")
+    ap.add_argument("--k", default="256,64", help="--score: poses per lane, paired with --s by position")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.shared = a.shared or a.score
     K = 40 if a.occupancy else 23 if a.surround else a.sweeps
     streams = [sg.stream_sweeps(K, 1 + i) for i in range(N_STREAMS)]
     imu = imu_schedules(K) if a.imu else None
@@ -632,6 +720,10 @@ def main():
         # (a lane in the stream map sees all of it: the smallest power of two that holds the map)
         total = int(M["corner"].shape[0] + M["surf"].shape[0])
         F = a.from_cap or (65536 if a.shared == "big" else 1 << int(np.ceil(np.log2(max(total, 1024)))))
+        if a.score:
+            for S, k in zip([int(v) for v in a.s.split(",") if v], [int(v) for v in a.k.split(",") if v]):
+                emit(run_score(S, k, streams, a.score, M, F))
+            return
         for S in [int(v) for v in a.s.split(",") if v]:
             emit(run_shared(S, streams, K, a.shared, M, F, profile=S == a.profile_s))
         return
