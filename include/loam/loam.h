@@ -639,6 +639,33 @@ int loam_lanes_localize_info(loam_ctx *ctx, loam_localize_result *out /* [n_lane
  * last update overflowed map_capacity.  LOAM_E_NOMEM / LOAM_E_HIP as loam_map_score. */
 int loam_lanes_score(loam_ctx *ctx, uint32_t n, const uint32_t *lane /* [n] */, float max_dist,
                      uint32_t k, const loam_pose6 *pose /* [n][k] */, loam_score_result *out /* [n][k] */);
+
+/* loam_map_localize for the lanes, between two steps, in both lane modes: k candidate poses for each
+ * of n listed lanes, each lane's candidates refined for that lane's own last sweep, all n x k in one
+ * launch sequence.  out[i*k + j], i < n, j < k, is bit for bit (all 60 bytes) what
+ * loam_map_localize(ctx, &Sum, C, S, 1, &aft[i*k + j], bef ? &bef[i*k + j] : NULL, ..) returns on
+ * this context, where C / S are lane lane[i]'s laserCloudCornerLast / laserCloudSurfLast as its last
+ * pulled frame left them (the clouds loam_lanes_score reads) and Sum is the lane's transformSum: the
+ * od_sum the pull reported on a frame with LOAM_PUB_POSE.  All three are read in place on the device.
+ * A row depends on the map, the lane's clouds and Sum, and its own (aft, bef) only: not on n, k, its
+ * position in the call, or the run.  The map is the context's streaming map, as for loam_lanes_score.
+ * As in loam_map_localize no IMU blend is applied: for a lane that receives IMU messages a row is
+ * therefore not what the lane's own shared step computes from the same poses.  Only the batch forms
+ * of the L-M run, never the persistent one-instance kernels.
+ * The call waits for the context's queued work (a deferred map update included), writes nothing but
+ * the localization working set it shares with loam_map_localize (grown on demand, kept until
+ * loam_destroy), changes nothing in the map or in any lane, and may be repeated.  To use a result,
+ * hand its aft to loam_lanes_set_pose with bef = the lane's od_sum.
+ * LOAM_E_INVAL, with out untouched: a null ctx / lane / aft / out (bef may be NULL = zeros), lanes
+ * not open, a step in flight, no pulled step yet on which the odometry was initialised, n == 0 or
+ * n > n_lanes, k == 0, n x k > LOAM_LOCALIZE_MAX, a lane index >= n_lanes, a lane listed twice, a
+ * failed lane, a lane between loam_lanes_restart and the pull of its init step, a listed lane whose
+ * corner cloud exceeds the mapping stack's 120 points per ring, a map whose last update overflowed
+ * map_capacity.  LOAM_E_NOMEM / LOAM_E_HIP as loam_map_localize.  In every error case the context
+ * and the lanes are as they were. */
+int loam_lanes_localize(loam_ctx *ctx, uint32_t n, const uint32_t *lane /* [n] */, uint32_t k,
+                        const loam_pose6 *aft /* [n][k] */, const loam_pose6 *bef /* [n][k] or NULL = zeros */,
+                        loam_localize_result *out /* [n][k] */);
 /* Frees the lanes' working set (waits for a step in flight).  LOAM_E_INVAL when not open. */
 int loam_lanes_close(loam_ctx *ctx);
 

@@ -197,6 +197,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
            "loam_lanes_restart", "loam_lanes_map_import", "loam_lanes_surround",
            "loam_lanes_open_shared", "loam_lanes_set_pose", "loam_lanes_localize_info", "loam_lanes_score",
+           "loam_lanes_localize",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -263,6 +264,8 @@ def lib():
         L.loam_lanes_localize_info.argtypes = [PP, P(LocalizeResult)]
         L.loam_lanes_score.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), ctypes.c_float, ctypes.c_uint32, P(Pose6),
                                        P(ScoreResult)]
+        L.loam_lanes_localize.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), ctypes.c_uint32, P(Pose6), P(Pose6),
+                                          P(LocalizeResult)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -723,23 +726,76 @@ class Engine:
                                       rec.ctypes.data_as(ctypes.POINTER(ScoreResult))))
         return {key: rec[key][:n * k].reshape(n, k).copy() for key in SCORE_KEYS}
 
-    def lanes_relocalize(self, lanes, poses, od_sum, max_dist=1.0):
+    def lanes_localize(self, lanes, aft, bef=None):
+        """candidate poses for the listed lanes' own last sweeps refined against the context's map in
+        one call (loam_lanes_localize): aft (n, k, 6), or (k, 6) used for every listed lane; bef the
+        same shapes, or None = zeros.  Returns map_localize's dict with arrays of shape (n, k), and
+        (n, k, 6) for aft: row [i, j] is what map_localize gives lane lanes[i]'s od_sum, corner_last
+        and surf_last at (aft[i, j], bef[i, j]).  n x k <= LOCALIZE_MAX."""
+        lanes = [int(l) for l in np.atleast_1d(lanes)]
+        n = len(lanes)
+        a = _lane_poses(n, aft)
+        k = a.shape[1]
+        P = ctypes.POINTER(Pose6)
+        pb = None
+        if bef is not None:
+            b = _lane_poses(n, bef)
+            if b.shape != a.shape:
+                raise ValueError("aft and bef must hold the same number of candidates per lane")
+            pb = b.ctypes.data_as(P)
+        idx = (ctypes.c_uint32 * max(n, 1))(*lanes)
+        rec = np.zeros(max(n * k, 1), _LOC_DTYPE)
+        _check(lib().loam_lanes_localize(self.h, n, idx, k, a.ctypes.data_as(P), pb,
+                                         rec.ctypes.data_as(ctypes.POINTER(LocalizeResult))))
+        return {key: rec[key][:n * k].reshape((n, k) + rec[key].shape[1:]).copy() for key in LOCALIZE_KEYS}
+
+    def lanes_relocalize(self, lanes, poses, od_sum, max_dist=1.0, refine=0):
         """re-seeds the listed shared lanes in the map: scores the guesses (lanes_score), takes each
         lane's best row by score_order and gives it to the lane with lanes_set_pose(aft = the chosen
         guess, bef = od_sum[lane]), od_sum being the last lanes_pull / lanes_step output's (n_lanes,
         6) array, so that only later odometry increments are applied on top.  Returns a dict: index
-        (n,) the chosen rows, aft (n, 6) the chosen guesses, score (map_score's keys, (n,) each)."""
+        (n,) the chosen rows, aft (n, 6) the chosen guesses, score (map_score's keys, (n,) each).
+        refine = m >= 1 (m x n <= LOCALIZE_MAX): relocalize's chain per lane.  Each lane's best m
+        guesses by score_order are refined with lanes_localize(aft = the guesses, bef =
+        od_sum[lane]), the LOC_SOLVED refined poses are scored again (a row that was not solved
+        keeps its coarse score), and the lane gets the refined aft of its best fine row.  index is
+        then (n,) that row of `poses`, aft its refined pose, score its fine score, and the dict also
+        holds localize (lanes_localize's result), coarse and fine (map_score's keys), each (n, m)
+        in the lanes' coarse order, with rows (n, m) = their rows of `poses`."""
         lanes = [int(l) for l in np.atleast_1d(lanes)]
         n = len(lanes)
         p = _lane_poses(n, poses)
         od_sum = np.asarray(od_sum, np.float32)
         if od_sum.ndim != 2 or od_sum.shape != (self.n_lanes, 6):
             raise ValueError("od_sum: the (n_lanes, 6) array of the last pulled step")
+        m = int(refine)
+        if m < 0 or m * n > LOCALIZE_MAX:
+            raise ValueError("refine x the listed lanes must be in [0, LOCALIZE_MAX]")
         score = self.lanes_score(lanes, p, max_dist)
-        index = np.array([score_order({key: v[i] for key, v in score.items()})[0] for i in range(n)], np.int64)
-        aft = np.ascontiguousarray(p[np.arange(n), index])
-        self.lanes_set_pose(lanes, aft, np.ascontiguousarray(od_sum[lanes]))
-        return {"index": index, "aft": aft, "score": {key: v[np.arange(n), index] for key, v in score.items()}}
+        order = [score_order({key: v[i] for key, v in score.items()}) for i in range(n)]
+        bef = np.ascontiguousarray(od_sum[lanes])
+        ar = np.arange(n)
+        if m == 0:
+            index = np.array([o[0] for o in order], np.int64)
+            aft = np.ascontiguousarray(p[ar, index])
+            self.lanes_set_pose(lanes, aft, bef)
+            return {"index": index, "aft": aft, "score": {key: v[ar, index] for key, v in score.items()}}
+        m = min(m, p.shape[1])
+        rows = np.stack([o[:m] for o in order])  # (n, m)
+        guess = np.ascontiguousarray(p[ar[:, None], rows])
+        loc = self.lanes_localize(lanes, guess, np.ascontiguousarray(np.broadcast_to(bef[:, None, :], guess.shape)))
+        coarse = {key: v[ar[:, None], rows] for key, v in score.items()}
+        fine = {key: v.copy() for key, v in coarse.items()}
+        ok = loc["status"] == LOC_SOLVED
+        if ok.any():  # (one call scores every row; the rows that were not solved keep their coarse score)
+            s = self.lanes_score(lanes, loc["aft"], max_dist)
+            for key in SCORE_KEYS:
+                fine[key][ok] = s[key][ok]
+        best = np.array([score_order({key: v[i] for key, v in fine.items()}, rows[i])[0] for i in range(n)], np.int64)
+        aft = np.ascontiguousarray(loc["aft"][ar, best])
+        self.lanes_set_pose(lanes, aft, bef)
+        return {"index": rows[ar, best], "aft": aft, "score": {key: v[ar, best] for key, v in fine.items()},
+                "rows": rows, "localize": loc, "coarse": coarse, "fine": fine}
 
     def lanes_close(self):
         _check(lib().loam_lanes_close(self.h))

@@ -2122,6 +2122,22 @@ extern "C" int loam_map_import(loam_ctx* x, const loam_map* in, uint64_t* droppe
 }
 
 // ------------------------------------------------------------------ multi-hypothesis localization
+namespace {
+// a k_mp_loc_result block as the C-ABI hands it out
+void loc_result_of(const int* r, loam_localize_result& o) {
+  std::memcpy(&o.aft, r + kLrAft, sizeof(loam_pose6));
+  o.status = r[kLrStatus];
+  o.iters = r[kLrIters];
+  o.degenerate_steps = r[kLrDegSteps];
+  o.rows_last = (uint32_t)r[kLrRowsLast];
+  o.rows_sum = (uint32_t)r[kLrRowsSum];
+  o.stack_corner = (uint32_t)r[kLrStackC];
+  o.stack_surf = (uint32_t)r[kLrStackS];
+  o.map_corner = (uint32_t)r[kLrMapC];
+  o.map_surf = (uint32_t)r[kLrMapS];
+}
+}  // namespace
+
 // n candidate (Aft, Bef) poses of one sweep against the streaming map, which is only read: every
 // candidate is an instance of the context's second mapping working set (MpLoc, mp.hpp).  The host
 // reads the candidates' FromMap counts once (to size the set), then the results.
@@ -2207,20 +2223,7 @@ extern "C" int loam_map_localize(loam_ctx* x, const loam_pose6* odom_sum, const 
   }
   x->prof.collect();
   const int* R = L.res_h();
-  for (uint32_t h = 0; h < n; ++h) {
-    const int* r = R + (size_t)h * kLocResWords;
-    loam_localize_result& o = out[h];
-    std::memcpy(&o.aft, r + kLrAft, sizeof(loam_pose6));
-    o.status = r[kLrStatus];
-    o.iters = r[kLrIters];
-    o.degenerate_steps = r[kLrDegSteps];
-    o.rows_last = (uint32_t)r[kLrRowsLast];
-    o.rows_sum = (uint32_t)r[kLrRowsSum];
-    o.stack_corner = (uint32_t)r[kLrStackC];
-    o.stack_surf = (uint32_t)r[kLrStackS];
-    o.map_corner = (uint32_t)r[kLrMapC];
-    o.map_surf = (uint32_t)r[kLrMapS];
-  }
+  for (uint32_t h = 0; h < n; ++h) loc_result_of(R + (size_t)h * kLocResWords, out[h]);
   return LOAM_OK;
 }
 
@@ -2459,15 +2462,9 @@ extern "C" int loam_lanes_open_shared(loam_ctx* x, uint32_t n_lanes, uint32_t la
   return LOAM_OK;
 }
 
-extern "C" int loam_lanes_set_pose(loam_ctx* x, uint32_t n, const uint32_t* lane, const loam_pose6* aft,
-                                   const loam_pose6* bef) {
-  if (!x || !lane || !aft) return fail(LOAM_E_INVAL, "null argument");
-  const std::string who = "loam_lanes_set_pose";
-  Lanes& L = x->lanes;
-  if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
-  if (!L.shared) return fail(LOAM_E_INVAL, who + ": the lanes have their own maps (loam_lanes_open); use loam_lanes_map_import");
-  if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
-  if (n == 0 || n > (uint32_t)L.S) return fail(LOAM_E_INVAL, who + ": n must be in [1, n_lanes]");
+namespace {
+// lanes_list_check's four rules with their messages: LOAM_OK, or the failure
+int lanes_list_refused(const std::string& who, const Lanes& L, const uint32_t* lane, uint32_t n) {
   std::vector<char> seen;
   uint32_t bad = 0;
   const int why = lanes_list_check(lane, n, L.S, L.fail.data(), L.life.data(), seen, &bad);
@@ -2478,6 +2475,20 @@ extern "C" int loam_lanes_set_pose(loam_ctx* x, uint32_t n, const uint32_t* lane
     if (why == kLaneListFailed) return fail(LOAM_E_INVAL, at + " has failed (loam_lanes_restart first)");
     return fail(LOAM_E_INVAL, at + " waits for its init step (the restart's clear would overwrite the pose)");
   }
+  return LOAM_OK;
+}
+}  // namespace
+
+extern "C" int loam_lanes_set_pose(loam_ctx* x, uint32_t n, const uint32_t* lane, const loam_pose6* aft,
+                                   const loam_pose6* bef) {
+  if (!x || !lane || !aft) return fail(LOAM_E_INVAL, "null argument");
+  const std::string who = "loam_lanes_set_pose";
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
+  if (!L.shared) return fail(LOAM_E_INVAL, who + ": the lanes have their own maps (loam_lanes_open); use loam_lanes_map_import");
+  if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
+  if (n == 0 || n > (uint32_t)L.S) return fail(LOAM_E_INVAL, who + ": n must be in [1, n_lanes]");
+  if (const int rc = lanes_list_refused(who, L, lane, n)) return rc;
   HIP_TRY(hipSetDevice(x->device));
   if (lanes_set_pose_alloc(L) != hipSuccess) {
     (void)hipGetLastError();
@@ -2526,16 +2537,7 @@ extern "C" int loam_lanes_score(loam_ctx* x, uint32_t n, const uint32_t* lane, f
     return fail(LOAM_E_INVAL, who + ": n x k must not exceed LOAM_SCORE_MAX");
   if (!(max_dist > 0.0f && max_dist <= 1.0f))
     return fail(LOAM_E_INVAL, who + ": max_dist must be in (0, 1] (the map index has 1 m cells)");
-  std::vector<char> seen;
-  uint32_t bad = 0;
-  const int why = lanes_list_check(lane, n, L.S, L.fail.data(), L.life.data(), seen, &bad);
-  if (why != kLaneListOk) {
-    const std::string at = who + ": lane[" + std::to_string(bad) + "] = " + std::to_string(lane[bad]);
-    if (why == kLaneListRange) return fail(LOAM_E_INVAL, at + " is out of range");
-    if (why == kLaneListTwice) return fail(LOAM_E_INVAL, at + " is listed twice");
-    if (why == kLaneListFailed) return fail(LOAM_E_INVAL, at + " has failed (loam_lanes_restart first)");
-    return fail(LOAM_E_INVAL, at + " waits for its init step (the restart's clear would overwrite the pose)");
-  }
+  if (const int rc = lanes_list_refused(who, L, lane, n)) return rc;
   int rc = map_drain(x);
   if (rc) return rc;
   MpBuffers& b = x->mp1;
@@ -2611,6 +2613,120 @@ extern "C" int loam_lanes_score(loam_ctx* x, uint32_t n, const uint32_t* lane, f
     }
   }
   std::memcpy(out, S.res_h(), rows * sizeof(loam_score_result));
+  return LOAM_OK;
+}
+
+// k candidate poses for each of n listed lanes refined for the lane's own last sweep:
+// loam_map_localize's sequence with every row's clouds and transformSum read in place from the row's
+// lane.  Three synchronisations: the lanes' nlast words (they size the rows' stacks), the rows'
+// FromMap counts (they size the FromMap part), the results.
+extern "C" int loam_lanes_localize(loam_ctx* x, uint32_t n, const uint32_t* lane, uint32_t k, const loam_pose6* aft,
+                                   const loam_pose6* bef, loam_localize_result* out) {
+  static_assert(kLocPlanRows == (uint32_t)kLocMax && kLocPlanBufs == (uint32_t)kOdBufs, "loc_plan.hpp and mp.hpp / od.hpp");
+  static_assert(LOAM_LANES_MAX <= kLocMax, "MpLoc's plan block holds every lane's nlast words");
+  if (!x || !lane || !aft || !out) return fail(LOAM_E_INVAL, "null argument");
+  const std::string who = "loam_lanes_localize";
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
+  if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
+  if (!L.pulled || !L.od_inited)
+    return fail(LOAM_E_INVAL, who + ": no step was pulled on which the odometry was initialised (no Last clouds yet)");
+  if (n == 0 || n > (uint32_t)L.S) return fail(LOAM_E_INVAL, who + ": n must be in [1, n_lanes]");
+  if (k == 0) return fail(LOAM_E_INVAL, who + ": k must be at least 1");
+  if ((uint64_t)n * (uint64_t)k > (uint64_t)LOAM_LOCALIZE_MAX)
+    return fail(LOAM_E_INVAL, who + ": n x k must not exceed LOAM_LOCALIZE_MAX");
+  if (const int rc = lanes_list_refused(who, L, lane, n)) return rc;
+  int rc = map_drain(x);
+  if (rc) return rc;
+  const MpBuffers& s = x->mp1;
+  MpLoc& Lc = x->loc;
+  const OdBuffers& o = L.od;
+  hipStream_t st = x->st;
+  hipError_t he = mp_loc_reserve_rows(Lc);
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LOAM_E_NOMEM, who + ": working set allocation failed: " + hipGetErrorString(he));
+  }
+  x->prof.begin(st);
+  he = hipMemcpyAsync(Lc.nlast_h(), o.nlast, (size_t)L.S * kOdBufs * 2 * sizeof(int), hipMemcpyDeviceToHost, st);
+  x->prof.mark("lanes_localize_d2h");
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    x->prof.collect();
+    return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
+  }
+  std::vector<int32_t> cnt((size_t)2 * n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const int* w = Lc.nlast_h() + ((size_t)lane[i] * kOdBufs + L.od_last) * 2;
+    cnt[2 * i] = w[0];
+    cnt[2 * i + 1] = w[1];
+  }
+  LaneLocShape shape;
+  const int plan = lanes_localize_plan(n, k, lane, cnt.data(), (uint32_t)L.S, (uint32_t)L.od_last, o.capC, o.capS, s.capC,
+                                       Lc.plan_h(), &shape);
+  if (plan != kLocPlanOk) {
+    x->prof.collect();
+    if (plan == kLocPlanStack)
+      return fail(LOAM_E_INVAL, who + ": a listed lane's corner cloud exceeds the mapping stack (120 points per ring)");
+    return fail(LOAM_E_HIP, who + ": a lane's Last cloud sizes are not valid (plan code " + std::to_string(plan) + ")");
+  }
+  const int rows = (int)shape.rows;
+  he = mp_loc_reserve(Lc, s, rows, shape.maxC, shape.maxS);
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    x->prof.collect();
+    return fail(LOAM_E_NOMEM, who + ": working set allocation failed: " + hipGetErrorString(he));
+  }
+  Prof* pf = x->prof.on ? &x->prof : nullptr;  // (with profiling the L-M kernels also count their work)
+  float* ch = Lc.cand_h();
+  for (int h = 0; h < rows; ++h) {
+    std::memcpy(ch + (size_t)h * 12, &aft[h], sizeof(loam_pose6));
+    if (bef) std::memcpy(ch + (size_t)h * 12 + 6, &bef[h], sizeof(loam_pose6));
+    else std::memset(ch + (size_t)h * 12 + 6, 0, sizeof(loam_pose6));
+  }
+  LocRows lr;
+  lr.plan = Lc.plan;
+  lr.k = (int)k;
+  lr.lastC = o.lastC;
+  lr.lastS = o.lastS;
+  lr.od_state = o.state;
+  const MpInput none = {};  // (the rows kernels read the lanes' clouds through the plan)
+  he = mp_localize_prepare(Lc, s, none, rows, st, pf, &lr);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    x->prof.collect();
+    return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
+  }
+  const int* head = Lc.head_h();
+  if (head[2 * rows] & ERR_CAP_MAP) {
+    x->prof.collect();
+    return fail(LOAM_E_INVAL, who + ": the last map update exceeded map_capacity, the store is not valid");
+  }
+  int from_max = 0, cloud_max = 0;
+  for (int h = 0; h < rows; ++h) {
+    from_max = std::max(from_max, head[2 * h] + head[2 * h + 1]);
+    cloud_max = std::max(cloud_max, std::max(head[2 * h], head[2 * h + 1]));
+  }
+  he = mp_loc_reserve_map(Lc, from_max);
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    x->prof.collect();
+    return fail(LOAM_E_NOMEM, who + ": FromMap allocation failed (" + std::to_string(rows) + " x " +
+                                  std::to_string(from_max) + " points): " + hipGetErrorString(he));
+  }
+  he = mp_localize_solve(Lc, s, none, rows, from_max, cloud_max, std::max(shape.maxC, shape.maxS), st, pf, &lr);
+  x->prof.mark("lanes_localize_d2h");
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    x->prof.collect();
+    return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
+  }
+  x->prof.collect();
+  const int* R = Lc.res_h();
+  for (int h = 0; h < rows; ++h) loc_result_of(R + (size_t)h * kLocResWords, out[h]);
   return LOAM_OK;
 }
 
@@ -2916,18 +3032,7 @@ extern "C" int loam_lanes_pull(loam_ctx* x, loam_lane_out* out) {
       // laserMapping's queue pointer walks inside transformUpdate, i.e. only when the L-M ran
       if (L.imu.step_imu && L.imu.mp_have[l] && w[kLoLmRan]) L.imu.mp[l].front = L.imu.mp_front[l];
       if (L.shared) {
-        const int* r = L.loc_h + (size_t)l * kLocResWords;
-        loam_localize_result& o = L.loc_info[l];
-        std::memcpy(&o.aft, r + kLrAft, sizeof(loam_pose6));
-        o.status = r[kLrStatus];
-        o.iters = r[kLrIters];
-        o.degenerate_steps = r[kLrDegSteps];
-        o.rows_last = (uint32_t)r[kLrRowsLast];
-        o.rows_sum = (uint32_t)r[kLrRowsSum];
-        o.stack_corner = (uint32_t)r[kLrStackC];
-        o.stack_surf = (uint32_t)r[kLrStackS];
-        o.map_corner = (uint32_t)r[kLrMapC];
-        o.map_surf = (uint32_t)r[kLrMapS];
+        loc_result_of(L.loc_h + (size_t)l * kLocResWords, L.loc_info[l]);
       }
     }
     if (L.imu.step_imu) std::memcpy(&L.imu_trans[(size_t)l * 12], L.imu.trans_h + (size_t)l * 12, 12 * sizeof(float));

@@ -23,6 +23,8 @@
 //  k_mp_loc_prepare / k_mp_loc_gather / k_mp_loc_result   loam_map_localize: n candidate poses of one
 //                  sweep as the instances of a second working set against the streaming store, which
 //                  is only read (prepare without recentring, FromMap per candidate, the L-M as above)
+//  k_mp_loc_prepare_rows / k_mp_loc_stack_rows   loam_lanes_localize: the same with every candidate's
+//                  sweep and odometry pose read in place from a listed lane (a row -> lane plan)
 
 #include <algorithm>
 #include <functional>
@@ -249,8 +251,7 @@ struct LocStore {
 // more than w.map_cap points, and every lane when the store's last update overflowed, gets
 // ERR_CAP_MAP and an empty valid set (nothing is gathered, no L-M runs, the poses stay).
 template <bool kLanes>
-__global__ __launch_bounds__(kMpThreads) void k_mp_loc_prepare(MpBuffers w, MpInput in, LocStore s,
-                                                                const float* cand, int* head) {
+LOAM_D void loc_prepare(const MpBuffers& w, const MpInput& in, const LocStore& s, const float* cand, int* head) {
   const int p = blockIdx.x, tid = threadIdx.x;
   float* st = w.state + (size_t)p * kMpStateFloats;
   int* ist = w.istate + (size_t)p * kMpStateInts;
@@ -310,6 +311,27 @@ __global__ __launch_bounds__(kMpThreads) void k_mp_loc_prepare(MpBuffers w, MpIn
     }
   }
 }
+template <bool kLanes>
+__global__ __launch_bounds__(kMpThreads) void k_mp_loc_prepare(MpBuffers w, MpInput in, LocStore s,
+                                                                const float* cand, int* head) {
+  loc_prepare<kLanes>(w, in, s, cand, head);
+}
+// The rows form (loam_lanes_localize): candidate p = blockIdx.x of gridDim.x = n k rows is row p % k
+// of listed lane p / k < n (rows.plan has n entries).  Bef / Aft come from the candidate table as
+// <false> takes them; the odometry pose of prepare_pose is the transformSum of the row's lane, read
+// in place from the lanes' odometry state (plan.lane < the lanes open: lanes_localize_plan).
+__global__ __launch_bounds__(kMpThreads) void k_mp_loc_prepare_rows(MpBuffers w, LocStore s, const float* cand,
+                                                                     int* head, LocRows rows) {
+  const LaneLocPlan& e = rows.plan[blockIdx.x / rows.k];
+  MpInput in;
+  in.corner = in.surf = in.full = nullptr;
+  in.corner_stride = in.surf_stride = in.full_stride = 0;
+  in.ncorner = in.nsurf = in.nfull = nullptr;
+  in.ncorner_stride = in.nsurf_stride = in.nfull_stride = 0;
+  in.pose = rows.od_state + (size_t)e.lane * kOdStateFloats + kOdSum;
+  in.pose_stride = 0;
+  loc_prepare<false>(w, in, s, cand, head);
+}
 
 // FromMap of every candidate (blockIdx.y) from the shared pool: its valid cubes' corner points,
 // then their surf points, cubes in valid order and points in store order (k_mp_gather's order).
@@ -356,15 +378,16 @@ __global__ __launch_bounds__(256) void k_mp_loc_gather(MpBuffers w, LocStore s) 
 }
 
 // ---------------------------------------------------------------- stacks
-__global__ __launch_bounds__(256) void k_mp_stack(MpBuffers b, MpInput in) {
-  const int p = blockIdx.y;
+// instance p's stacks from its two clouds (nc / ns points, clamped to capC / capS by the caller):
+// every point to the map frame and back (:424-434, :683-691), corner at 0, surf at capC of the
+// instance's cap_stack segment; then the segment words of the stacks' VoxelGrid.  over(): a count as
+// given exceeds its capacity (ERR_CAP_STACK; asked by the one thread that writes the words)
+template <class Over>
+LOAM_D void stack_body(const MpBuffers& b, int p, const float4* corner, const float4* surf, int nc, int ns, Over over) {
   const loampose::MapRot r = rot_load(b, p);
-  const int nc = min(in.ncorner[p * in.ncorner_stride], b.capC);
-  const int ns = min(in.nsurf[p * in.nsurf_stride], b.capS);
   float4* out = b.stack2 + (size_t)p * b.cap_stack;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < nc + ns; i += gridDim.x * 256) {
-    const float4 a = i < nc ? in.corner[(size_t)p * in.corner_stride + i]
-                            : in.surf[(size_t)p * in.surf_stride + (i - nc)];
+    const float4 a = i < nc ? corner[i] : surf[i - nc];
     const float4 m = loampose::point_to_map(r, a);
     out[i < nc ? i : b.capC + (i - nc)] = loampose::point_to_tobe_mapped(r, m);
   }
@@ -377,9 +400,30 @@ __global__ __launch_bounds__(256) void k_mp_stack(MpBuffers b, MpInput in) {
     b.sseg_e[p * 2 + 1] = (int)(base + b.capC) + ns;
     b.sseg_leaf[p * 2 + 0] = 0.2f;
     b.sseg_leaf[p * 2 + 1] = 0.4f;
-    if (in.ncorner[p * in.ncorner_stride] > b.capC || in.nsurf[p * in.nsurf_stride] > b.capS)
-      b.istate[(size_t)p * kMpStateInts + kMiErr] |= ERR_CAP_STACK;
+    if (over()) b.istate[(size_t)p * kMpStateInts + kMiErr] |= ERR_CAP_STACK;
   }
+}
+
+__global__ __launch_bounds__(256) void k_mp_stack(MpBuffers b, MpInput in) {
+  const int p = blockIdx.y;
+  const int nc = min(in.ncorner[p * in.ncorner_stride], b.capC);
+  const int ns = min(in.nsurf[p * in.nsurf_stride], b.capS);
+  stack_body(b, p, in.corner + (size_t)p * in.corner_stride, in.surf + (size_t)p * in.surf_stride, nc, ns, [&] {
+    return in.ncorner[p * in.ncorner_stride] > b.capC || in.nsurf[p * in.nsurf_stride] > b.capS;
+  });
+}
+
+// k_mp_stack for the rows of loam_lanes_localize: instance p = blockIdx.y of gridDim.y = n k rows
+// takes the Last clouds of listed lane p / k < n (rows.plan has n entries) in place.  The plan's
+// offsets lie inside [kOdBufs][lanes][cap] and its counts inside the lanes' capacities
+// (lanes_localize_plan); they are clamped to the working set's capC / capS as k_mp_stack clamps its
+// counts, so nothing is read past a lane's cloud or written past the row's segment.  No workgroup
+// waits for another.
+__global__ __launch_bounds__(256) void k_mp_loc_stack_rows(MpBuffers b, LocRows rows) {
+  const int p = blockIdx.y;
+  const LaneLocPlan& e = rows.plan[p / rows.k];
+  stack_body(b, p, rows.lastC + e.offC, rows.lastS + e.offS, min(e.nC, b.capC), min(e.nS, b.capS),
+             [&] { return e.nC > b.capC || e.nS > b.capS; });
 }
 
 // ---------------------------------------------------------------- FromMap gather
@@ -3119,7 +3163,24 @@ void mp_loc_free(MpLoc& L) {
   if (L.head) (void)hipFree(L.head);
   if (L.res) (void)hipFree(L.res);
   if (L.pin) (void)hipHostFree(L.pin);
+  if (L.plan) (void)hipFree(L.plan);
+  if (L.plan_pin) (void)hipHostFree(L.plan_pin);
   L = MpLoc();
+}
+
+hipError_t mp_loc_reserve_rows(MpLoc& L) {
+  if (L.plan_pin) return hipSuccess;
+  DevAlloc A;
+  A(&L.plan, (size_t)kLocMax * sizeof(LaneLocPlan));
+  if (A.err == hipSuccess)
+    A.err = hipHostMalloc((void**)&L.plan_pin, (size_t)kLocMax * (kOdBufs * 2 * sizeof(int) + sizeof(LaneLocPlan)),
+                          hipHostMallocDefault);
+  if (A.err != hipSuccess) {
+    if (L.plan) (void)hipFree(L.plan);
+    L.plan = nullptr;
+    L.plan_pin = nullptr;
+  }
+  return A.err;
 }
 
 hipError_t mp_loc_reserve(MpLoc& L, const MpBuffers& s, int n, int ncorner, int nsurf) {
@@ -3226,25 +3287,39 @@ hipError_t mp_loc_reserve_map(MpLoc& L, int from_max) {
   return hipSuccess;
 }
 
-hipError_t mp_localize_prepare(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, hipStream_t st, Prof* prof) {
+hipError_t mp_localize_prepare(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, hipStream_t st, Prof* prof,
+                               const LocRows* rows) {
   MpBuffers& w = L.w;
   w.P = n;
   hipError_t e = hipMemcpyAsync(L.cand, L.cand_h(), (size_t)n * 12 * sizeof(float), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_mp_loc_prepare<false>, dim3(n), dim3(kMpThreads), 0, st, w, in, loc_store(s), L.cand, L.head);
-  if (prof) prof->mark("k_mp_loc_prepare");
+  if (rows) {  // (n = its listed lanes x rows->k)
+    e = hipMemcpyAsync(L.plan, L.plan_h(), (size_t)(n / rows->k) * sizeof(LaneLocPlan), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    if (prof) prof->mark("lanes_localize_h2d");
+    hipLaunchKernelGGL(k_mp_loc_prepare_rows, dim3(n), dim3(kMpThreads), 0, st, w, loc_store(s), L.cand, L.head, *rows);
+    if (prof) prof->mark("k_mp_loc_prepare_rows");
+  } else {
+    hipLaunchKernelGGL(k_mp_loc_prepare<false>, dim3(n), dim3(kMpThreads), 0, st, w, in, loc_store(s), L.cand, L.head);
+    if (prof) prof->mark("k_mp_loc_prepare");
+  }
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   return hipMemcpyAsync(L.head_h(), L.head, (size_t)(2 * n + 1) * sizeof(int), hipMemcpyDeviceToHost, st);
 }
 
 hipError_t mp_localize_solve(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, int from_max, int cloud_max,
-                             int stack_max, hipStream_t st, Prof* prof) {
+                             int stack_max, hipStream_t st, Prof* prof, const LocRows* rows) {
   MpBuffers& w = L.w;
   w.P = n;
   auto mark = [&](const char* name) { if (prof) prof->mark(name); };
-  hipLaunchKernelGGL(k_mp_stack, dim3(16, n), dim3(256), 0, st, w, in);
-  mark("k_mp_stack");
+  if (rows) {
+    hipLaunchKernelGGL(k_mp_loc_stack_rows, dim3(16, n), dim3(256), 0, st, w, *rows);
+    mark("k_mp_loc_stack_rows");
+  } else {
+    hipLaunchKernelGGL(k_mp_stack, dim3(16, n), dim3(256), 0, st, w, in);
+    mark("k_mp_stack");
+  }
   mp_stack_vg(w, n, st, stack_max);
   mark("vg_stack");
   const bool map_empty = from_max == 0;  // no candidate can run the L-M (:706): nothing to gather or hash

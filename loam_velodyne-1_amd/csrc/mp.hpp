@@ -8,6 +8,7 @@
 #include <string>
 
 #include "engine.hpp"
+#include "loc_plan.hpp"
 #include "xfer.hpp"
 #include "od.hpp"
 #include "vg.hpp"
@@ -253,6 +254,21 @@ struct MpLoc {
   float* cand_h() const { return (float*)pin; }
   int* head_h() const { return (int*)(pin + (size_t)kLocMax * 12 * 4); }
   int* res_h() const { return head_h() + 2 * kLocMax + 4; }
+  // loam_lanes_localize's plan block (allocated by its first call, mp_loc_reserve_rows): pinned, the
+  // lanes' nlast words as they come down ([kLocMax][kOdBufs][2]) and the listed lanes' LaneLocPlan
+  // entries as they go up; device, those entries
+  char* plan_pin = nullptr;
+  LaneLocPlan* plan = nullptr;  // device [kLocMax]
+  int* nlast_h() const { return (int*)plan_pin; }
+  LaneLocPlan* plan_h() const { return (LaneLocPlan*)(plan_pin + (size_t)kLocMax * kOdBufs * 2 * sizeof(int)); }
+};
+// loam_lanes_localize: instance p (a row) reads the sweep of listed lane p / k in place.  plan[i], i
+// < n, is listed lane i (loc_plan.hpp); lastC / lastS / od_state are the lanes' OdBuffers arrays
+struct LocRows {
+  const LaneLocPlan* plan;  // device [n]
+  int k;                    // rows per listed lane (the launch has n k instances)
+  const float4 *lastC, *lastS;
+  const float* od_state;    // [lanes][kOdStateFloats]
 };
 void mp_loc_free(MpLoc& L);
 // the candidate tables and, for n candidates and a sweep of ncorner + nsurf points, the working set's
@@ -261,14 +277,18 @@ void mp_loc_free(MpLoc& L);
 hipError_t mp_loc_reserve(MpLoc& L, const MpBuffers& s, int n, int ncorner, int nsurf);
 // the FromMap part (from, the two hash indexes) for from_max points per candidate
 hipError_t mp_loc_reserve_map(MpLoc& L, int from_max);
+// the plan block of loam_lanes_localize (nothing enqueued reads it when it is made)
+hipError_t mp_loc_reserve_rows(MpLoc& L);
 // k_mp_loc_prepare for n candidates (L.cand) on the sweep `in` (strides 0) + the counts into
-// L.head_h(); the caller synchronises st, then reads them
-hipError_t mp_localize_prepare(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, hipStream_t st, Prof* prof);
+// L.head_h(); the caller synchronises st, then reads them.  rows (loam_lanes_localize): the n
+// candidates are rows of L.plan (L.plan_h() goes up first), `in` is not read
+hipError_t mp_localize_prepare(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, hipStream_t st, Prof* prof,
+                               const LocRows* rows = nullptr);
 // the stacks, the FromMap gather (from_max > 0), the hash builds, the L-M and the result blocks
 // into L.res_h(); the caller synchronises st, then reads them.  from_max: the largest FromMap of a
-// candidate, cloud_max: its largest corner or surf part; stack_max as mp_frame's
+// candidate, cloud_max: its largest corner or surf part; stack_max as mp_frame's.  rows: as above
 hipError_t mp_localize_solve(MpLoc& L, const MpBuffers& s, const MpInput& in, int n, int from_max, int cloud_max,
-                             int stack_max, hipStream_t st, Prof* prof);
+                             int stack_max, hipStream_t st, Prof* prof, const LocRows* rows = nullptr);
 
 // ---- shared lanes (loam_lanes_open_shared): every lane's mapping frame against one streaming store ----
 // The lanes' working set: an MpBuffers of P lanes built as MpLoc::w is (no pools, slot tables, cube

@@ -4,7 +4,8 @@ stepped by loam_chain_sweep from one thread, through the C-ABI on one GPU (DESIG
   python tools/lanes_bench.py [--s 1,16,64] [--sweeps 27] [--map-cap 131072] [--yard-max 1024]
                               [--profile-s 64] [--imu] [--restart K,M] [--occupancy N] [--map-import N]
                               [--surround] [--shared stream|big [--from-cap F]]
-                              [--score stream|big [--k K1,K2]] [--out FILE]
+                              [--score stream|big [--k K1,K2]] [--localize stream|big [--k K1,K2]]
+                              [--out FILE]
 
 Per S: S lanes over eight distinct VLP-16 synthetic streams laid out cyclically.  The wall time of
 lanes_step (push + pull), and of the push alone (host packing + enqueue), median and range over the
@@ -76,7 +77,16 @@ times: one loam_lanes_score call, and the parent's only way, S loam_map_score ca
 with the lane's Last clouds handed in from host memory (obtained from node-call contexts, which is
 not timed).  max_dist 0.5; wall time per way, median and range of 5 after a warm-up; one more call of
 each under loam_set_profiling for the device time per kernel; sampled rows of both ways compared bit
-for bit."""
+for bit.
+
+--localize stream|big (instead of the above): the same fleet and shapes (--s and --k
+paired by position: 64,1024 with 16,1).  Per shape, k candidate poses near every lane's pose (the
+score mode's distribution as aft, the lane's od_sum as bef) refined both ways on the same context,
+alternating three times: one loam_lanes_localize call, and the parent's only way, S loam_map_localize
+calls of k candidates each with the lane's Last clouds and od_sum handed in from host memory (from
+node-call contexts, not timed).  Wall time per way, median and range of 5 after a warm-up; one more
+call of each under loam_set_profiling for the device time per kernel and the share of the two rows
+kernels; sampled rows of both ways compared bit for bit in every pair."""
 import argparse
 import importlib
 import json
@@ -670,6 +680,78 @@ def run_score(S, k, streams, name, M, from_cap, pairs=3, reps=5):
     return line
 
 
+def run_localize(S, k, streams, name, M, from_cap, pairs=3, reps=5):
+    """one JSON line: k candidates for each of S shared lanes in the map M, loam_lanes_localize against
+    S loam_map_localize calls on the same context, `pairs` alternating timings"""
+    kw = dict(corner=M["corner"], surf=M["surf"], center=M["center"], surround_phase=4)
+    total = int(M["corner"].shape[0] + M["surf"].shape[0])
+    eng = loam.Engine(loam.default_config(system_delay=1, map_capacity=max(1 << 17, 1 << int(np.ceil(np.log2(total))))))
+    eng.set_tuning(batch_streams=0)
+    eng.map_import(**kw)
+    eng.lanes_open_shared(S, from_cap)
+    eng.lanes_set_pose(list(range(S)), np.zeros(6, np.float32))
+    n_steps = 3
+    for j in range(n_steps):
+        o = eng.lanes_step([streams[l % N_STREAMS][j] for l in range(S)], stamp=0.1 * j)
+    # the yardstick's inputs (not timed): every stream's Last clouds and od_sum of that step from a node-call context
+    last = []
+    for i in range(min(S, N_STREAMS)):
+        A = loam.Engine(loam.default_config(system_delay=1, skip_frame_num=0))
+        for j in range(n_steps):
+            rc, f = A.scan_registration(streams[i][j], stamp=0.1 * j)
+            if rc == 0:
+                _, od, cl, sl, _ = A.odometry(f, stamp=0.1 * j)
+        A.close()
+        last.append((np.asarray(od, np.float32), cl, sl))
+    rng = np.random.default_rng(31)
+    P = (rng.uniform(-1, 1, (k, 6)) * np.array([0.05, 0.05, 0.05, 0.5, 0.5, 0.5])).astype(np.float32)
+    lanes = list(range(S))
+    bef = np.ascontiguousarray(np.stack([np.broadcast_to(last[l % N_STREAMS][0], (k, 6)) for l in lanes]))
+    aft = np.ascontiguousarray(np.broadcast_to(P, (S, k, 6)))
+
+    def new():
+        return eng.lanes_localize(lanes, aft, bef)
+
+    def yard():
+        return [eng.map_localize(*last[l % N_STREAMS], P, bef[l]) for l in lanes]
+
+    def timed(call):
+        call()  # warm-up
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            call()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return spread(ts)
+
+    def same_rows():
+        got, want = new(), yard()
+        return all(np.array_equal(got[key][l].view(np.uint32), want[l][key].view(np.uint32))
+                   for key in loam.LOCALIZE_KEYS for l in sorted({0, S // 2, S - 1}))
+    runs, same = [], []
+    for _ in range(pairs):
+        runs.append(dict(lanes_localize_ms=timed(new), map_localize_calls_ms=timed(yard)))
+        same.append(bool(same_rows()))
+    got = new()
+    line = dict(localize_leg=name, S=S, k=k, rows=S * k, map_points=total,
+                lanes_failed=int(np.count_nonzero(o["status"] != 0)),
+                rows_solved=int(np.count_nonzero(got["status"] == loam.LOC_SOLVED)),
+                from_map_points_per_row=int(np.mean(got["map_corner"].astype(np.int64) + got["map_surf"])),
+                stack_points_per_lane=int(np.mean([c.shape[0] + s_.shape[0] for _, c, s_ in last])), pairs=runs,
+                new_below_yardstick=[bool(r["lanes_localize_ms"]["median"] < r["map_localize_calls_ms"]["median"]) for r in runs],
+                yardstick_over_new=[round(r["map_localize_calls_ms"]["median"] / r["lanes_localize_ms"]["median"], 2)
+                                    for r in runs],
+                sampled_rows_equal=same)
+    line["device_ms_lanes_localize"] = dn = _profiled(eng, new)
+    line["device_ms_map_localize_calls"] = _profiled(eng, yard)
+    dev = sum(v for key, v in dn.items() if key.startswith(("k_", "vg_", "lanes_localize")))
+    line["rows_kernels_share_of_device_ms"] = round((dn.get("k_mp_loc_prepare_rows", 0.0) + dn.get("k_mp_loc_stack_rows", 0.0)) /
+                                                    dev, 4) if dev else None
+    eng.lanes_close()
+    eng.close()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--s", default="1,16,64")
@@ -686,10 +768,12 @@ def main():
     ap.add_argument("--from-cap", type=int, default=0,
                     help="--shared: lane_from_capacity (0: the power of two that holds the stream map, 65536 in the big map)")
     ap.add_argument("--score", default=None, help="stream|big: loam_lanes_score against S loam_map_score calls in that map")
-    ap.add_argument("--k", default="256,64", help="--score: poses per lane, paired with --s by position")
+    ap.add_argument("--localize", default=None,
+                    help="stream|big: loam_lanes_localize against S loam_map_localize calls in that map")
+    ap.add_argument("--k", default="256,64", help="--score / --localize: poses per lane, paired with --s by position")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.shared = a.shared or a.score
+    a.shared = a.shared or a.score or a.localize
     K = 40 if a.occupancy else 23 if a.surround else a.sweeps
     streams = [sg.stream_sweeps(K, 1 + i) for i in range(N_STREAMS)]
     imu = imu_schedules(K) if a.imu else None
@@ -723,6 +807,10 @@ def main():
         if a.score:
             for S, k in zip([int(v) for v in a.s.split(",") if v], [int(v) for v in a.k.split(",") if v]):
                 emit(run_score(S, k, streams, a.score, M, F))
+            return
+        if a.localize:
+            for S, k in zip([int(v) for v in a.s.split(",") if v], [int(v) for v in a.k.split(",") if v]):
+                emit(run_localize(S, k, streams, a.localize, M, F))
             return
         for S in [int(v) for v in a.s.split(",") if v]:
             emit(run_shared(S, streams, K, a.shared, M, F, profile=S == a.profile_s))
