@@ -446,6 +446,44 @@ int loam_lanes_push(loam_ctx *ctx, double stamp, const loam_cloud_in *raw /* [n_
  * the de-skew and mapping's roll / pitch blend look the queues up by them.  A null stamp array or
  * a stamp that is not finite (either call): LOAM_E_INVAL, nothing is enqueued or counted. */
 int loam_lanes_push_stamped(loam_ctx *ctx, const double *stamp /* [n_lanes] */, const loam_cloud_in *raw /* [n_lanes] */);
+/* loam_lanes_push_stamped for sweeps that are already in device memory: raw[l].data
+ * is a device pointer, and one kernel gathers every lane's sweep straight into scan registration's
+ * input.  No host packing, no pinned staging and no bulk copy takes place; the call never
+ * synchronises with the host.  It enqueues the step loam_lanes_push_stamped(ctx, stamp, raw_host)
+ * enqueues for raw_host[l] holding the same bytes in host memory: every later output (the pull
+ * records, registered clouds, /imu_trans, exported maps, surround clouds, score and localize rows)
+ * is bit for bit that of the host push, and the two kinds of push may alternate from step to step.
+ * raw[l].data is plain device memory of the context's device (hipMalloc; a framework's tensor), x, y,
+ * z floats at byte offsets 0, 4, 8 of each record, stride_bytes at least 12 and a multiple of 4, and
+ * data 4-byte aligned (the one rule the host form does not have: the device reads dwords).
+ * A lane fails, sticky, with the host push's codes: count == 0 (how a lane retires), null data, a
+ * bad stride or data % 4 != 0: LOAM_E_INVAL; count > max_points: LOAM_E_CAPACITY; a sweep without a
+ * finite point is found by scan registration.  Of a failed lane, a waiting lane (loam_lanes_restart)
+ * and every lane inside system_delay raw[l] is not looked at: not the pointer, its memory or its range.
+ * LOAM_E_INVAL with nothing enqueued, nothing counted and no lane changed: a null ctx, stamp or raw;
+ * lanes not open; a step in flight; a stamp that is not finite; unknown flag bits; a live lane's
+ * non-null, aligned pointer that HIP does not report as device memory of the context's device
+ * (pinned or registered host memory, managed memory and another device's memory are refused); a live
+ * lane's range [data, data + (count - 1) stride_bytes + 12) that leaves its allocation (+ 16 at a
+ * 16-byte stride, whose fourth word is copied as the host form copies it).
+ * LOAM_E_NOMEM, and nothing changed, when the first call's descriptor block (32 bytes per lane)
+ * cannot be allocated.
+ * Ordering against the producer of the sweeps, by flags:
+ *   0: the sweeps are visible to the device already (the caller synchronised) and stay untouched
+ *      until loam_lanes_pull of this step returns; producer_stream is not read.
+ *   LOAM_FEED_WAIT: the gather waits for the work enqueued so far on producer_stream (an event
+ *      recorded there, waited for on the context's stream).
+ *   LOAM_FEED_RELEASE: work enqueued on producer_stream after this call waits for the gather (an
+ *      event recorded behind it, waited for on producer_stream) and may overwrite the sweeps.
+ * The two events are created, timing disabled, by the first call that needs them and live until
+ * loam_lanes_close; none is recorded on a step that reads no sweep (inside system_delay, or every
+ * lane failed, waiting or retiring). */
+#define LOAM_FEED_WAIT    1
+#define LOAM_FEED_RELEASE 2
+int loam_lanes_push_device(loam_ctx *ctx, const double *stamp /* [n_lanes] */,
+                           const loam_cloud_in *raw /* [n_lanes], data = device pointers */,
+                           void *producer_stream /* a hipStream_t, read only when flags != 0 */,
+                           uint32_t flags);
 /* loam_imu for one lane: the message enters the lane's scanRegistration and laserMapping queues
  * (on the host; the next push uploads the new entries).  A lane that never got a message runs
  * without IMU; a lane may get its first message before any step.  From the first message of any

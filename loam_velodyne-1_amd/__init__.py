@@ -169,6 +169,7 @@ _SCORE_DTYPE = np.dtype([(n, np.float64 if t is ctypes.c_double else np.uint32) 
 
 
 LANES_MAX = 1024  # LOAM_LANES_MAX: lanes of one context
+FEED_WAIT, FEED_RELEASE = 1, 2  # LOAM_FEED_*: loam_lanes_push_device's ordering against the producer's stream
 
 
 class LaneOut(ctypes.Structure):
@@ -197,7 +198,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
            "loam_lanes_restart", "loam_lanes_map_import", "loam_lanes_surround",
            "loam_lanes_open_shared", "loam_lanes_set_pose", "loam_lanes_localize_info", "loam_lanes_score",
-           "loam_lanes_localize",
+           "loam_lanes_localize", "loam_lanes_push_device",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -266,6 +267,7 @@ def lib():
                                        P(ScoreResult)]
         L.loam_lanes_localize.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), ctypes.c_uint32, P(Pose6), P(Pose6),
                                           P(LocalizeResult)]
+        L.loam_lanes_push_device.argtypes = [PP, P(ctypes.c_double), P(CloudIn), ctypes.c_void_p, ctypes.c_uint32]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -293,6 +295,30 @@ def _cloud_in(a):
         return a, None
     a = np.ascontiguousarray(a, np.float32)
     return CloudIn(a.ctypes.data, a.shape[0], a.shape[1] * 4), a
+
+
+def _cloud_in_device(r):
+    """a sweep in device memory as a loam_cloud_in: a ready CloudIn, a (ptr, count, stride_bytes)
+    tuple, or an object with __cuda_array_interface__ (a torch tensor on the GPU): 2-D float32, at
+    least 3 columns, unit column stride"""
+    if isinstance(r, CloudIn):
+        return r
+    if isinstance(r, tuple):
+        ptr, count, stride = r
+        return CloudIn(int(ptr) or None, int(count), int(stride))
+    cai = getattr(r, "__cuda_array_interface__", None)
+    if cai is None:
+        raise ValueError("a device sweep is a CloudIn, a (ptr, count, stride_bytes) tuple or an object with "
+                         "__cuda_array_interface__")
+    shape, strides = tuple(cai["shape"]), cai.get("strides")
+    if np.dtype(cai["typestr"]) != np.dtype(np.float32):
+        raise ValueError("a device sweep must be float32")
+    if len(shape) != 2 or shape[1] < 3:
+        raise ValueError("a device sweep must be 2-D with at least 3 columns")
+    row, col = (shape[1] * 4, 4) if strides is None else (int(strides[0]), int(strides[1]))
+    if col != 4 or not 0 <= row < 1 << 32:
+        raise ValueError("a device sweep needs unit column stride and a row stride that is not negative")
+    return CloudIn(int(cai["data"][0]) or None, int(shape[0]), row)
 
 
 class _Out:
@@ -585,6 +611,34 @@ class Engine:
             raise ValueError("one stamp per lane")
         t = (ctypes.c_double * self.n_lanes)(*[float(v) for v in stamp])
         _check(lib().loam_lanes_push_stamped(self.h, t, a))
+
+    def lanes_push_device(self, raws, stamp=0.0, stream=None, wait=False, release=False):
+        """lanes_push for sweeps that are already in device memory (loam_lanes_push_device): raws[l]
+        is a CloudIn, a (ptr, count, stride_bytes) tuple or an object with __cuda_array_interface__
+        (a torch tensor on this GPU: 2-D float32, at least 3 columns).  stream: the producer's HIP
+        stream as an integer handle (torch.cuda.current_stream().cuda_stream); wait: the gather waits
+        for the work enqueued on it so far; release: its later work waits for the gather and may
+        overwrite the sweeps.  Without either the caller has synchronised and leaves the sweeps
+        untouched until lanes_pull returns."""
+        if len(raws) != self.n_lanes:
+            raise ValueError("one sweep per lane")
+        if (wait or release) and stream is None:
+            raise ValueError("wait / release need the producer's stream")
+        a = (CloudIn * self.n_lanes)()
+        for l, r in enumerate(raws):
+            a[l] = _cloud_in_device(r)
+        if np.ndim(stamp) == 0:
+            stamp = [stamp] * self.n_lanes
+        if len(stamp) != self.n_lanes:
+            raise ValueError("one stamp per lane")
+        t = (ctypes.c_double * self.n_lanes)(*[float(v) for v in stamp])
+        flags = (FEED_WAIT if wait else 0) | (FEED_RELEASE if release else 0)
+        _check(lib().loam_lanes_push_device(self.h, t, a, ctypes.c_void_p(stream if stream is not None else 0), flags))
+
+    def lanes_step_device(self, raws, stamp=0.0, stream=None, wait=False, release=False):
+        """lanes_push_device followed by lanes_pull"""
+        self.lanes_push_device(raws, stamp, stream, wait, release)
+        return self.lanes_pull()
 
     def lanes_imu(self, lane, stamp, quat_xyzw, lin_acc):
         """/imu/data of one lane (loam_lanes_imu): loam_imu for that lane's sequence"""

@@ -123,6 +123,19 @@ int loam_dev_od_nn_destroy(loam_dev_od_nn* h);
 int loam_dev_sr_ring_of(int device, int32_t n_rings, int32_t ring_model, float ring_lo_deg, float ring_hi_deg,
                         const float* pts, int32_t n, int32_t* ring, int32_t* exact, int32_t* fast);
 
+/* loam_lanes_push_device's validation and gather (lanes_feed_plan.hpp, lanes.hip k_lanes_gather_dev) on
+ * S caller sweeps in device memory: raw [S] is a loam_cloud_in array (include/loam/loam.h) whose data
+ * are device pointers; every lane counts as running.  out_raw [S][cap][4] words: first filled with
+ * LOAM_DEV_VG_SENTINEL (every word), then lane s's points at [s][0 .. out_n[s]); out_n [S]: what the
+ * kernel wrote into scan registration's sizes (0 for a lane the product would fail: count 0 or beyond
+ * cap, null or misaligned data, a bad stride).  S in 1 .. LOAM_LANES_MAX, cap in 1 ..
+ * LOAM_DEV_LANES_GATHER_MAX_CAP.  LOAM_E_INVAL for bad arguments and for what the product refuses at
+ * call level (a pointer that is not device memory of `device`, a sweep that leaves its allocation),
+ * before anything is launched; LOAM_E_HIP without a GPU; LOAM_E_NOMEM. */
+#define LOAM_DEV_LANES_GATHER_MAX_CAP (1 << 22)
+int loam_dev_lanes_gather(int device, int32_t S, int32_t cap, const void* raw /* loam_cloud_in [S] */, uint32_t* out_raw,
+                          int32_t* out_n);
+
 #ifdef __cplusplus
 }
 #endif

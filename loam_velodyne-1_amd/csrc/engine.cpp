@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/loam/loam.h"
+#include "dev_hooks.h"
 #include "engine.hpp"
 #include "lanes.hpp"
 #include "mp.hpp"
@@ -2741,30 +2742,38 @@ extern "C" int loam_lanes_close(loam_ctx* x) {
 }
 
 namespace {
-// loam_lanes_push / loam_lanes_push_stamped: lane l's sweep stamp is stamps ? stamps[l] : stamp
-int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud_in* raw) {
+// Every push: what is refused before anything is enqueued, counted or changed.  Lane l's sweep stamp
+// is stamps ? stamps[l] : stamp.
+int lanes_push_check(loam_ctx* x, const double* stamps, double stamp, const std::string& who) {
+  const Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
+  if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
+  for (int l = 0; l < L.S; ++l)
+    if (!std::isfinite(stamps ? stamps[l] : stamp)) return fail(LOAM_E_INVAL, who + ": a sweep stamp is not finite");
+  return LOAM_OK;
+}
+
+// Every push, behind its checks: drops what the last step left; false inside system_delay, where the
+// step is counted and nothing is enqueued
+bool lanes_push_begin(loam_ctx* x) {
   Lanes& L = x->lanes;
-  if (!L.S) return fail(LOAM_E_INVAL, "loam_lanes_push: lanes are not open");
-  if (L.in_flight) return fail(LOAM_E_INVAL, "loam_lanes_push: a step is in flight (loam_lanes_pull first)");
-  const int S = L.S;
-  for (int l = 0; l < S; ++l)
-    if (!std::isfinite(stamps ? stamps[l] : stamp)) return fail(LOAM_E_INVAL, "loam_lanes_push: a sweep stamp is not finite");
-  LanesImu& I = L.imu;
-  I.step_imu = false;
+  L.imu.step_imu = false;
   L.have_reg = false;
-  for (int l = 0; l < S; ++l) L.life[l].due = kDueNo;  // (the last step's /laser_cloud_surround)
-  if (!L.sr_inited) {  // src/scanRegistration.cpp:213-219 (Q1): the sweeps are not looked at
-    L.sr_init_count++;
-    if (L.sr_init_count >= (int)x->cfg.system_delay) L.sr_inited = true;
-    L.in_flight = true;
-    L.step_ran = false;
-    return LOAM_OK;
-  }
-  HIP_TRY(hipSetDevice(x->device));
-  // a lane whose sweep cannot be uploaded, and a lane that failed before, is an empty sweep on the
-  // device: its slot goes through the kernels as an empty problem of a batch does
-  // a restarted lane: an empty problem too until its init frame, and raw[l] is not looked at
-  int n_clear = 0, n_init = 0;
+  for (int l = 0; l < L.S; ++l) L.life[l].due = kDueNo;  // (the last step's /laser_cloud_surround)
+  if (L.sr_inited) return true;
+  // src/scanRegistration.cpp:213-219 (Q1): the sweeps are not looked at
+  L.sr_init_count++;
+  if (L.sr_init_count >= (int)x->cfg.system_delay) L.sr_inited = true;
+  L.in_flight = true;
+  L.step_ran = false;
+  return false;
+}
+
+// the lanes' kinds on this step and loam_lanes_restart's lists of it
+// a restarted lane: an empty problem until its init frame, and raw[l] is not looked at
+void lanes_push_kinds(Lanes& L, int& n_clear, int& n_init) {
+  const int S = L.S;
+  n_clear = n_init = 0;
   for (int l = 0; l < S; ++l) {
     LaneLife& f = L.life[l];
     f.kind = kLaneRuns;
@@ -2773,40 +2782,31 @@ int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud
     L.rs_h[n_clear++] = l;
     if (f.kind == kLaneInits) L.rs_h[S + n_init++] = l;
   }
-  std::vector<loam_cloud_in> eff((size_t)S);
-  int* nn = L.tab_h;
-  int* off = nn + S;
-  size_t run = 0;
-  for (int l = 0; l < S; ++l) {
-    const bool waits = L.life[l].kind == kLaneWaits;
-    L.fail_new[l] = waits ? LOAM_OK : lane_sweep_code(raw[l], x->cap);
-    eff[l] = raw[l];
-    if (waits || L.fail_new[l] != LOAM_OK || L.fail[l] != LOAM_OK) eff[l].count = 0;
-    nn[l] = (int)eff[l].count;
-    off[l] = (int)run;
-    run += eff[l].count;
-  }
+}
+
+// opens the step's timeline; the restarted lanes as lanes_alloc left them, in front of everything
+// the step does
+int lanes_push_clear(loam_ctx* x, int n_clear) {
+  Lanes& L = x->lanes;
   hipStream_t st = x->st;
-  Prof* pf = x->prof.on ? &x->prof : nullptr;
   x->prof.begin(st);
-  if (n_clear) {  // the restarted lanes as lanes_alloc left them, in front of everything the step does
-    HIP_TRY(hipMemcpyAsync(L.rs_d, L.rs_h, (size_t)2 * S * sizeof(int), hipMemcpyHostToDevice, st));
+  if (n_clear) {
+    HIP_TRY(hipMemcpyAsync(L.rs_d, L.rs_h, (size_t)2 * L.S * sizeof(int), hipMemcpyHostToDevice, st));
     x->prof.mark("lanes_h2d");
-    HIP_TRY(lanes_restart_clear(L, L.rs_d, n_clear, kClearOd | kClearMp | (I.on ? kClearImu : 0), st));
+    HIP_TRY(lanes_restart_clear(L, L.rs_d, n_clear, kClearOd | kClearMp | (L.imu.on ? kClearImu : 0), st));
     x->prof.mark("k_lanes_restart");
   }
-  // packed in chunks of sweeps, each chunk's copy enqueued before the next is packed
-  constexpr int kPushChunk = 128;  // sweeps
-  for (int s0 = 0; s0 < S; s0 += kPushChunk) {
-    const int s1 = std::min(S, s0 + kPushChunk);
-    pack_tight_of([&](size_t s) -> const loam_cloud_in& { return eff[s]; }, (size_t)s0, (size_t)s1, off, L.stage_h);
-    const size_t a = (size_t)off[s0], b = (size_t)off[s1 - 1] + (size_t)nn[s1 - 1];
-    if (b > a)
-      HIP_TRY(hipMemcpyAsync(L.stage_d + a, L.stage_h + a, (b - a) * sizeof(float4), hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(hipMemcpyAsync(L.tab_d, nn, (size_t)2 * S * sizeof(int), hipMemcpyHostToDevice, st));
-  HIP_TRY(sr_scatter_packed(L.stage_d, L.tab_d + S, L.tab_d, L.sr.raw, x->cap, S, st));
-  HIP_TRY(hipMemcpyAsync(L.sr.raw_n, L.tab_d, (size_t)S * sizeof(int), hipMemcpyDeviceToDevice, st));
+  return LOAM_OK;
+}
+
+// Every push, behind the sweeps in sr.raw / sr.raw_n: the step's IMU block, its kernels and the
+// life counters
+int lanes_push_finish(loam_ctx* x, const double* stamps, double stamp, int n_clear, int n_init, const std::string& who) {
+  Lanes& L = x->lanes;
+  LanesImu& I = L.imu;
+  const int S = L.S;
+  hipStream_t st = x->st;
+  Prof* pf = x->prof.on ? &x->prof : nullptr;
   // IMU: any live lane with a message makes this an IMU step for all lanes
   bool imu = false;
   if (I.on) {
@@ -2850,8 +2850,96 @@ int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud
   L.in_flight = true;
   L.step_ran = true;
   I.step_imu = imu;
-  if (he != hipSuccess) return fail(LOAM_E_HIP, std::string("loam_lanes_push: ") + hipGetErrorString(he));
+  if (he != hipSuccess) return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
   return LOAM_OK;
+}
+
+// loam_lanes_push / loam_lanes_push_stamped
+int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud_in* raw) {
+  const std::string who = "loam_lanes_push";
+  Lanes& L = x->lanes;
+  if (const int rc = lanes_push_check(x, stamps, stamp, who)) return rc;
+  const int S = L.S;
+  if (!lanes_push_begin(x)) return LOAM_OK;
+  HIP_TRY(hipSetDevice(x->device));
+  // a lane whose sweep cannot be uploaded, and a lane that failed before, is an empty sweep on the
+  // device: its slot goes through the kernels as an empty problem of a batch does
+  int n_clear = 0, n_init = 0;
+  lanes_push_kinds(L, n_clear, n_init);
+  std::vector<loam_cloud_in> eff((size_t)S);
+  int* nn = L.tab_h;
+  int* off = nn + S;
+  size_t run = 0;
+  for (int l = 0; l < S; ++l) {
+    const bool waits = L.life[l].kind == kLaneWaits;
+    L.fail_new[l] = waits ? LOAM_OK : lane_sweep_code(raw[l], x->cap);
+    eff[l] = raw[l];
+    if (waits || L.fail_new[l] != LOAM_OK || L.fail[l] != LOAM_OK) eff[l].count = 0;
+    nn[l] = (int)eff[l].count;
+    off[l] = (int)run;
+    run += eff[l].count;
+  }
+  hipStream_t st = x->st;
+  if (const int rc = lanes_push_clear(x, n_clear)) return rc;
+  // packed in chunks of sweeps, each chunk's copy enqueued before the next is packed
+  constexpr int kPushChunk = 128;  // sweeps
+  for (int s0 = 0; s0 < S; s0 += kPushChunk) {
+    const int s1 = std::min(S, s0 + kPushChunk);
+    pack_tight_of([&](size_t s) -> const loam_cloud_in& { return eff[s]; }, (size_t)s0, (size_t)s1, off, L.stage_h);
+    const size_t a = (size_t)off[s0], b = (size_t)off[s1 - 1] + (size_t)nn[s1 - 1];
+    if (b > a)
+      HIP_TRY(hipMemcpyAsync(L.stage_d + a, L.stage_h + a, (b - a) * sizeof(float4), hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipMemcpyAsync(L.tab_d, nn, (size_t)2 * S * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(sr_scatter_packed(L.stage_d, L.tab_d + S, L.tab_d, L.sr.raw, x->cap, S, st));
+  HIP_TRY(hipMemcpyAsync(L.sr.raw_n, L.tab_d, (size_t)S * sizeof(int), hipMemcpyDeviceToDevice, st));
+  return lanes_push_finish(x, stamps, stamp, n_clear, n_init, who);
+}
+
+// what HIP knows of a caller's pointer: the allocation around it, and whether that is plain device
+// memory of `device` (pinned, registered, managed and peer memory are not)
+void lanes_feed_lookup(const void* p, int device, LaneFeedIn& q) {
+  q.on_device = 0;
+  q.base = 0;
+  q.size = 0;
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof(at));
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.isManaged ||
+      at.device != device || hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+    (void)hipGetLastError();  // (a pointer HIP does not know is an error of the query, not of the context)
+    return;
+  }
+  q.on_device = 1;
+  q.base = (uintptr_t)base;
+  q.size = (uint64_t)size;
+}
+
+// raw[0..S) and the lanes' states into the plan's input, with HIP's answer for every pointer the
+// step would read.  A pointer inside the allocation found for the previous lane of this call takes
+// that answer; nothing is kept between calls (the memory may have been freed).
+void lanes_feed_inputs(const loam_cloud_in* raw, int S, int cap, int device, const int* state, std::vector<LaneFeedIn>& in) {
+  in.resize((size_t)S);
+  const LaneFeedIn* prev = nullptr;
+  for (int l = 0; l < S; ++l) {
+    LaneFeedIn& q = in[l];
+    std::memset(&q, 0, sizeof(q));
+    q.state = state[l];
+    if (q.state != kFeedRuns) continue;  // (raw[l] is not looked at)
+    q.ptr = (uintptr_t)raw[l].data;
+    q.count = raw[l].count;
+    q.stride = raw[l].stride_bytes;
+    if (!lanes_feed_looks(q, cap)) continue;
+    if (prev && q.ptr >= prev->base && (uint64_t)(q.ptr - prev->base) < prev->size) {
+      q.on_device = 1;
+      q.base = prev->base;
+      q.size = prev->size;
+    } else {
+      lanes_feed_lookup(raw[l].data, device, q);
+    }
+    if (q.on_device) prev = &q;
+  }
 }
 }  // namespace
 
@@ -2863,6 +2951,107 @@ extern "C" int loam_lanes_push(loam_ctx* x, double stamp, const loam_cloud_in* r
 extern "C" int loam_lanes_push_stamped(loam_ctx* x, const double* stamp, const loam_cloud_in* raw) {
   if (!x || !stamp || !raw) return fail(LOAM_E_INVAL, "null argument");
   return lanes_push(x, stamp, 0.0, raw);
+}
+
+extern "C" int loam_lanes_push_device(loam_ctx* x, const double* stamp, const loam_cloud_in* raw, void* producer_stream,
+                                      uint32_t flags) {
+  static_assert(kFeedLaneOk == LOAM_OK && kFeedLaneInval == LOAM_E_INVAL && kFeedLaneCapacity == LOAM_E_CAPACITY,
+                "lanes_feed_plan.hpp");
+  const std::string who = "loam_lanes_push_device";
+  if (!x || !stamp || !raw) return fail(LOAM_E_INVAL, "null argument");
+  if (flags & ~(uint32_t)(LOAM_FEED_WAIT | LOAM_FEED_RELEASE)) return fail(LOAM_E_INVAL, who + ": unknown flag bits");
+  Lanes& L = x->lanes;
+  if (const int rc = lanes_push_check(x, stamp, 0.0, who)) return rc;
+  const int S = L.S;
+  HIP_TRY(hipSetDevice(x->device));
+  if (lanes_feed_alloc(L) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LOAM_E_NOMEM, who + ": the descriptor block's allocation failed");
+  }
+  hipStream_t prod = (hipStream_t)producer_stream;
+  bool feeds = false;
+  if (L.sr_inited) {  // (inside system_delay the sweeps are not looked at)
+    std::vector<int> state((size_t)S);
+    for (int l = 0; l < S; ++l) state[l] = L.fail[l] != LOAM_OK ? kFeedFailed : L.life[l].wait > 0 ? kFeedWaits : kFeedRuns;
+    std::vector<LaneFeedIn> in;
+    lanes_feed_inputs(raw, S, x->cap, x->device, state.data(), in);
+    // (the last step was pulled: its copy of the descriptor block is done; the lanes' codes go into
+    // fail_new only when nothing can refuse the call any more)
+    std::vector<int32_t> code((size_t)S);
+    uint32_t bad = 0;
+    const int verdict = lanes_feed_plan(in.data(), (uint32_t)S, x->cap, L.fd_h, code.data(), &bad);
+    if (verdict != kFeedOk) {
+      char msg[128];
+      lanes_feed_message(verdict, bad, msg, sizeof(msg));
+      return fail(LOAM_E_INVAL, who + ": " + msg);
+    }
+    for (int l = 0; l < S && !feeds; ++l) feeds = L.fd_h[l].n > 0;
+    if (feeds && (flags & LOAM_FEED_WAIT) && !L.feed_wait) HIP_TRY(hipEventCreateWithFlags(&L.feed_wait, hipEventDisableTiming));
+    if (feeds && (flags & LOAM_FEED_RELEASE) && !L.feed_release)
+      HIP_TRY(hipEventCreateWithFlags(&L.feed_release, hipEventDisableTiming));
+    std::copy(code.begin(), code.end(), L.fail_new.begin());
+  }
+  if (!lanes_push_begin(x)) return LOAM_OK;
+  int n_clear = 0, n_init = 0;
+  lanes_push_kinds(L, n_clear, n_init);
+  hipStream_t st = x->st;
+  if (const int rc = lanes_push_clear(x, n_clear)) return rc;
+  if (feeds && (flags & LOAM_FEED_WAIT)) {  // the gather behind the work enqueued so far on the producer's stream
+    HIP_TRY(hipEventRecord(L.feed_wait, prod));
+    HIP_TRY(hipStreamWaitEvent(st, L.feed_wait, 0));
+  }
+  HIP_TRY(lanes_gather_dev(L, x->cap, st));
+  x->prof.mark("k_lanes_gather_dev");
+  if (feeds && (flags & LOAM_FEED_RELEASE)) {  // the producer's later work behind the gather
+    HIP_TRY(hipEventRecord(L.feed_release, st));
+    HIP_TRY(hipStreamWaitEvent(prod, L.feed_release, 0));
+  }
+  return lanes_push_finish(x, stamp, 0.0, n_clear, n_init, who);
+}
+
+// dev_hooks.h: the device feed's validation and gather on caller-supplied device sweeps
+extern "C" int loam_dev_lanes_gather(int device, int32_t S, int32_t cap, const void* raw_in, uint32_t* out_raw,
+                                     int32_t* out_n) {
+  const loam_cloud_in* raw = (const loam_cloud_in*)raw_in;
+  if (!raw || !out_raw || !out_n || S < 1 || S > LOAM_LANES_MAX || cap < 1 || cap > LOAM_DEV_LANES_GATHER_MAX_CAP)
+    return fail(LOAM_E_INVAL, "loam_dev_lanes_gather: bad argument");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(LOAM_E_HIP, "no HIP device");  // (no CPU path)
+  if (device < 0 || device >= ndev) return fail(LOAM_E_INVAL, "loam_dev_lanes_gather: no such device");
+  HIP_TRY(hipSetDevice(device));
+  const std::vector<int> state((size_t)S, kFeedRuns);
+  std::vector<LaneFeedIn> in;
+  lanes_feed_inputs(raw, S, cap, device, state.data(), in);
+  std::vector<LaneFeedDesc> desc((size_t)S);
+  std::vector<int32_t> code((size_t)S);
+  uint32_t bad = 0;
+  const int verdict = lanes_feed_plan(in.data(), (uint32_t)S, cap, desc.data(), code.data(), &bad);
+  if (verdict != kFeedOk) {
+    char msg[128];
+    lanes_feed_message(verdict, bad, msg, sizeof(msg));
+    return fail(LOAM_E_INVAL, std::string("loam_dev_lanes_gather: ") + msg);
+  }
+  const size_t words = (size_t)S * cap * 4;
+  LaneFeedDesc* desc_d = nullptr;
+  float4* raw_d = nullptr;
+  int* n_d = nullptr;
+  hipError_t e = hipMalloc((void**)&desc_d, (size_t)S * sizeof(LaneFeedDesc));
+  if (e == hipSuccess) e = hipMalloc((void**)&raw_d, words * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&n_d, (size_t)S * sizeof(int));
+  const bool nomem = e != hipSuccess;
+  if (e == hipSuccess) e = hipMemcpy(desc_d, desc.data(), (size_t)S * sizeof(LaneFeedDesc), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemsetD32((hipDeviceptr_t)raw_d, (int)LOAM_DEV_VG_SENTINEL, words);
+  if (e == hipSuccess) e = hipMemsetD32((hipDeviceptr_t)n_d, -1, (size_t)S);
+  if (e == hipSuccess) e = lanes_gather_launch(desc_d, raw_d, n_d, cap, S, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out_raw, raw_d, words * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out_n, n_d, (size_t)S * sizeof(int), hipMemcpyDeviceToHost);
+  if (desc_d) (void)hipFree(desc_d);
+  if (raw_d) (void)hipFree(raw_d);
+  if (n_d) (void)hipFree(n_d);
+  if (e == hipSuccess) return LOAM_OK;
+  (void)hipGetLastError();
+  return nomem ? fail(LOAM_E_NOMEM, "loam_dev_lanes_gather: allocation failed")
+               : fail(LOAM_E_HIP, std::string("loam_dev_lanes_gather: ") + hipGetErrorString(e));
 }
 
 extern "C" int loam_lanes_imu(loam_ctx* x, uint32_t lane, double stamp, const double* quat_xyzw,

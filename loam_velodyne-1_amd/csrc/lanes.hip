@@ -559,6 +559,59 @@ hipError_t lanes_alloc(Lanes& L, int S, int cap, int R, int map_cap, int od_max_
   return hipSuccess;
 }
 
+namespace {
+// loam_lanes_push_device's gather: workgroup (., s) copies lane s's d.n points from
+// the caller's device memory into raw[s * cap ..) as (x, y, z, w) words; workgroup (0, s) writes
+// raw_n[s].  A 16-byte stride at a 16-byte aligned pointer is one 16-byte load and store per point
+// (w as it is, as pack()'s memcpy leaves it); every other layout is three dword loads and w = 0.0f
+// (a 16-byte stride at another alignment: four, w as it is).
+// Words are moved as integers: NaN payloads pass unchanged.
+__global__ __launch_bounds__(256) void k_lanes_gather_dev(const LaneFeedDesc* __restrict__ desc, uint4* __restrict__ raw,
+                                                          int* __restrict__ raw_n, int cap) {
+  const int s = blockIdx.y;
+  const LaneFeedDesc d = desc[s];
+  const int n = min(d.n, cap);
+  if (blockIdx.x == 0 && threadIdx.x == 0) raw_n[s] = n;
+  uint4* dst = raw + (size_t)s * cap;
+  const int step = gridDim.x * 256;
+  if (d.stride == 16 && (d.ptr & 15) == 0) {
+    const uint4* src = (const uint4*)d.ptr;
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += step) dst[t] = src[t];
+    return;
+  }
+  const char* base = (const char*)d.ptr;
+  const size_t stride = (uint32_t)d.stride;
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += step) {
+    const uint32_t* p = (const uint32_t*)(base + (size_t)t * stride);
+    dst[t] = make_uint4(p[0], p[1], p[2], d.stride == 16 ? p[3] : 0u);
+  }
+}
+}  // namespace
+
+hipError_t lanes_gather_launch(const LaneFeedDesc* desc_d, float4* raw, int* raw_n, int cap, int S, hipStream_t st) {
+  if (S <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_lanes_gather_dev, dim3(std::max(1, std::min(64, (cap + 255) / 256)), S), dim3(256), 0, st, desc_d,
+                     (uint4*)raw, raw_n, cap);
+  return hipGetLastError();
+}
+
+hipError_t lanes_gather_dev(Lanes& L, int cap, hipStream_t st) {
+  const hipError_t e = hipMemcpyAsync(L.fd_d, L.fd_h, (size_t)L.S * sizeof(LaneFeedDesc), hipMemcpyHostToDevice, st);
+  return e != hipSuccess ? e : lanes_gather_launch(L.fd_d, L.sr.raw, L.sr.raw_n, cap, L.S, st);
+}
+
+hipError_t lanes_feed_alloc(Lanes& L) {
+  if (L.fd_h && L.fd_d) return hipSuccess;
+  hipError_t e = hipHostMalloc((void**)&L.fd_h, (size_t)L.S * sizeof(LaneFeedDesc), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&L.fd_d, (size_t)L.S * sizeof(LaneFeedDesc));
+  if (e != hipSuccess) {
+    if (L.fd_h) (void)hipHostFree(L.fd_h);
+    if (L.fd_d) (void)hipFree(L.fd_d);
+    L.fd_h = L.fd_d = nullptr;
+  }
+  return e;
+}
+
 hipError_t lanes_imu_alloc(Lanes& L) {
   LanesImu& I = L.imu;
   const size_t S = (size_t)L.S;
@@ -643,6 +696,10 @@ void lanes_free(Lanes& L) {
   if (L.stage_d) (void)hipFree(L.stage_d);
   if (L.tab_h) (void)hipHostFree(L.tab_h);
   if (L.tab_d) (void)hipFree(L.tab_d);
+  if (L.fd_h) (void)hipHostFree(L.fd_h);
+  if (L.fd_d) (void)hipFree(L.fd_d);
+  if (L.feed_wait) (void)hipEventDestroy(L.feed_wait);
+  if (L.feed_release) (void)hipEventDestroy(L.feed_release);
   if (L.out_d) (void)hipFree(L.out_d);
   if (L.out_h) (void)hipHostFree(L.out_h);
   if (L.rs_h) (void)hipHostFree(L.rs_h);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "lanes_feed_plan.hpp"
 #include "mp.hpp"
 #include "od.hpp"
 
@@ -73,6 +74,11 @@ struct Lanes {
   float4* stage_d = nullptr;  // device [S * cap]
   int* tab_h = nullptr;       // pinned [2S]: sizes, then offsets
   int* tab_d = nullptr;       // device [2S]
+  // loam_lanes_push_device's descriptor block (allocated by the first call) and the two events that
+  // order a step's gather against the producer's stream (created by the first call that needs them)
+  LaneFeedDesc* fd_h = nullptr;  // pinned [S]
+  LaneFeedDesc* fd_d = nullptr;  // device [S]
+  hipEvent_t feed_wait = nullptr, feed_release = nullptr;
   int* out_d = nullptr;       // device [S][kLaneOutWords]
   int* out_h = nullptr;       // pinned copy, read by loam_lanes_pull after the step's one synchronisation
   // the node state every lane shares (lockstep): scanRegistration's systemDelay counter,
@@ -136,6 +142,14 @@ hipError_t lanes_imu_put(Lanes& L, size_t bytes, int nrec, hipStream_t st);
 // odometry state (od_init: and transformSum's start, src/laserOdometry.cpp:451-452) and into
 // imu.trans_d, and on mapping steps every lane's (roll, pitch, flag) into the mapping state
 hipError_t lanes_imu_commit(Lanes& L, bool od_init, bool mapping, hipStream_t st);
+
+// the device feed's descriptor block (the first loam_lanes_push_device); on failure nothing is kept
+hipError_t lanes_feed_alloc(Lanes& L);
+// k_lanes_gather_dev: L.fd_h's S descriptors to the device, then every feeding lane's sweep from the
+// caller's device memory into sr.raw at its stride and every lane's size into sr.raw_n
+hipError_t lanes_gather_dev(Lanes& L, int cap, hipStream_t st);
+// the kernel alone on device descriptors (loam_dev_lanes_gather)
+hipError_t lanes_gather_launch(const LaneFeedDesc* desc_d, float4* raw, int* raw_n, int cap, int S, hipStream_t st);
 
 // the restart lists' buffers (the first loam_lanes_restart)
 hipError_t lanes_restart_alloc(Lanes& L);

@@ -5,7 +5,7 @@ stepped by loam_chain_sweep from one thread, through the C-ABI on one GPU (DESIG
                               [--profile-s 64] [--imu] [--restart K,M] [--occupancy N] [--map-import N]
                               [--surround] [--shared stream|big [--from-cap F]]
                               [--score stream|big [--k K1,K2]] [--localize stream|big [--k K1,K2]]
-                              [--out FILE]
+                              [--feed device [--pairs 3]] [--out FILE]
 
 Per S: S lanes over eight distinct VLP-16 synthetic streams laid out cyclically.  The wall time of
 lanes_step (push + pull), and of the push alone (host packing + enqueue), median and range over the
@@ -20,6 +20,15 @@ through loam_lanes_imu, and the yardstick contexts get the same messages through
 their chain_sweep; the time of those calls is reported on its own (imu_feed_ms, per
 step) and is not part of the step times on either side.  One JSON line per S.  Run under a time
 limit.
+
+--feed device (instead of the above): per S, the same steps fed from host memory
+(loam_lanes_push) and from device memory (loam_lanes_push_device; the sweeps uploaded once per stream
+into hipMalloc'd buffers before timing), --pairs times alternating in one process, the host feed
+first: step and push times as above for each feed, the ratios of the medians, whether the device
+feed's last pull equals the host feed's bit for bit, and the device feed once more with every sweep
+in one allocation, whose push needs one pointer query instead of one per lane (pointer_queries_ms =
+the difference of the two pushes).  --profile-s: one profiled run of each feed (the lanes_h2d /
+k_lanes_gather_dev marks).
 
 --restart K,M (instead of the above): per S, one lanes run of --sweeps steps whose
 first half has no restart and whose second half restarts K lanes (K = 0: S / 4) before every M-th
@@ -127,7 +136,46 @@ def imu_schedules(K):
     return out
 
 
-def run_lanes(S, streams, K, map_cap, profile=False, imu=None):
+class DeviceSweeps:
+    """every stream's sweeps uploaded once into hipMalloc'd memory (--feed device): one buffer per
+    stream (consecutive lanes lie in different allocations: the push queries HIP for every lane), or
+    all of them in one arena (one query per push)"""
+
+    def __init__(self, streams, K, arena=False):
+        import ctypes
+        loam.lib()
+        self.hip = hip = ctypes.CDLL("libamdhip64.so")
+        hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        hip.hipFree.argtypes = [ctypes.c_void_p]
+        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        packed = [np.ascontiguousarray(np.concatenate(st[:K]), np.float32) for st in streams]
+        sizes = [(a.nbytes + 255) // 256 * 256 for a in packed]
+        self.bufs = []
+        for n in [sum(sizes)] if arena else sizes:
+            p = ctypes.c_void_p()
+            if hip.hipMalloc(ctypes.byref(p), n) != 0:
+                raise RuntimeError("hipMalloc failed")
+            self.bufs.append(p.value)
+        starts = np.concatenate([[0], np.cumsum(sizes)])
+        bases = [self.bufs[0] + int(starts[i]) if arena else self.bufs[i] for i in range(len(packed))]
+        for base, a in zip(bases, packed):
+            if hip.hipMemcpy(base, a.ctypes.data, a.nbytes, 1) != 0:
+                raise RuntimeError("hipMemcpy failed")
+        self.raws = []  # [stream][k] = (ptr, count, stride)
+        for i, st in enumerate(streams):
+            off, row = 0, []
+            for sw in st[:K]:
+                row.append((bases[i] + off, sw.shape[0], sw.shape[1] * 4))
+                off += sw.shape[0] * sw.shape[1] * 4
+            self.raws.append(row)
+
+    def free(self):
+        for p in self.bufs:
+            self.hip.hipFree(p)
+
+
+def run_lanes(S, streams, K, map_cap, profile=False, imu=None, dev=None):
+    """dev: a DeviceSweeps: the steps go through lanes_push_device (flags 0: the uploads were synchronous)"""
     eng = loam.Engine(loam.default_config(system_delay=1))
     t0 = time.perf_counter()
     eng.lanes_open(S, map_cap)
@@ -138,7 +186,7 @@ def run_lanes(S, streams, K, map_cap, profile=False, imu=None):
     n_prof = [0, 0]
     feed = []
     for k in range(K):
-        raws = [streams[l % N_STREAMS][k] for l in range(S)]
+        raws = [(dev.raws if dev else streams)[l % N_STREAMS][k] for l in range(S)]
         if profile and k == 2 + WARM:
             eng.set_profiling(True)
         if imu:
@@ -148,7 +196,7 @@ def run_lanes(S, streams, K, map_cap, profile=False, imu=None):
                     eng.lanes_imu(l, *m)
             feed.append((time.perf_counter() - t0) * 1e3)
         t0 = time.perf_counter()
-        eng.lanes_push(raws, stamp=0.1 * k)
+        (eng.lanes_push_device if dev else eng.lanes_push)(raws, stamp=0.1 * k)
         t1 = time.perf_counter()
         o = eng.lanes_pull()
         t2 = time.perf_counter()
@@ -174,6 +222,46 @@ def run_lanes(S, streams, K, map_cap, profile=False, imu=None):
         res["imu_feed_ms"] = spread(feed[2 + WARM:])
         res["imu_trans_nonzero_lanes"] = int(np.count_nonzero(np.any(trans != 0, axis=1)))
     return res, last, kern, n_prof
+
+
+def run_feed(S, streams, K, map_cap, pairs=3, profile=False):
+    """--feed device: the same steps fed from host memory (lanes_push) and from device memory
+    (lanes_push_device), alternating in one process, the host feed first; the device feed once more
+    from one arena, where one pointer query serves every lane"""
+    devs = {"device": DeviceSweeps(streams, K), "device_arena": DeviceSweeps(streams, K, arena=True)}
+    runs = []
+    equal = True
+    for p in range(pairs):
+        pair = {}
+        for feed in ("host", "device", "device_arena"):
+            res, last, _, _ = run_lanes(S, streams, K, map_cap, dev=devs.get(feed))
+            pair[feed] = res
+            if feed == "host":
+                ref = last
+            else:
+                equal = equal and all(np.array_equal(np.ascontiguousarray(last[k]).view(np.uint32),
+                                                     np.ascontiguousarray(ref[k]).view(np.uint32)) for k in last)
+        runs.append(pair)
+    line = dict(S=S, sweeps=K, pairs=runs, device_last_pull_equals_host=bool(equal))
+    for kind in ("mapped", "unmapped"):
+        ratios = [r["host"][f"step_{kind}_ms"]["median"] / r["device"][f"step_{kind}_ms"]["median"] for r in runs]
+        line[f"host_over_device_{kind}"] = [round(v, 3) for v in ratios]
+        line[f"device_below_host_{kind}"] = bool(min(ratios) > 1.0)
+    # what the per-lane pointer queries cost: the push with a query for every lane against the push
+    # whose lanes all lie in one allocation (one query)
+    q = [r["device"]["push_mapped_ms"]["median"] - r["device_arena"]["push_mapped_ms"]["median"] for r in runs]
+    line["pointer_queries_ms"] = [round(v, 4) for v in q]
+    line["push_device_ms"] = [r["device"]["push_mapped_ms"]["median"] for r in runs]
+    if profile:
+        kerns = {}
+        for feed in ("host", "device"):
+            _, _, kern, n_prof = run_lanes(S, streams, K, map_cap, profile=True, dev=devs.get(feed))
+            kerns[feed] = dict(device_ms_per_step=kern, device_ms_per_step_total=round(sum(kern.values()), 4),
+                               steps=n_prof[0] + n_prof[1])
+        line["profiled"] = kerns
+    for d in devs.values():
+        d.free()
+    return line
 
 
 def run_yardstick(n, streams, K, map_cap, imu=None):
@@ -771,6 +859,9 @@ def main():
     ap.add_argument("--localize", default=None,
                     help="stream|big: loam_lanes_localize against S loam_map_localize calls in that map")
     ap.add_argument("--k", default="256,64", help="--score / --localize: poses per lane, paired with --s by position")
+    ap.add_argument("--feed", default="host", choices=("host", "device"),
+                    help="device: steps fed from host and from device memory (lanes_push_device), alternating")
+    ap.add_argument("--pairs", type=int, default=3, help="--feed device: alternating runs of each feed")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     a.shared = a.shared or a.score or a.localize
@@ -840,6 +931,10 @@ def main():
             line = run_restart(S, streams, K, a.map_cap, n, every, False)
             line.update(run_restart(S, streams, K, a.map_cap, n, every, True))
             emit(line)
+        return
+    if a.feed == "device":
+        for S in [int(v) for v in a.s.split(",") if v]:
+            emit(run_feed(S, streams, K, a.map_cap, pairs=a.pairs, profile=S == a.profile_s))
         return
     for S in [int(v) for v in a.s.split(",") if v]:
         res, last, _, _ = run_lanes(S, streams, K, a.map_cap, imu=imu)
