@@ -704,6 +704,49 @@ int loam_lanes_score(loam_ctx *ctx, uint32_t n, const uint32_t *lane /* [n] */, 
 int loam_lanes_localize(loam_ctx *ctx, uint32_t n, const uint32_t *lane /* [n] */, uint32_t k,
                         const loam_pose6 *aft /* [n][k] */, const loam_pose6 *bef /* [n][k] or NULL = zeros */,
                         loam_localize_result *out /* [n][k] */);
+/* The write-back half of the shared mode, between two steps, shared lanes only: the listed lanes'
+ * last pulled mapping frames enter the context's map in one call.  It is laserMapping's
+ * map update (src/laserMapping.cpp:980-1036: insertion, then the VoxelGrid of the frame's valid
+ * cubes) for all listed lanes at once.  Let M be the map as loam_map_export gives it before the call.
+ * A listed lane's stack is the downsampled CornerStack / SurfStack of its last pulled mapping frame,
+ * taken into the map frame with the pose the frame registered its cloud with (transformTobeMapped
+ * after the L-M and the IMU blend, or the predicted pose of a LOAM_LOC_NO_LM frame); its valid set is
+ * that frame's laserCloudValidInd.  Both are read in place on the device.  After the call, per kind
+ * (corner, surf) and cube c:
+ *   content(c) = M(c) ++ the stack points of lane[0] that fall into c ++ those of lane[1] ++ ...
+ * (each lane's points in stack order, c by the reference's cube formula about the map's centre); if c
+ * is in the union of the listed lanes' valid sets, content(c) goes through one PCL VoxelGrid (leaf
+ * 0.2 corner, 0.4 surf), otherwise it stays the concatenation.  The result depends on M, the listed
+ * lanes' frames and the order of the list only.  With n = 1 it is, bit for bit, the map a context
+ * holds that imported M with the lane's Aft / Bef and was given the lane's sweep by loam_mapping.
+ * No lane state, no pose, not the context's Bef / Aft or surround_phase and not the grid centre
+ * change, and the grid is never recentred; /laser_cloud_surround of the context's last own frame is
+ * no longer due (as after loam_map_import).  The next step reads the new map; loam_mapping /
+ * loam_chain_sweep on the context continue in it.  The call synchronises.
+ * Commit before anything moves the map's centre (a loam_map_import with another centre, a
+ * loam_mapping / loam_chain_sweep on the context that recentres the grid): the lanes' valid sets are
+ * cube indices about the centre their frames ran with, and this is not checked.
+ * LOAM_E_INVAL, with nothing changed and out unwritten: a null argument, lanes not open or opened
+ * with loam_lanes_open, a step in flight, n == 0 or n > n_lanes, a lane index >= n_lanes, a lane
+ * listed twice, a failed lane, a lane between loam_lanes_restart and the pull of its init step, a
+ * lane whose last pulled step was not a mapping frame of its own with LOAM_LOC_SOLVED or
+ * LOAM_LOC_NO_LM (LOAM_LOC_NONE, LOAM_LOC_OFFGRID, inside system_delay), a lane whose frame was
+ * committed since that pull (a frame enters the map once), a map whose last update overflowed
+ * map_capacity.
+ * LOAM_E_CAPACITY, with the map unchanged bit for bit and only out->map_points written: the VoxelGrid
+ * input of the union's cubes (old content and appended points, both kinds) or the map after the
+ * commit exceeds map_capacity.  map_points then holds, per kind, the points of the one that did not
+ * fit (the VoxelGrid input is found first); their sum is the map_capacity that part needs.
+ * LOAM_E_NOMEM when the first call's working set (sized by n_lanes and the stack capacity, 24 bytes
+ * per stack point and lane) cannot be allocated; LOAM_E_HIP. */
+typedef struct {
+  uint64_t inserted[2];   /* corner, surf points appended (inside the grid) */
+  uint64_t outside[2];    /* stack points outside the cube grid, dropped as the reference drops them */
+  uint64_t map_points[2]; /* the map's corner / surf points after the commit */
+  uint32_t cubes;         /* cubes of the union of the listed lanes' valid sets */
+} loam_commit_result;
+int loam_lanes_map_commit(loam_ctx *ctx, uint32_t n, const uint32_t *lane /* [n] */, loam_commit_result *out);
+
 /* Frees the lanes' working set (waits for a step in flight).  LOAM_E_INVAL when not open. */
 int loam_lanes_close(loam_ctx *ctx);
 

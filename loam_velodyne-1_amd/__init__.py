@@ -169,6 +169,14 @@ _SCORE_DTYPE = np.dtype([(n, np.float64 if t is ctypes.c_double else np.uint32) 
 
 
 LANES_MAX = 1024  # LOAM_LANES_MAX: lanes of one context
+
+
+class CommitResult(ctypes.Structure):
+    """include/loam/loam.h loam_commit_result: what loam_lanes_map_commit did to the map"""
+    _fields_ = [("inserted", ctypes.c_uint64 * 2), ("outside", ctypes.c_uint64 * 2),
+                ("map_points", ctypes.c_uint64 * 2), ("cubes", ctypes.c_uint32)]
+
+
 FEED_WAIT, FEED_RELEASE = 1, 2  # LOAM_FEED_*: loam_lanes_push_device's ordering against the producer's stream
 
 
@@ -198,7 +206,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
            "loam_lanes_restart", "loam_lanes_map_import", "loam_lanes_surround",
            "loam_lanes_open_shared", "loam_lanes_set_pose", "loam_lanes_localize_info", "loam_lanes_score",
-           "loam_lanes_localize", "loam_lanes_push_device",
+           "loam_lanes_localize", "loam_lanes_push_device", "loam_lanes_map_commit",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -268,6 +276,7 @@ def lib():
         L.loam_lanes_localize.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), ctypes.c_uint32, P(Pose6), P(Pose6),
                                           P(LocalizeResult)]
         L.loam_lanes_push_device.argtypes = [PP, P(ctypes.c_double), P(CloudIn), ctypes.c_void_p, ctypes.c_uint32]
+        L.loam_lanes_map_commit.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), P(CommitResult)]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -756,6 +765,26 @@ class Engine:
         b = None if bef is None else poses(bef)
         idx = (ctypes.c_uint32 * max(n, 1))(*lanes)
         _check(lib().loam_lanes_set_pose(self.h, n, idx, a.ctypes.data_as(P), None if b is None else b.ctypes.data_as(P)))
+
+    def lanes_map_commit(self, lanes):
+        """the listed shared lanes' last pulled mapping frames into this context's map in one call
+        (loam_lanes_map_commit): per cube the map's content, then each listed lane's stack points in
+        list order, the cubes of the lanes' valid sets downsampled once.  Returns a dict of
+        loam_commit_result's fields (inserted / outside / map_points as (corner, surf) pairs, cubes).
+        LoamError with LOAM_E_CAPACITY leaves the map as it was; only that error carries a `commit`
+        attribute, whose map_points are the points that did not fit."""
+        lanes = [int(l) for l in np.atleast_1d(lanes)]
+        idx = (ctypes.c_uint32 * max(len(lanes), 1))(*lanes)
+        r = CommitResult()
+        rc = lib().loam_lanes_map_commit(self.h, len(lanes), idx, ctypes.byref(r))
+        out = {"inserted": (int(r.inserted[0]), int(r.inserted[1])), "outside": (int(r.outside[0]), int(r.outside[1])),
+               "map_points": (int(r.map_points[0]), int(r.map_points[1])), "cubes": int(r.cubes)}
+        if rc != LOAM_OK:
+            err = LoamError(rc, lib().loam_last_error().decode())
+            if rc == LOAM_E_CAPACITY:
+                err.commit = out
+            raise err
+        return out
 
     def lanes_localize_info(self):
         """every shared lane's mapping frame of the last pulled step as map_localize reports a

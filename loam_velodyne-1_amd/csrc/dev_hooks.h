@@ -136,6 +136,17 @@ int loam_dev_sr_ring_of(int device, int32_t n_rings, int32_t ring_model, float r
 int loam_dev_lanes_gather(int device, int32_t S, int32_t cap, const void* raw /* loam_cloud_in [S] */, uint32_t* out_raw,
                           int32_t* out_n);
 
+/* What loam_lanes_map_commit reads of one shared lane (include/loam/loam.h): the lane's
+ * downsampled CornerStack / SurfStack of its last pulled mapping frame in the map frame, computed by
+ * the commit's own transform, in stack order, the points outside the cube grid included
+ * (corner_out: 120 n_rings x 4 floats, surf_out: max_points x 4 floats at most; n_out: the two
+ * counts), and the frame's valid cubes (valid_out [125], *n_valid).  So that a test can restate a
+ * commit of several lanes on the host.  LOAM_E_INVAL where the commit would
+ * refuse the lane. */
+struct loam_ctx;
+int loam_dev_lanes_commit_input(struct loam_ctx* ctx, uint32_t lane, float* corner_out, float* surf_out,
+                                uint32_t* n_out /* [2] */, int32_t* valid_out /* [125] */, uint32_t* n_valid);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2520,6 +2520,123 @@ extern "C" int loam_lanes_localize_info(loam_ctx* x, loam_localize_result* out) 
   return LOAM_OK;
 }
 
+namespace {
+// loam_lanes_map_commit's refusals of the call itself and of the lane list (lanes_commit_check's
+// rules with their messages): LOAM_OK, or the failure
+int lanes_commit_refused(const std::string& who, loam_ctx* x, const uint32_t* lane, uint32_t n) {
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
+  if (!L.shared)
+    return fail(LOAM_E_INVAL, who + ": the lanes have their own maps (loam_lanes_open), which they write themselves");
+  if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
+  if (!L.pulled) return fail(LOAM_E_INVAL, who + ": no step was pulled");
+  std::vector<char> seen;
+  std::vector<int32_t> status((size_t)L.S);
+  for (int l = 0; l < L.S; ++l) status[l] = L.loc_info[l].status;
+  uint32_t bad = 0;
+  const int why = lanes_commit_check(lane, n, L.S, L.fail.data(), L.life.data(), status.data(), L.committed.data(), seen, &bad);
+  if (why == kCommitOk) return LOAM_OK;
+  if (why == kCommitCount) return fail(LOAM_E_INVAL, who + ": n must be in [1, n_lanes]");
+  const std::string at = who + ": lane[" + std::to_string(bad) + "] = " + std::to_string(lane[bad]);
+  if (why == kCommitRange) return fail(LOAM_E_INVAL, at + " is out of range");
+  if (why == kCommitTwice) return fail(LOAM_E_INVAL, at + " is listed twice");
+  if (why == kCommitFailed) return fail(LOAM_E_INVAL, at + " has failed (loam_lanes_restart first)");
+  if (why == kCommitWaits) return fail(LOAM_E_INVAL, at + " waits for its init step");
+  if (why == kCommitOffgrid)
+    return fail(LOAM_E_INVAL, at + " was not evaluated (LOAM_LOC_OFFGRID: the frame would recentre the grid)");
+  if (why == kCommitDone) return fail(LOAM_E_INVAL, at + ": its last frame is in the map already (a frame enters the map once)");
+  return fail(LOAM_E_INVAL, at + " ran no mapping frame on the last pulled step");
+}
+// the store's error word after the context's queued work has been drained
+int store_overflowed(loam_ctx* x, const std::string& who) {
+  int err = 0;
+  HIP_TRY(hipMemcpy(&err, x->mp1.istate + kMiErr, sizeof(int), hipMemcpyDeviceToHost));
+  if (err & ERR_CAP_MAP) return fail(LOAM_E_INVAL, who + ": the last map update exceeded map_capacity, the store is not valid");
+  return LOAM_OK;
+}
+}  // namespace
+
+// The listed lanes' last frames into the context's streaming store (mp_lanes_commit):
+// built in the store's idle pool, which becomes the current one after the result block says it fits.
+extern "C" int loam_lanes_map_commit(loam_ctx* x, uint32_t n, const uint32_t* lane, loam_commit_result* out) {
+  if (!x || !lane || !out) return fail(LOAM_E_INVAL, "null argument");
+  const std::string who = "loam_lanes_map_commit";
+  if (const int rc = lanes_commit_refused(who, x, lane, n)) return rc;
+  Lanes& L = x->lanes;
+  if (const int rc = map_drain(x)) return rc;
+  if (const int rc = store_overflowed(x, who)) return rc;
+  if (mp_commit_alloc(L.cm, L.S, L.mp.cap_stack) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LOAM_E_NOMEM, who + ": allocation failed");
+  }
+  MpBuffers& s = x->mp1;
+  for (uint32_t i = 0; i < n; ++i) L.cm.list_h()[i] = (int)lane[i];
+  hipStream_t st = x->st;
+  x->prof.begin(st);
+  hipError_t he = mp_lanes_commit(L.cm, L.mp, s, (int)n, st, &x->prof);
+  const hipError_t se = hipStreamSynchronize(st);
+  if (he == hipSuccess) he = se;
+  x->prof.collect();
+  if (he != hipSuccess) return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
+  const int* r = L.cm.res_h();
+  if (r[kCrErr]) {
+    const int at = r[kCrErr] == kCrErrVin ? kCrVin : kCrMap;
+    out->map_points[0] = (uint64_t)r[at];
+    out->map_points[1] = (uint64_t)r[at + 1];
+    return fail(LOAM_E_CAPACITY, who + (r[kCrErr] == kCrErrVin ? ": the VoxelGrid input of the union's cubes exceeds map_capacity"
+                                                                 : ": the map after the commit exceeds map_capacity"));
+  }
+  s.pool_cur = 1 - s.pool_cur;
+  // (statistics only, as loam_map_import: no frame of the context built this store)
+  *(int*)(x->xb.h + kXferMpUpd + 4 * (1 - s.pool_cur)) = 0;
+  x->surround_due = false;
+  for (uint32_t i = 0; i < n; ++i) L.committed[lane[i]] = 1;
+  for (int k = 0; k < 2; ++k) {
+    out->inserted[k] = (uint64_t)r[kCrIns + k];
+    out->outside[k] = (uint64_t)r[kCrOut + k];
+    out->map_points[k] = (uint64_t)r[kCrMap + k];
+  }
+  out->cubes = (uint32_t)r[kCrCubes];
+  return LOAM_OK;
+}
+
+// the hook of dev_hooks.h: a lane's stack in the map frame and its valid set, as the commit reads them
+extern "C" int loam_dev_lanes_commit_input(loam_ctx* x, uint32_t lane, float* corner_out, float* surf_out,
+                                           uint32_t* n_out, int32_t* valid_out, uint32_t* n_valid) {
+  if (!x || !corner_out || !surf_out || !n_out || !valid_out || !n_valid) return fail(LOAM_E_INVAL, "null argument");
+  const std::string who = "loam_dev_lanes_commit_input";
+  if (const int rc = lanes_commit_refused(who, x, &lane, 1)) return rc;
+  Lanes& L = x->lanes;
+  const MpBuffers& w = L.mp;
+  if (const int rc = map_drain(x)) return rc;
+  float4 *dC = nullptr, *dS = nullptr;
+  hipError_t he = hipMalloc((void**)&dC, (size_t)w.capC * sizeof(float4));
+  if (he == hipSuccess) he = hipMalloc((void**)&dS, (size_t)w.capS * sizeof(float4));
+  int cnt[2] = {0, 0}, nv = 0;
+  if (he == hipSuccess) he = mp_lanes_commit_input(w, (int)lane, dC, dS, x->st);
+  if (he == hipSuccess) he = hipStreamSynchronize(x->st);
+  if (he == hipSuccess) he = hipMemcpy(cnt, w.sseg_cnt + (size_t)lane * 2, sizeof(cnt), hipMemcpyDeviceToHost);
+  if (he == hipSuccess)
+    he = hipMemcpy(&nv, w.istate + (size_t)lane * kMpStateInts + kMiNValid, sizeof(int), hipMemcpyDeviceToHost);
+  cnt[0] = std::min(std::max(cnt[0], 0), w.capC);
+  cnt[1] = std::min(std::max(cnt[1], 0), w.capS);
+  nv = std::min(std::max(nv, 0), kMaxValid);
+  if (he == hipSuccess && cnt[0]) he = hipMemcpy(corner_out, dC, (size_t)cnt[0] * sizeof(float4), hipMemcpyDeviceToHost);
+  if (he == hipSuccess && cnt[1]) he = hipMemcpy(surf_out, dS, (size_t)cnt[1] * sizeof(float4), hipMemcpyDeviceToHost);
+  if (he == hipSuccess && nv)
+    he = hipMemcpy(valid_out, w.valid + (size_t)lane * kMaxValid, (size_t)nv * sizeof(int), hipMemcpyDeviceToHost);
+  if (dC) (void)hipFree(dC);
+  if (dS) (void)hipFree(dS);
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
+  }
+  n_out[0] = (uint32_t)cnt[0];
+  n_out[1] = (uint32_t)cnt[1];
+  *n_valid = (uint32_t)nv;
+  return LOAM_OK;
+}
+
 // k pose guesses for each of n listed lanes against the whole streaming map (score.hpp, DESIGN.md
 // §31): loam_map_score's sequence with the lanes' Last clouds read in place.  The lanes' nlast
 // words come down with the map's sizes; the host then knows every listed lane's tiles.
@@ -3167,6 +3284,7 @@ extern "C" int loam_lanes_pull(loam_ctx* x, loam_lane_out* out) {
     std::memset(&none, 0, sizeof(none));
     none.status = LOAM_LOC_NONE;
     L.loc_info.assign((size_t)S, none);
+    L.committed.assign((size_t)S, 0);  // (loam_lanes_map_commit: the frames of this pull are new)
   }
   if (!L.step_ran) {  // inside system_delay: nothing was enqueued
     L.in_flight = false;

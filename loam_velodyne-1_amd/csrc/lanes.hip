@@ -556,6 +556,7 @@ hipError_t lanes_alloc(Lanes& L, int S, int cap, int R, int map_cap, int od_max_
   L.fail_new.assign(S, LOAM_OK);
   L.nreg.assign(S, 0);
   L.life.assign(S, LaneLife());
+  L.committed.assign(shared ? S : 0, 0);
   return hipSuccess;
 }
 
@@ -712,6 +713,7 @@ void lanes_free(Lanes& L) {
   if (L.sp_d) (void)hipFree(L.sp_d);
   if (L.loc_h) (void)hipHostFree(L.loc_h);
   if (L.loc_d) (void)hipFree(L.loc_d);
+  mp_commit_free(L.cm);
   L = Lanes();
 }
 

@@ -108,6 +108,10 @@ struct Lanes {
   int* loc_d = nullptr;        // device [S][kLocResWords]
   int* loc_h = nullptr;        // pinned copy
   std::vector<loam_localize_result> loc_info;  // [S]
+  // loam_lanes_map_commit: its working set (allocated by the first call) and which
+  // lanes' last pulled frames are in the map already (cleared by every pull)
+  MpCommit cm;
+  std::vector<char> committed;  // [S]
   // the protocol: a step pushed and not yet pulled; what that step published; whether the last
   // pulled step left registered clouds
   bool in_flight = false, step_ran = false, have_reg = false;
@@ -179,6 +183,33 @@ inline int lanes_list_check(const uint32_t* lane, uint32_t n, int S, const int* 
     if (life[l].wait >= 0) return kLaneListWaits;
   }
   return kLaneListOk;
+}
+
+// loam_lanes_map_commit's argument check of the lane list (host only): 0, or which rule the count or
+// lane[*bad] breaks.  lane[] is read below n only, and only when n is in [1, S]; fail / life / status /
+// committed have S entries and are read at indices below S: a lane's sticky failure, its life cycle,
+// the LOAM_LOC_* status of its last pulled step (LOAM_LOC_NONE where it ran no mapping frame of its
+// own) and whether that frame was committed since
+enum { kCommitOk = 0, kCommitCount, kCommitRange, kCommitTwice, kCommitFailed, kCommitWaits, kCommitNoFrame,
+       kCommitOffgrid, kCommitDone };
+inline int lanes_commit_check(const uint32_t* lane, uint32_t n, int S, const int* fail, const LaneLife* life,
+                              const int32_t* status, const char* committed, std::vector<char>& seen, uint32_t* bad) {
+  *bad = 0;
+  if (S <= 0 || n == 0 || n > (uint32_t)S) return kCommitCount;
+  seen.assign((size_t)S, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    *bad = i;
+    const uint32_t l = lane[i];
+    if (l >= (uint32_t)S) return kCommitRange;
+    if (seen[l]) return kCommitTwice;
+    seen[l] = 1;
+    if (fail[l] != LOAM_OK) return kCommitFailed;
+    if (life[l].wait >= 0) return kCommitWaits;
+    if (status[l] == LOAM_LOC_OFFGRID) return kCommitOffgrid;
+    if (status[l] != LOAM_LOC_SOLVED && status[l] != LOAM_LOC_NO_LM) return kCommitNoFrame;
+    if (committed[l]) return kCommitDone;
+  }
+  return kCommitOk;
 }
 
 // loam_lanes_open_shared's capacity arithmetic (host only): LOAM_OK, or which limit the arguments

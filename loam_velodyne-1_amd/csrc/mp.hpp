@@ -305,5 +305,57 @@ hipError_t mp_alloc_shared(MpBuffers& b, int P, int R, int cap_pts, int from_cap
 // takes the persistent form.
 void mp_lanes_shared_frame(MpBuffers& w, MpBuffers& s, const MpInput& in, int* res, hipStream_t st, Prof* prof);
 
+// ---- shared lanes: the listed lanes' last frames into the store (loam_lanes_map_commit) ----
+// The map update of mp_update for many stacks and one store: every listed lane's stack (w.stack, read
+// in place with the lane's rotation, as k_mp_register maps its cloud) appended to the store's cubes in
+// list order, the cubes of the union of the lanes' valid sets through one VoxelGrid each, the result
+// compacted into the store's idle pool.  A key is kind * kCubeNum + cube, the export's canonical key.
+// The result block (device and pinned copy): kCrErr 0 = done; kCrErrVin: the VoxelGrid input of the
+// union's cubes (kCrVin, per kind) exceeds map_cap; kCrErrMap: the new map (kCrMap, per kind) does.
+constexpr int kCmResWords = 16;
+enum { kCrErr = 0, kCrIns = 1, kCrOut = 3, kCrMap = 5, kCrCubes = 7, kCrVin = 8 };
+enum { kCrErrVin = 1, kCrErrMap = 2 };
+constexpr int kCmUniWords = (kCubeNum + 31) / 32;
+// the words one memset clears in front of a commit: the union bitmap, the VoxelGrid's list counters, the result block
+constexpr int kCmZeroInts = kCmUniWords + 4 + kCmResWords;
+struct MpCommit {
+  int S = 0, cap_stack = 0, kmax = 0;  // lanes it holds, their stack stride, key entries per lane
+  // per listed lane (by list position): a stack point's entry in the lane's key list (-1: outside the
+  // grid) and its stable rank among the lane's points of that key
+  int* ent_of = nullptr;    // [S][cap_stack]
+  int* rank_of = nullptr;   // [S][cap_stack]
+  int* lkey = nullptr;      // [S][kmax] the keys the lane's stack touches
+  int* lcnt = nullptr;      // [S][kmax] their counts; behind k_cm_prefix the points of earlier listed lanes in the key
+  int* lnk = nullptr;       // [S] entries of the lane
+  float4* app = nullptr;    // [S * cap_stack] the appended points (map frame) grouped by key, lanes in list order
+  int* list = nullptr;      // [S] the call's lane list
+  int* zero = nullptr;      // [kCmZeroInts] uni | counts | res
+  LOAM_HD unsigned* uni() const { return (unsigned*)zero; }  // the union of the listed lanes' valid cubes, a bit per cube
+  LOAM_HD int* counts() const { return zero + kCmUniWords; }  // VgJob::counts ([2]: the segment list's length)
+  LOAM_HD int* res() const { return zero + kCmUniWords + 4; }
+  // per key: appended points (offset in app, count); the VoxelGrid segment of a union cube's key
+  int *aoff = nullptr, *acnt = nullptr;                                         // [kMapKeys]
+  int *seg_b = nullptr, *seg_e = nullptr, *seg_cnt = nullptr, *vlist = nullptr;  // [kMapKeys]
+  float* seg_leaf = nullptr;
+  int* lists[2] = {nullptr, nullptr};  // the cascade's lists [kMapKeys]
+  int* pin = nullptr;       // pinned: the lane list [S], then the result block
+  int* list_h() const { return pin; }
+  int* res_h() const { return pin + S; }
+};
+// the working set for S lanes of cap_stack stack points (the first commit); on failure nothing is kept
+hipError_t mp_commit_alloc(MpCommit& c, int S, int cap_stack);
+void mp_commit_free(MpCommit& c);
+// bytes mp_commit_alloc asks the device for (DESIGN.md §34 derives them)
+size_t mp_commit_bytes(int S, int cap_stack);
+// the n lanes of c.list_h() (indices below w.P, each once) into the store s: everything up to the new
+// pool and slot table and the result block's copy into c.res_h().  The caller synchronises st, reads
+// the block and, where kCrErr is 0, switches the store (s.pool_cur = 1 - s.pool_cur).  Only the
+// commit's buffers, the store's idle pool / slot table and its VoxelGrid scratch (vin, vout, the sort
+// arrays) are written.
+hipError_t mp_lanes_commit(MpCommit& c, const MpBuffers& w, MpBuffers& s, int n, hipStream_t st, Prof* prof);
+// lane `lane`'s stack in the map frame by the commit's transform, in stack order (corner into outC,
+// surf into outS: device, capC / capS points) — loam_dev_lanes_commit_input
+hipError_t mp_lanes_commit_input(const MpBuffers& w, int lane, float4* outC, float4* outS, hipStream_t st);
+
 }  // namespace loam
 #endif

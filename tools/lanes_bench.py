@@ -5,7 +5,7 @@ stepped by loam_chain_sweep from one thread, through the C-ABI on one GPU (DESIG
                               [--profile-s 64] [--imu] [--restart K,M] [--occupancy N] [--map-import N]
                               [--surround] [--shared stream|big [--from-cap F]]
                               [--score stream|big [--k K1,K2]] [--localize stream|big [--k K1,K2]]
-                              [--feed device [--pairs 3]] [--out FILE]
+                              [--commit stream|big] [--feed device [--pairs 3]] [--out FILE]
 
 Per S: S lanes over eight distinct VLP-16 synthetic streams laid out cyclically.  The wall time of
 lanes_step (push + pull), and of the push alone (host packing + enqueue), median and range over the
@@ -95,7 +95,19 @@ alternating three times: one loam_lanes_localize call, and the parent's only way
 calls of k candidates each with the lane's Last clouds and od_sum handed in from host memory (from
 node-call contexts, not timed).  Wall time per way, median and range of 5 after a warm-up; one more
 call of each under loam_set_profiling for the device time per kernel and the share of the two rows
-kernels; sampled rows of both ways compared bit for bit in every pair."""
+kernels; sampled rows of both ways compared bit for bit in every pair.
+
+--commit stream|big (instead of the above): S shared lanes in that map with
+map_capacity = the power of two that holds the map and S stacks of 4096 points.  Behind every mapping
+step one loam_lanes_map_commit of all live lanes: its wall time, median and range over the mapping
+steps after the warm-up, --pairs times alternating with the yardstick, the parent's way to the same
+effect: S loam_mapping calls per mapping step on a context holding the map, fed each stream's
+CornerLast / SurfLast / fullEnd of that step from host memory (from node calls, not timed; shared
+lanes hand out no feature clouds, so the cost of S downloads is reported from loam_lanes_registered).
+Also: hipMemGetInfo around the first commit against the derived working set, the map's size after
+every commit, and the mapping steps' wall time with commits against one more run without.
+--profile-s S: one more fleet at that S with every timed commit under loam_set_profiling (device ms per
+stage, summed over the commits)."""
 import argparse
 import importlib
 import json
@@ -693,6 +705,135 @@ def run_shared(S, streams, K, name, M, from_cap, pairs=3, profile=False):
     return line
 
 
+def commit_bytes(S, cap_stack):
+    """device bytes of loam_lanes_map_commit's working set as DESIGN.md §34 derives them"""
+    keys = 2 * 21 * 11 * 21
+    return S * cap_stack * 24 + S * min(cap_stack, keys) * 8 + S * 8 + (152 + 4 + 16) * 4 + keys * 9 * 4
+
+
+def run_commit(S, streams, K, name, M, from_cap, pairs=3, profile=False):
+    """one JSON line: S shared lanes in the map M; behind every mapping step after the
+    warm-up one loam_lanes_map_commit of all S lanes, against the parent's way to the same effect: S
+    loam_mapping calls on a context holding M, one lane's clouds after the other.  The yardstick's
+    clouds are each stream's CornerLast / SurfLast / fullEnd of that step from node calls (shared
+    lanes hand out no feature clouds; what a download would cost is reported from
+    loam_lanes_registered).  `pairs` alternating (commit, yardstick) runs; the first commit's device
+    memory; the mapping steps of a run with commits against the same run without."""
+    kw = dict(corner=M["corner"], surf=M["surf"], center=M["center"], surround_phase=4)
+    total = int(M["corner"].shape[0] + M["surf"].shape[0])
+    cfg = loam.default_config()
+    pts_cap = int(cfg.max_points) + 120 * int(cfg.n_rings)  # a lane's stack capacity
+    # the VoxelGrid input of a commit holds the union's cubes and every lane's stack before it shrinks
+    cap = 1 << int(np.ceil(np.log2(total + S * 4096)))
+    cap = max(cap, 1 << 17)
+
+    def fleet(commit, prof=False):
+        eng = loam.Engine(loam.default_config(system_delay=1, map_capacity=cap))
+        eng.set_tuning(batch_streams=0)
+        eng.map_import(**kw)
+        eng.lanes_open_shared(S, from_cap)
+        eng.lanes_set_pose(list(range(S)), np.zeros(6, np.float32))
+        lanes = list(range(S))
+        steps, commits, downloads, grown, ws = [], [], [], [], None
+        res = refused = None
+        device = {}
+        committing = commit
+        for k in range(K):
+            raws = [streams[l % N_STREAMS][k] for l in range(S)]
+            t0 = time.perf_counter()
+            eng.lanes_push(raws, stamp=0.1 * k)
+            o = eng.lanes_pull()
+            t1 = time.perf_counter()
+            if not o["mapped"].max():
+                continue
+            if k >= 2 + WARM:
+                steps.append((t1 - t0) * 1e3)
+            if not commit:
+                continue
+            # the lanes a commit takes: live, and their frame ran (LOAM_LOC_SOLVED or LOAM_LOC_NO_LM)
+            st = eng.lanes_localize_info()["status"]
+            ok = [l for l in lanes if o["status"][l] == 0 and o["mapped"][l] and st[l] in (loam.LOC_SOLVED, loam.LOC_NO_LM)]
+            if not ok:
+                continue
+            if k >= 2 + WARM:  # (what downloading one cloud per lane costs: the registered clouds)
+                t0 = time.perf_counter()
+                for l in ok:
+                    eng.lanes_registered(l)
+                downloads.append((time.perf_counter() - t0) * 1e3)
+            free0 = _mem_free()
+            t0 = time.perf_counter()
+            try:
+                if prof and k >= 2 + WARM:  # (device ms per launch between the marks, summed over the timed commits)
+                    for name_, ms in _profiled(eng, lambda: eng.lanes_map_commit(ok)).items():
+                        device[name_] = round(device.get(name_, 0.0) + ms, 4)
+                    device["commits"] = device.get("commits", 0) + 1
+                    continue
+                res = eng.lanes_map_commit(ok)
+            except loam.LoamError as err:  # (reported, and the run goes on without further commits)
+                refused = str(err)[:160]
+                commit = False
+                continue
+            t1 = time.perf_counter()
+            if ws is None:
+                ws = free0 - _mem_free()
+            if k >= 2 + WARM:
+                commits.append((t1 - t0) * 1e3)
+            grown.append(sum(res["map_points"]))
+        out = dict(step_mapped_ms=spread(steps), lanes_failed=int(np.count_nonzero(o["status"] != 0)))
+        if committing:
+            out.update(commit_ms=spread(commits), registered_download_ms=spread(downloads), working_set_bytes=ws,
+                       map_points_after_commits=grown, last_commit=res, commit_refused=refused)
+        if prof:
+            out["device_ms"] = device
+        eng.lanes_close()
+        eng.close()
+        return out
+
+    # the yardstick's clouds: per stream and step what loam_odometry publishes for laserMapping
+    feats = []
+    for i in range(min(S, N_STREAMS)):
+        A = loam.Engine(loam.default_config(system_delay=1))
+        per = {}
+        for k in range(K):
+            rc, f = A.scan_registration(streams[i][k], stamp=0.1 * k)
+            if rc == 0:
+                pub, pose, cl, sl, full = A.odometry(f, stamp=0.1 * k)
+                if pub == 7:
+                    per[k] = (pose, cl, sl, full)
+        A.close()
+        feats.append(per)
+
+    def yard():
+        Y = loam.Engine(loam.default_config(system_delay=1, map_capacity=cap))
+        Y.map_import(**kw)
+        ts, failed = [], None
+        for k in sorted(set.intersection(*[set(f) for f in feats])):
+            t0 = time.perf_counter()
+            try:
+                for l in range(S):
+                    Y.mapping(*feats[l % len(feats)][k], stamp=0.1 * k)
+            except loam.LoamError as err:
+                failed = str(err)[:160]
+                break
+            if k >= 2 + WARM:
+                ts.append((time.perf_counter() - t0) * 1e3)
+        Y.close()
+        return dict(mapping_calls_ms=spread(ts), mapping_failed=failed)
+    runs = [dict(commit=fleet(True), yardstick=yard()) for _ in range(pairs)]
+    plain = fleet(False)
+    line = dict(commit_leg=name, S=S, sweeps=K, map_points=total, map_capacity=cap, lane_from_capacity=from_cap,
+                working_set_bytes_derived=commit_bytes(S, pts_cap), pairs=runs, steps_without_commits=plain)
+    both = [(r["commit"]["commit_ms"], r["yardstick"]["mapping_calls_ms"]) for r in runs]
+    both = [(c, y) for c, y in both if c and y]  # (a side without a timed mapping step has no figure)
+    line["pairs_timed"] = len(both)
+    line["commit_below_yardstick"] = [bool(c["median"] < y["median"]) for c, y in both]
+    line["ranges_apart"] = [bool(c["max"] < y["min"]) for c, y in both]
+    line["yardstick_over_commit"] = [round(y["median"] / c["median"], 1) for c, y in both]
+    if profile:
+        line["profile_commit"] = fleet(True, prof=True)
+    return line
+
+
 def _profiled(eng, call):
     """device ms per kernel and the work counters of one call under loam_set_profiling"""
     eng.set_profiling(True)
@@ -858,13 +999,15 @@ def main():
     ap.add_argument("--score", default=None, help="stream|big: loam_lanes_score against S loam_map_score calls in that map")
     ap.add_argument("--localize", default=None,
                     help="stream|big: loam_lanes_localize against S loam_map_localize calls in that map")
+    ap.add_argument("--commit", default=None,
+                    help="stream|big: loam_lanes_map_commit of all lanes against S loam_mapping calls in that map")
     ap.add_argument("--k", default="256,64", help="--score / --localize: poses per lane, paired with --s by position")
     ap.add_argument("--feed", default="host", choices=("host", "device"),
                     help="device: steps fed from host and from device memory (lanes_push_device), alternating")
     ap.add_argument("--pairs", type=int, default=3, help="--feed device: alternating runs of each feed")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.shared = a.shared or a.score or a.localize
+    a.shared = a.shared or a.score or a.localize or a.commit
     K = 40 if a.occupancy else 23 if a.surround else a.sweeps
     streams = [sg.stream_sweeps(K, 1 + i) for i in range(N_STREAMS)]
     imu = imu_schedules(K) if a.imu else None
@@ -898,6 +1041,11 @@ def main():
         if a.score:
             for S, k in zip([int(v) for v in a.s.split(",") if v], [int(v) for v in a.k.split(",") if v]):
                 emit(run_score(S, k, streams, a.score, M, F))
+            return
+        if a.commit:
+            for S in [int(v) for v in a.s.split(",") if v]:
+                # (the map grows with every commit and a lane gathers from all of it: room for it)
+                emit(run_commit(S, streams, K, a.commit, M, max(F, 1 << 17), pairs=a.pairs, profile=S == a.profile_s))
             return
         if a.localize:
             for S, k in zip([int(v) for v in a.s.split(",") if v], [int(v) for v in a.k.split(",") if v]):
