@@ -92,6 +92,9 @@ def test_degeneracy_stream_parity(loam, oc, sg):
 
 
 def test_degeneracy_batch_parity(loam, oc, sg):
+    """a batch of 3: the small-batch kernels only (k_od_rows_small of P <= 63, k_mp_lm_small of
+    P <= 4).  The batch forms of P >= 64 on degenerate, NaN-guarded and row-starved problems:
+    tests/test_gpu_batch_branches.py"""
     prev, cur = sg.single_problem(0)
     prevs = [scenarios.ground_only(prev), scenarios.ground_only(prev, -1.2), prev]
     curs = [scenarios.ground_only(cur), scenarios.ground_only(cur, -1.2), cur]
