@@ -961,7 +961,11 @@ struct MpState {
   int imuFront = 0, imuLast = -1;
   double imuTime[kImuQue] = {0};
   float imuRoll[kImuQue] = {0}, imuPitch[kImuQue] = {0};
-  MpState() : corner(kNum), surf(kNum) {}
+  // the last frame's insertion (:980-1016) for oracle_map_export: stack points pushed into each
+  // cube (corner, surf) before the re-downsampling, and the stack points outside the grid
+  std::vector<int32_t> inserted[2];
+  uint64_t dropped[2] = {0, 0};
+  MpState() : corner(kNum), surf(kNum) { inserted[0].assign(kNum, 0); inserted[1].assign(kNum, 0); }
 };
 
 // :110-197
@@ -1336,19 +1340,31 @@ void mp_body(const Cfg& cfg, MpState& m, const std::vector<P>& cornerLast,
     }
   }
   // :980-1016 insertion
+  for (int kind = 0; kind < 2; ++kind) {
+    m.inserted[kind].assign(kNum, 0);
+    m.dropped[kind] = 0;
+  }
   for (const P& p : cornerStack) {
     P q;
     point_associate_to_map(T, p, q);
     int ci = cube_of(q.x, m.cenW), cj = cube_of(q.y, m.cenH), ck = cube_of(q.z, m.cenD);
-    if (ci >= 0 && ci < kW && cj >= 0 && cj < kH && ck >= 0 && ck < kDp)
+    if (ci >= 0 && ci < kW && cj >= 0 && cj < kH && ck >= 0 && ck < kDp) {
       m.corner[ci + kW * cj + kW * kH * ck].push_back(q);
+      m.inserted[0][ci + kW * cj + kW * kH * ck]++;
+    } else {
+      m.dropped[0]++;
+    }
   }
   for (const P& p : surfStack) {
     P q;
     point_associate_to_map(T, p, q);
     int ci = cube_of(q.x, m.cenW), cj = cube_of(q.y, m.cenH), ck = cube_of(q.z, m.cenD);
-    if (ci >= 0 && ci < kW && cj >= 0 && cj < kH && ck >= 0 && ck < kDp)
+    if (ci >= 0 && ci < kW && cj >= 0 && cj < kH && ck >= 0 && ck < kDp) {
       m.surf[ci + kW * cj + kW * kH * ck].push_back(q);
+      m.inserted[1][ci + kW * cj + kW * kH * ck]++;
+    } else {
+      m.dropped[1]++;
+    }
   }
   // :1018-1036 per valid cube re-downsampling
   std::vector<P> tmp;
@@ -1538,6 +1554,49 @@ int oracle_mapping_surround(void* h, loam_cloud_out* out, int* published) {
     return LOAM_OK;
   }
   return write_cloud(o->surround, out);
+}
+
+// The oracle's cube map and mapping pose state as loam_map_export hands out the engine's: each cloud
+// cube index ascending, the vector's order inside a cube; every pts NULL is the sizes-only query;
+// LOAM_E_CAPACITY writes no point and fills every count and offset.  inserted ([2][LOAM_MAP_CUBES],
+// corner then surf) and dropped ([2]) describe the last oracle_mapping frame's insertion
+// (src/laserMapping.cpp:980-1016): the stack points pushed into each cube before the
+// re-downsampling, and the stack points outside the grid.  Either may be NULL.
+int oracle_map_export(void* h, loam_map* out, int32_t* inserted, uint64_t* dropped) {
+  if (h == nullptr || out == nullptr) return LOAM_E_INVAL;
+  const MpState& m = static_cast<Oracle*>(h)->mp;
+  const std::vector<std::vector<P>>* arr[2] = {&m.corner, &m.surf};
+  loam_map_cloud* cl[2] = {&out->corner, &out->surf};
+  bool fits = true;
+  for (int kind = 0; kind < 2; ++kind) {
+    uint64_t n = 0;
+    for (int c = 0; c < kNum; ++c) {
+      if (cl[kind]->cube_offset) cl[kind]->cube_offset[c] = (uint32_t)n;
+      n += (*arr[kind])[c].size();
+    }
+    if (cl[kind]->cube_offset) cl[kind]->cube_offset[kNum] = (uint32_t)n;
+    cl[kind]->count = n;
+    if (cl[kind]->pts && n > cl[kind]->capacity) fits = false;
+  }
+  out->center[0] = m.cenW; out->center[1] = m.cenH; out->center[2] = m.cenD;
+  out->surround_phase = m.mapFrameCount;
+  from6(m.transformAftMapped, &out->aft);
+  from6(m.transformBefMapped, &out->bef);
+  if (inserted)
+    for (int kind = 0; kind < 2; ++kind)
+      std::memcpy(inserted + (size_t)kind * kNum, m.inserted[kind].data(), kNum * sizeof(int32_t));
+  if (dropped) { dropped[0] = m.dropped[0]; dropped[1] = m.dropped[1]; }
+  if (!fits) return LOAM_E_CAPACITY;
+  for (int kind = 0; kind < 2; ++kind) {
+    if (!cl[kind]->pts) continue;
+    P* dst = (P*)cl[kind]->pts;
+    for (int c = 0; c < kNum; ++c) {
+      const std::vector<P>& v = (*arr[kind])[c];
+      if (!v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(P));
+      dst += v.size();
+    }
+  }
+  return LOAM_OK;
 }
 
 // /imu/data: scanRegistration's imuHandler (:638-660) and laserMapping's (:323-335).

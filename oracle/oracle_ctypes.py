@@ -64,6 +64,21 @@ class Stats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+MAP_CUBES = 4851  # LOAM_MAP_CUBES
+
+
+class MapCloud(ctypes.Structure):
+    """include/loam/loam.h loam_map_cloud"""
+    _fields_ = [("pts", ctypes.c_void_p), ("capacity", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                ("cube_offset", ctypes.c_void_p)]
+
+
+class Map(ctypes.Structure):
+    """include/loam/loam.h loam_map"""
+    _fields_ = [("corner", MapCloud), ("surf", MapCloud), ("center", ctypes.c_int32 * 3),
+                ("surround_phase", ctypes.c_int32), ("aft", Pose6), ("bef", Pose6)]
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -88,6 +103,7 @@ def lib():
                                      ctypes.POINTER(Pose6), ctypes.POINTER(CloudOut)]
         L.oracle_mapping_surround.argtypes = [ctypes.c_void_p, ctypes.POINTER(CloudOut),
                                               ctypes.POINTER(ctypes.c_int)]
+        L.oracle_map_export.argtypes = [ctypes.c_void_p, ctypes.POINTER(Map), ctypes.c_void_p, ctypes.c_void_p]
         L.oracle_maintenance.argtypes = [ctypes.POINTER(Pose6)] * 4
         L.oracle_imu.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                  ctypes.POINTER(ctypes.c_double)]
@@ -218,6 +234,30 @@ class Oracle:
             rc = lib().oracle_mapping_surround(self.h, ctypes.byref(out.c), ctypes.byref(pub))
         assert rc == 0, rc
         return out.get() if pub.value else None
+
+    def map_export(self):
+        """the oracle's cube map and mapping pose state as Engine.map_export() returns the engine's
+        (corner / surf [N, 4] float32 in cube order, corner_offset / surf_offset [MAP_CUBES + 1]
+        uint32, center, surround_phase, aft, bef), and of the last mapping frame's insertion
+        (src/laserMapping.cpp:980-1016): inserted ([2, MAP_CUBES] int32: the stack points pushed
+        into each cube, corner then surf, before the re-downsampling) and dropped ([2]: the stack
+        points outside the grid).  The sizes-only call first, then one call with room."""
+        m = Map()
+        offs = [np.zeros(MAP_CUBES + 1, np.uint32) for _ in range(2)]
+        m.corner.cube_offset, m.surf.cube_offset = offs[0].ctypes.data, offs[1].ctypes.data
+        inserted = np.zeros((2, MAP_CUBES), np.int32)
+        dropped = np.zeros(2, np.uint64)
+        rc = lib().oracle_map_export(self.h, ctypes.byref(m), None, None)  # sizes only
+        assert rc == 0, rc
+        pts = [np.empty((int(c.count), 4), np.float32) for c in (m.corner, m.surf)]
+        for c, a in zip((m.corner, m.surf), pts):
+            c.pts, c.capacity = a.ctypes.data, a.shape[0]
+        rc = lib().oracle_map_export(self.h, ctypes.byref(m), inserted.ctypes.data, dropped.ctypes.data)
+        assert rc == 0, rc
+        return {"corner": pts[0], "surf": pts[1], "corner_offset": offs[0], "surf_offset": offs[1],
+                "center": np.array(m.center[:], np.int32), "surround_phase": int(m.surround_phase),
+                "aft": m.aft.arr(), "bef": m.bef.arr(), "inserted": inserted,
+                "dropped": (int(dropped[0]), int(dropped[1]))}
 
     def stats(self):
         s = Stats()
