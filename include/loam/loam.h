@@ -601,6 +601,59 @@ typedef struct {
  * next push (loam_lanes_map_export uses them the same way). */
 int loam_lanes_surround(loam_ctx *ctx, loam_lanes_cloud *out);
 
+/* ---- every topic cloud of the last pulled step, for a list of lanes in one call ----
+ * A loam_batch_cloud per topic, packed over the listed lanes: lane lane[i]'s points of a cloud are
+ * pts[offset[i] .. offset[i+1]) and offset[n] = count (offset has n + 1 entries here). */
+#define LOAM_LANE_CLOUDS 9
+typedef struct {
+  loam_batch_cloud full, sharp, less_sharp, flat, less_flat;   /* scanRegistration's five */
+  loam_batch_cloud corner_last, surf_last;                     /* laserCloudCornerLast / SurfLast */
+  loam_batch_cloud full_end;                                   /* /velodyne_cloud_3 */
+  loam_batch_cloud registered;                                 /* /velodyne_cloud_registered */
+} loam_lanes_clouds_out;
+
+/* Valid between a pull and the next push, in both lane modes; lane = NULL lists lanes 0 .. n - 1
+ * and needs n == n_lanes.  The protocol is loam_batch_features': a cloud whose pts and offset are
+ * both NULL is not wanted and its struct is left untouched; for every other cloud count and (when
+ * given) offset[0 .. n] are always filled, the points when pts is given; every pts NULL is the
+ * sizes-only query; LOAM_E_CAPACITY (a wanted cloud's points do not fit its capacity) writes no
+ * point, fills every wanted count / offset, and the call may be repeated.  The call changes nothing
+ * in any lane and may be repeated with the same bits.
+ * Contents, for a lane whose status on the last pulled step was LOAM_OK, bit for bit and in order:
+ *   full .. less_flat   what loam_scan_registration writes for the lane's sweep (de-skewed where the
+ *                       lane has IMU messages);
+ *   corner_last, surf_last   the lane's Last clouds as that frame left them, the clouds
+ *                       loam_lanes_score / loam_lanes_localize read: what loam_odometry writes on a
+ *                       frame with LOAM_PUB_CLOUDS, the raw lessSharp / lessFlat clouds on the lane's
+ *                       init frame; filled on frames that do not publish them too;
+ *   full_end            on a frame whose pull record has LOAM_PUB_FULL, as loam_odometry writes it;
+ *                       an empty range otherwise;
+ *   registered          when the pull reported mapped = 1: n_registered points, what
+ *                       loam_lanes_registered returns (0 for a LOAM_LOC_OFFGRID shared lane).
+ * Every cloud is an empty range, without an error, for a failed or retired lane, a lane on a wait
+ * step, a lane between loam_lanes_restart and the pull of its init step, every lane inside
+ * system_delay and before the first pull.  When every range is empty nothing is launched.
+ * LOAM_E_INVAL with out untouched: null ctx / out, lanes not open, a step in flight, n == 0 or
+ * n > n_lanes, lane == NULL with n != n_lanes, an index >= n_lanes, a lane listed twice, a wanted
+ * cloud of the list exceeding 2^32 - 1 points, or (the host form) a max_points so large that one
+ * lane's nine clouds at their strides (5 max_points + 276 n_rings points) exceed the download
+ * staging of 2^21 points.  That limit holds whichever clouds are wanted, for every call that gives a
+ * pts; the sizes-only query and the device form use no staging and have no such limit.
+ * LOAM_E_NOMEM when the first call's allocation fails, LOAM_E_HIP for a failed HIP call. */
+int loam_lanes_clouds(loam_ctx *ctx, uint32_t n, const uint32_t *lane /* [n] or NULL */, loam_lanes_clouds_out *out);
+/* The same with every pts in plain device memory of the context's device, 16-byte aligned, and
+ * capacity * 16 bytes inside its allocation (anything else: LOAM_E_INVAL, nothing written).  The
+ * points are packed straight into the caller's buffers: no staging, no device-to-host copy.  offset
+ * and count stay host-side and are filled before return (the call's one small synchronisation).
+ * consumer_stream (a hipStream_t) non-NULL: the stream is made to wait for the pack and the call
+ * returns without waiting; NULL: the call synchronises before it returns.  Same bits as the host form.
+ * The pack runs on the context's own stream and is ordered behind nothing of the caller's: whatever
+ * still reads or writes the destination buffers, on consumer_stream or any other stream, must have
+ * finished (or been synchronised with) before the call.  The lanes' own buffers need no such care: the
+ * next push starts on the same stream, behind the pack. */
+int loam_lanes_clouds_device(loam_ctx *ctx, uint32_t n, const uint32_t *lane, loam_lanes_clouds_out *out,
+                             void *consumer_stream);
+
 /* ---- shared lanes: every lane localizes in the context's one map, which a step only reads ----
  * Opens n_lanes lanes whose laserMapping refines against the context's streaming map (the store
  * loam_map_import / loam_mapping / loam_chain_sweep maintain), which a lanes step only reads.

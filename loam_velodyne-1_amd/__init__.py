@@ -198,6 +198,14 @@ class LanesCloud(ctypes.Structure):
                 ("offset", ctypes.c_void_p), ("published", ctypes.c_void_p)]
 
 
+LANE_CLOUDS = BATCH_CLOUDS + ("corner_last", "surf_last", "full_end", "registered")  # LOAM_LANE_CLOUDS, in order
+
+
+class LanesCloudsOut(ctypes.Structure):
+    """include/loam/loam.h loam_lanes_clouds_out: every topic cloud of the listed lanes, packed per topic"""
+    _fields_ = [(n, BatchCloud) for n in LANE_CLOUDS]
+
+
 EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_error", "loam_imu",
            "loam_scan_registration", "loam_odometry", "loam_mapping", "loam_mapping_surround",
            "loam_maintenance", "loam_chain_sweep",
@@ -207,6 +215,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_lanes_restart", "loam_lanes_map_import", "loam_lanes_surround",
            "loam_lanes_open_shared", "loam_lanes_set_pose", "loam_lanes_localize_info", "loam_lanes_score",
            "loam_lanes_localize", "loam_lanes_push_device", "loam_lanes_map_commit",
+           "loam_lanes_clouds", "loam_lanes_clouds_device",
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
@@ -277,6 +286,9 @@ def lib():
                                           P(LocalizeResult)]
         L.loam_lanes_push_device.argtypes = [PP, P(ctypes.c_double), P(CloudIn), ctypes.c_void_p, ctypes.c_uint32]
         L.loam_lanes_map_commit.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), P(CommitResult)]
+        L.loam_lanes_clouds.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), P(LanesCloudsOut)]
+        L.loam_lanes_clouds_device.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_uint32), P(LanesCloudsOut),
+                                               ctypes.c_void_p]
         L.loam_msg_from_pose.argtypes = [ctypes.c_int, ctypes.c_double, P(Pose6), P(Pose6), P(OdometryMsg), P(TfMsg)]
         L.loam_pose_from_msg.argtypes = [P(OdometryMsg), P(Pose6), P(Pose6)]
         _LIB = L
@@ -694,6 +706,62 @@ class Engine:
             rc = lib().loam_lanes_registered(self.h, int(lane), ctypes.byref(out.c))
         _check(rc)
         return out.get()
+
+    def _lanes_list(self, lanes):
+        """(n, the ctypes index array or None for every lane) of a lanes_clouds list"""
+        if lanes is None:
+            return self.n_lanes, None
+        lanes = [int(l) for l in np.atleast_1d(lanes)]
+        return len(lanes), (ctypes.c_uint32 * max(len(lanes), 1))(*lanes)
+
+    def lanes_clouds(self, lanes=None, clouds=None):
+        """the topic clouds of the last pulled step for the listed lanes (loam_lanes_clouds; lanes
+        None = every lane, clouds None = all nine of LANE_CLOUDS): {name: [an (n, 4) float32 array
+        per listed lane]}, an empty array where the lane's frame has no such cloud.  Valid until the
+        next lanes_push; the sizes-only call first, then one call with room."""
+        clouds = LANE_CLOUDS if clouds is None else tuple(clouds)
+        for c in clouds:
+            if c not in LANE_CLOUDS:
+                raise ValueError(f"unknown cloud {c!r}")
+        n, idx = self._lanes_list(lanes)
+        lc = LanesCloudsOut()
+        offs = {c: np.zeros(n + 1, np.uint32) for c in clouds}
+        for c in clouds:
+            getattr(lc, c).offset = offs[c].ctypes.data
+        if clouds:
+            _check(lib().loam_lanes_clouds(self.h, n, idx, ctypes.byref(lc)))  # sizes only
+        pts = {c: np.empty((int(getattr(lc, c).count), 4), np.float32) for c in clouds}
+        for c in clouds:
+            b = getattr(lc, c)
+            b.pts, b.capacity = pts[c].ctypes.data, pts[c].shape[0]
+        if any(p.shape[0] for p in pts.values()):
+            _check(lib().loam_lanes_clouds(self.h, n, idx, ctypes.byref(lc)))
+        return {c: [pts[c][offs[c][i]:offs[c][i + 1]].copy() for i in range(n)] for c in clouds}
+
+    def lanes_clouds_device(self, dst, lanes=None, stream=None):
+        """lanes_clouds into device memory (loam_lanes_clouds_device): dst = {name: an object with
+        __cuda_array_interface__ (a torch tensor on this GPU: float32, contiguous, 4 floats per point,
+        16-byte aligned)}; the points are packed straight into it.  stream: the consumer's HIP stream as
+        an integer handle: its later work waits for the pack and the call does not; None: the call
+        waits.  Earlier work that still uses the buffers must have finished before the call (the pack
+        waits for nothing of the caller's).  Returns {name: offsets [n + 1] uint32}: listed lane i's points of a cloud are rows
+        offsets[i] .. offsets[i + 1] of its buffer."""
+        n, idx = self._lanes_list(lanes)
+        lc = LanesCloudsOut()
+        offs = {}
+        for c, buf in dst.items():
+            if c not in LANE_CLOUDS:
+                raise ValueError(f"unknown cloud {c!r}")
+            cai = buf.__cuda_array_interface__
+            if np.dtype(cai["typestr"]) != np.dtype(np.float32) or cai.get("strides") is not None:
+                raise ValueError("a destination must be contiguous float32")
+            offs[c] = np.zeros(n + 1, np.uint32)
+            b = getattr(lc, c)
+            b.pts, b.capacity = int(cai["data"][0]) or None, int(np.prod(cai["shape"])) // 4
+            b.offset = offs[c].ctypes.data
+        _check(lib().loam_lanes_clouds_device(self.h, n, idx, ctypes.byref(lc),
+                                              ctypes.c_void_p(stream if stream is not None else 0)))
+        return offs
 
     def lanes_map_export(self, lane):
         """one lane's cube map and mapping pose state (loam_lanes_map_export): the dict map_export

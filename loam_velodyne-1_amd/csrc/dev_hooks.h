@@ -147,6 +147,23 @@ struct loam_ctx;
 int loam_dev_lanes_commit_input(struct loam_ctx* ctx, uint32_t lane, float* corner_out, float* surf_out,
                                 uint32_t* n_out /* [2] */, int32_t* valid_out /* [125] */, uint32_t* n_valid);
 
+/* loam_lanes_clouds' two kernels (lanes.hip k_lanes_pack_offsets / k_lanes_pack) on nine
+ * caller-made clouds of S lanes: cloud c has strides[c] points of room per lane at src[c] ([S][strides[c]][4]
+ * floats, host memory) and counts[c * S + l] points in lane l (any value: the kernel clamps it to [0,
+ * strides[c]]); mask [S]: bit c of mask[l] = cloud c of lane l counts; list [n]: the lanes to pack, in
+ * order.  table_out [9][n + 1]: the offsets kernel's table.  dst [dst_points][4] floats goes to the device
+ * as it is, cloud c's selection is packed behind cloud c - 1's from dst[0] on, and dst comes back: what
+ * lies behind the selection is as the caller left it.  LOAM_DEV_LANES_PACK_TILE is the pack kernel's
+ * tile in points.  LOAM_E_INVAL for bad arguments (S outside 1 .. LOAM_LANES_MAX, n outside 1 .. S, a
+ * stride outside 1 .. LOAM_DEV_LANES_PACK_MAX_STRIDE, an index >= S), LOAM_E_CAPACITY when dst_points is
+ * less than the selection (checked on the host, before anything is launched), LOAM_E_HIP without a GPU,
+ * LOAM_E_NOMEM. */
+#define LOAM_DEV_LANES_PACK_TILE 1024
+#define LOAM_DEV_LANES_PACK_MAX_STRIDE (1 << 22)
+int loam_dev_lanes_pack(int device, int32_t S, const int32_t* strides /* [9] */, const int32_t* counts /* [9][S] */,
+                        const int32_t* mask /* [S] */, const uint32_t* list /* [n] */, int32_t n,
+                        const float* const* src /* [9] */, float* dst, uint64_t dst_points, uint64_t* table_out);
+
 #ifdef __cplusplus
 }
 #endif

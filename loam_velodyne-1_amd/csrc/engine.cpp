@@ -3372,6 +3372,288 @@ extern "C" int loam_lanes_registered(loam_ctx* x, uint32_t lane, loam_cloud_out*
   return LOAM_OK;
 }
 
+// ------------------------------------------------------------------ loam_lanes_clouds
+namespace {
+// Which of the nine clouds lane l holds from the last pulled step (bit c: cloud c of
+// loam_lanes_clouds_out).  The host owns the lane states; the device's counts are stale where a bit
+// is clear: k_od_end leaves fullEnd / nfullEnd alone on frames that do not publish it and writes an
+// ordinary frame's into a lane whose own init frame the step was, and a failed lane's counts may
+// hold anything.
+int lanes_clouds_mask(const Lanes& L, int l) {
+  const LaneLife& f = L.life[l];
+  if (!L.pulled || !L.step_ran || L.fail[l] != LOAM_OK || f.wait >= 0 || f.kind == kLaneWaits) return 0;
+  int m = 0x7f;  // scanRegistration's five and the Last clouds: every frame of a live lane
+  if (f.kind == kLaneRuns && (L.step_pub & LOAM_PUB_FULL)) m |= 1 << 7;
+  if (f.kind == kLaneRuns && L.step_mapped && L.nreg[l] > 0) m |= 1 << 8;  // (a LOAM_LOC_OFFGRID lane registered nothing)
+  return m;
+}
+
+int lanes_clouds(loam_ctx* x, uint32_t n, const uint32_t* lane, loam_lanes_clouds_out* out, bool device,
+                 void* consumer_stream) {
+  static_assert(sizeof(loam_lanes_clouds_out) == LOAM_LANE_CLOUDS * 32 && LOAM_LANE_CLOUDS == kLaneClouds, "loam.h");
+  const std::string who = device ? "loam_lanes_clouds_device" : "loam_lanes_clouds";
+  if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
+  Lanes& L = x->lanes;
+  if (!L.S) return fail(LOAM_E_INVAL, who + ": lanes are not open");
+  if (L.in_flight) return fail(LOAM_E_INVAL, who + ": a step is in flight (loam_lanes_pull first)");
+  const int S = L.S;
+  if (n == 0 || n > (uint32_t)S) return fail(LOAM_E_INVAL, who + ": n must be in [1, n_lanes]");
+  if (!lane && n != (uint32_t)S) return fail(LOAM_E_INVAL, who + ": lane == NULL lists every lane: n must be n_lanes");
+  if (lane) {
+    std::vector<char> seen((size_t)S, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+      const std::string at = who + ": lane[" + std::to_string(i) + "] = " + std::to_string(lane[i]);
+      if (lane[i] >= (uint32_t)S) return fail(LOAM_E_INVAL, at + " is out of range");
+      if (seen[lane[i]]) return fail(LOAM_E_INVAL, at + " is listed twice");
+      seen[lane[i]] = 1;
+    }
+  }
+  loam_batch_cloud* cl[kLaneClouds] = {&out->full, &out->sharp, &out->less_sharp, &out->flat, &out->less_flat,
+                                       &out->corner_last, &out->surf_last, &out->full_end, &out->registered};
+  static const char* const kName[kLaneClouds] = {"full", "sharp", "less_sharp", "flat", "less_flat",
+                                                 "corner_last", "surf_last", "full_end", "registered"};
+  unsigned wanted = 0, with_pts = 0;
+  for (int c = 0; c < kLaneClouds; ++c) {
+    if (cl[c]->pts || cl[c]->offset) wanted |= 1u << c;
+    if (cl[c]->pts) with_pts |= 1u << c;
+  }
+  HIP_TRY(hipSetDevice(x->device));
+  if (device) {  // every destination as loam_lanes_push_device validates its sources
+    for (int c = 0; c < kLaneClouds; ++c) {
+      if (!(with_pts >> c & 1)) continue;
+      const uintptr_t p = (uintptr_t)cl[c]->pts;
+      LaneFeedIn q;
+      std::memset(&q, 0, sizeof(q));
+      lanes_feed_lookup(cl[c]->pts, x->device, q);
+      const std::string at = who + ": " + kName[c] + ".pts";
+      if (!q.on_device) return fail(LOAM_E_INVAL, at + " is not plain device memory of the context's device");
+      if (p & 15) return fail(LOAM_E_INVAL, at + " is not 16-byte aligned");
+      const uint64_t room = q.size - (uint64_t)(p - q.base);
+      if (cl[c]->capacity > room / sizeof(float4))
+        return fail(LOAM_E_INVAL, at + ": capacity x 16 bytes leaves the pointer's allocation");
+    }
+  } else {
+    const uint64_t lane_max = (uint64_t)pack_sweep_max(x) + L.od.capC + 2 * (uint64_t)L.od.capS + L.mp.capS;
+    if (with_pts && lane_max > kPackStagePts)
+      return fail(LOAM_E_INVAL, who + ": max_points is too large for the download staging (one lane's nine clouds "
+                                "must fit " + std::to_string(kPackStagePts) + " points)");
+  }
+  // the masks, on the host: when no wanted cloud of any listed lane is there, nothing is launched
+  std::vector<int> mask((size_t)S, 0);
+  unsigned any = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const int l = lane ? (int)lane[i] : (int)i;
+    mask[l] = lanes_clouds_mask(L, l);
+    any |= (unsigned)mask[l];
+  }
+  if (!(any & wanted)) {
+    for (int c = 0; c < kLaneClouds; ++c) {
+      if (!(wanted >> c & 1)) continue;
+      cl[c]->count = 0;
+      if (cl[c]->offset) std::fill(cl[c]->offset, cl[c]->offset + n + 1, 0u);
+    }
+    return LOAM_OK;
+  }
+  if (lanes_clouds_alloc(L) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LOAM_E_NOMEM, who + ": the mask / table block's allocation failed");
+  }
+  hipStream_t st = x->st;
+  std::copy(mask.begin(), mask.end(), L.cl_h);
+  for (uint32_t i = 0; i < n; ++i) L.cl_h[S + i] = lane ? (int)lane[i] : (int)i;
+  const int* mask_d = L.cl_d;
+  const int* list_d = L.cl_d + S;
+  const LanePackJob job = lanes_pack_job(L);
+  x->prof.begin(st);
+  HIP_TRY(hipMemcpyAsync(L.cl_d, L.cl_h, (size_t)2 * S * sizeof(int), hipMemcpyHostToDevice, st));
+  x->prof.mark("lanes_clouds_h2d");
+  HIP_TRY(lanes_pack_offsets(job, mask_d, list_d, (int)n, L.cl_tab_d, st));
+  x->prof.mark("k_lanes_pack_offsets");
+  const size_t row = (size_t)n + 1;
+  HIP_TRY(hipMemcpyAsync(L.cl_tab_h, L.cl_tab_d, kLaneClouds * row * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  x->prof.mark("lanes_clouds_table_d2h");
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t* T = L.cl_tab_h;  // T[c * row + j]
+  for (int c = 0; c < kLaneClouds; ++c)
+    if ((wanted >> c & 1) && T[c * row + n] > 0xffffffffull) {
+      x->prof.collect();
+      return fail(LOAM_E_INVAL, who + ": a cloud of this list has more points than a uint32_t offset holds; ask for fewer lanes");
+    }
+  bool fits = true;
+  unsigned pmask = 0;
+  for (int c = 0; c < kLaneClouds; ++c) {
+    if (!(wanted >> c & 1)) continue;
+    const uint64_t total = T[c * row + n];
+    cl[c]->count = total;
+    if (cl[c]->offset)
+      for (size_t j = 0; j < row; ++j) cl[c]->offset[j] = (uint32_t)T[c * row + j];
+    if (!cl[c]->pts) continue;
+    if (cl[c]->capacity < total) fits = false;
+    else if (total > 0) pmask |= 1u << c;
+  }
+  if (!fits) {
+    x->prof.collect();
+    return fail(LOAM_E_CAPACITY, who + ": a cloud's capacity is too small (count holds the required size)");
+  }
+  if (!pmask) {
+    x->prof.collect();
+    return LOAM_OK;
+  }
+  LanePackDst d;
+  if (device) {  // straight into the caller's buffers
+    for (int c = 0; c < kLaneClouds; ++c) {
+      d.dst[c] = (float4*)cl[c]->pts;
+      d.dbase[c] = 0;
+    }
+    hipStream_t cons = (hipStream_t)consumer_stream;
+    if (cons && !L.cl_done) HIP_TRY(hipEventCreateWithFlags(&L.cl_done, hipEventDisableTiming));
+    HIP_TRY(lanes_pack(job, L.cl_tab_d, list_d, (int)n, 0, (int)n, pmask, d, st));
+    x->prof.mark("k_lanes_pack");
+    if (cons) {  // the consumer's later work behind the pack; the marks are folded in by the next timeline
+      HIP_TRY(hipEventRecord(L.cl_done, st));
+      HIP_TRY(hipStreamWaitEvent(cons, L.cl_done, 0));
+      return LOAM_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    x->prof.collect();
+    return LOAM_OK;
+  }
+  std::vector<LaneCloudsChunk> chunks;
+  uint32_t bad = 0;
+  if (!lanes_clouds_plan(T, n, pmask, kPackStagePts, chunks, &bad)) {  // (cannot happen: lane_max above)
+    x->prof.collect();
+    return fail(LOAM_E_INVAL, who + ": a lane's clouds exceed the download staging");
+  }
+  if (const int rc = ensure_pack_stage(x, "lanes clouds download")) {
+    x->prof.collect();
+    return rc;
+  }
+  // chunk k: packed into device buffer k & 1 and DMA'd into pinned buffer k & 1; while the host
+  // copies chunk k into the caller's arrays, chunk k + 1 is packed and transferred (loam_batch_features)
+  auto enqueue = [&](size_t k) -> hipError_t {
+    const LaneCloudsChunk& ch = chunks[k];
+    const int i = (int)(k & 1);
+    for (int c = 0; c < kLaneClouds; ++c) {
+      d.dst[c] = x->pack_dev[i];
+      d.dbase[c] = (long long)ch.cbase[c] - (long long)T[c * row + ch.j0];
+    }
+    x->prof.mark("lanes_clouds_host_wait");
+    hipError_t e = lanes_pack(job, L.cl_tab_d, list_d, (int)n, (int)ch.j0, (int)(ch.j1 - ch.j0), pmask, d, st);
+    x->prof.mark("k_lanes_pack");
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(x->pack_pin[i], x->pack_dev[i], ch.pts * sizeof(float4), hipMemcpyDeviceToHost, st);
+    x->prof.mark("lanes_clouds_d2h");
+    if (e == hipSuccess) e = hipEventRecord(x->pack_done[i], st);
+    return e;
+  };
+  hipError_t he = hipSuccess;
+  for (size_t k = 0; k < chunks.size() && k < 2 && he == hipSuccess; ++k) he = enqueue(k);
+  for (size_t k = 0; k < chunks.size() && he == hipSuccess; ++k) {
+    const LaneCloudsChunk& ch = chunks[k];
+    he = hipEventSynchronize(x->pack_done[k & 1]);
+    if (he != hipSuccess) break;
+    for (int c = 0; c < kLaneClouds; ++c) {
+      if (!(pmask >> c & 1)) continue;
+      const uint64_t a = T[c * row + ch.j0], b = T[c * row + ch.j1];
+      if (b > a) copy_wide(cl[c]->pts + a, x->pack_pin[k & 1] + ch.cbase[c], (size_t)(b - a) * sizeof(float4));
+    }
+    if (k + 2 < chunks.size()) he = enqueue(k + 2);
+  }
+  if (he != hipSuccess) {  // (drain what was enqueued before reporting)
+    (void)hipStreamSynchronize(st);
+    return fail(LOAM_E_HIP, who + ": " + hipGetErrorString(he));
+  }
+  x->prof.collect();
+  return LOAM_OK;
+}
+}  // namespace
+
+extern "C" int loam_lanes_clouds(loam_ctx* x, uint32_t n, const uint32_t* lane, loam_lanes_clouds_out* out) {
+  return lanes_clouds(x, n, lane, out, false, nullptr);
+}
+
+extern "C" int loam_lanes_clouds_device(loam_ctx* x, uint32_t n, const uint32_t* lane, loam_lanes_clouds_out* out,
+                                        void* consumer_stream) {
+  return lanes_clouds(x, n, lane, out, true, consumer_stream);
+}
+
+// dev_hooks.h: the two pack kernels on caller-made clouds
+extern "C" int loam_dev_lanes_pack(int device, int32_t S, const int32_t* strides, const int32_t* counts, const int32_t* mask,
+                                   const uint32_t* list, int32_t n, const float* const* src, float* dst, uint64_t dst_points,
+                                   uint64_t* table_out) {
+  static_assert(LOAM_DEV_LANES_PACK_TILE == kLanePackTile, "dev_hooks.h");
+  const std::string who = "loam_dev_lanes_pack";
+  if (!strides || !counts || !mask || !list || !src || !dst || !table_out || S < 1 || S > LOAM_LANES_MAX || n < 1 || n > S)
+    return fail(LOAM_E_INVAL, who + ": bad argument");
+  size_t src_pts[kLaneClouds], all = 0;
+  for (int c = 0; c < kLaneClouds; ++c) {
+    if (!src[c] || strides[c] < 1 || strides[c] > LOAM_DEV_LANES_PACK_MAX_STRIDE) return fail(LOAM_E_INVAL, who + ": bad cloud");
+    src_pts[c] = (size_t)S * strides[c];
+    all += src_pts[c];
+  }
+  for (int32_t i = 0; i < n; ++i)
+    if (list[i] >= (uint32_t)S) return fail(LOAM_E_INVAL, who + ": a lane index is out of range");
+  // what the kernels will count, restated: the destination must hold it
+  uint64_t need = 0;
+  for (int c = 0; c < kLaneClouds; ++c)
+    for (int32_t i = 0; i < n; ++i)
+      if (mask[list[i]] >> c & 1) need += (uint64_t)std::min(std::max(counts[(size_t)c * S + list[i]], 0), strides[c]);
+  if (need > dst_points) return fail(LOAM_E_CAPACITY, who + ": dst is too small for the selection");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(LOAM_E_HIP, "no HIP device");  // (no CPU path)
+  if (device < 0 || device >= ndev) return fail(LOAM_E_INVAL, who + ": no such device");
+  HIP_TRY(hipSetDevice(device));
+  float4 *src_d = nullptr, *dst_d = nullptr;
+  int* ints_d = nullptr;  // counts [9][S], mask [S], list [n]
+  uint64_t* tab_d = nullptr;
+  const size_t nints = (size_t)kLaneClouds * S + S + n, tab = (size_t)kLaneClouds * (n + 1);
+  hipError_t e = hipMalloc((void**)&src_d, all * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc((void**)&dst_d, std::max<uint64_t>(dst_points, 1) * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc((void**)&ints_d, nints * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&tab_d, tab * sizeof(uint64_t));
+  const bool nomem = e != hipSuccess;
+  LanePackJob job;
+  LanePackDst d;
+  job.S = S;
+  size_t at = 0;
+  for (int c = 0; c < kLaneClouds && e == hipSuccess; ++c) {
+    e = hipMemcpy(src_d + at, src[c], src_pts[c] * sizeof(float4), hipMemcpyHostToDevice);
+    job.c[c] = {src_d + at, ints_d + (size_t)c * S, strides[c], 1};
+    at += src_pts[c];
+    d.dst[c] = dst_d;  // cloud c's selection behind cloud c - 1's (dbase below, from the table)
+    d.dbase[c] = 0;
+  }
+  if (e == hipSuccess) e = hipMemcpy(ints_d, counts, (size_t)kLaneClouds * S * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ints_d + (size_t)kLaneClouds * S, mask, (size_t)S * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ints_d + (size_t)kLaneClouds * S + S, list, (size_t)n * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dst_d, dst, dst_points * sizeof(float4), hipMemcpyHostToDevice);
+  const int* mask_d = ints_d + (size_t)kLaneClouds * S;
+  const int* list_d = mask_d + S;
+  if (e == hipSuccess) e = lanes_pack_offsets(job, mask_d, list_d, n, tab_d, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(table_out, tab_d, tab * sizeof(uint64_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) {
+    uint64_t run = 0, total = 0;
+    for (int c = 0; c < kLaneClouds; ++c) total += table_out[(size_t)c * (n + 1) + n];
+    if (total != need) {  // (the kernel and the restatement above disagree: nothing is packed)
+      e = hipErrorUnknown;
+    } else {
+      for (int c = 0; c < kLaneClouds; ++c) {
+        d.dbase[c] = (long long)run;
+        run += table_out[(size_t)c * (n + 1) + n];
+      }
+      e = lanes_pack(job, tab_d, list_d, n, 0, n, (1u << kLaneClouds) - 1, d, nullptr);
+    }
+  }
+  if (e == hipSuccess) e = hipMemcpy(dst, dst_d, dst_points * sizeof(float4), hipMemcpyDeviceToHost);
+  if (src_d) (void)hipFree(src_d);
+  if (dst_d) (void)hipFree(dst_d);
+  if (ints_d) (void)hipFree(ints_d);
+  if (tab_d) (void)hipFree(tab_d);
+  if (e == hipSuccess) return LOAM_OK;
+  (void)hipGetLastError();
+  return nomem ? fail(LOAM_E_NOMEM, who + ": allocation failed") : fail(LOAM_E_HIP, who + ": " + hipGetErrorString(e));
+}
+
 extern "C" int loam_lanes_map_export(loam_ctx* x, uint32_t lane, loam_map* out) {
   if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
   Lanes& L = x->lanes;

@@ -688,8 +688,168 @@ hipError_t lanes_imu_commit(Lanes& L, bool od_init, bool mapping, hipStream_t st
   return e;
 }
 
+// ---------------------------------------------------------------- loam_lanes_clouds
+namespace {
+constexpr int kLanePackOffThreads = 256;
+// One workgroup: for each of the nine clouds the exclusive prefix sums, over the n listed lanes, of
+// the lane's count where bit c of its mask word is set (else 0): table[c][j] = points of cloud c in
+// entries [0, j), j = 0 .. n.  The entries go through the block scan 256 at a time with the running
+// total carried in a register.  A count is clamped to its stride (a failed lane's may hold anything):
+// k_lanes_pack's reads stay inside the lane's slot.  An index outside [0, S) counts nothing.
+__global__ __launch_bounds__(kLanePackOffThreads) void k_lanes_pack_offsets(LanePackJob job, const int* mask,
+                                                                            const int* list, int n, uint64_t* table) {
+  __shared__ int scratch[kLanePackOffThreads / 64 + 1];
+  const int tid = threadIdx.x;
+  for (int c = 0; c < kLaneClouds; ++c) {
+    const LanePackSrc s = job.c[c];
+    uint64_t* row = table + (size_t)c * (n + 1);
+    uint64_t carry = 0;
+    for (int base = 0; base < n; base += kLanePackOffThreads) {
+      const int j = base + tid;
+      int m = 0;
+      if (j < n) {
+        const int l = list[j];
+        if (l >= 0 && l < job.S && (mask[l] >> c & 1)) m = min(max(s.count[(size_t)l * s.count_stride], 0), s.stride);
+      }
+      int total = 0;  // (<= 256 x 2^22 points: an int holds a block's sum)
+      const int excl = loamdev::block_excl_scan<kLanePackOffThreads>(m, scratch, total);
+      if (j < n) row[j] = carry + (uint64_t)excl;
+      carry += (uint64_t)total;
+    }
+    if (tid == 0) row[n] = carry;
+  }
+}
+
+constexpr int kLanePackThreads = 256, kLanePackPer = 4;
+static_assert(kLanePackTile == kLanePackThreads * kLanePackPer, "lanes.hpp");
+constexpr int kLanePackGridMax = 2048;  // 8 workgroups for each of the 256 CUs; the rest grid-strided
+struct LanePackOne {      // a wanted cloud: its slots, where point 0 of its selection goes, its table row
+  const float4* src;
+  float4* dst;
+  int stride, cloud;
+};
+struct LanePackSel {
+  LanePackOne w[kLaneClouds];  // the nc wanted clouds, in cloud order
+  int tile0[kLaneClouds + 1];  // the first tile of each among an entry's tiles (tile0[k] = the sum for k >= nc)
+  int n;                  // the table's entries (row length n + 1)
+  int j0, nj;             // this launch packs entries [j0, j0 + nj)
+  int nc, S;
+};
+// Work item = (entry, wanted cloud, kLanePackTile-point tile of the cloud's stride), k_sr_pack's shape:
+// the valid points of the tile from the lane's slot to their packed place, one float4 per thread per
+// access and four in flight.  A tile beyond the lane's count ends after two table reads.  Source
+// (slot base + t) and destination (packed offset + t) advance by one 16-byte point per thread: both
+// sides coalesced and 16-byte aligned.  The counts come from the table alone (clamped and masked by
+// k_lanes_pack_offsets).  (Measured against items that each take every 8th / 32nd tile of a cloud,
+// whose number does not grow with the strides, and against items read off the counts, the tiles of
+// each cloud's packed range with a search of the table per point: DESIGN.md §35; this shape was the
+// fastest.)
+__global__ __launch_bounds__(kLanePackThreads) void k_lanes_pack(LanePackSel sel, const uint64_t* table, const int* list) {
+  const uint32_t per_entry = (uint32_t)sel.tile0[kLaneClouds];
+  const uint32_t items = per_entry * (uint32_t)sel.nj;  // (< 2^31: lanes_pack)
+  for (uint32_t w = blockIdx.x; w < items; w += gridDim.x) {
+    const int j = sel.j0 + (int)(w / per_entry), r = (int)(w % per_entry);
+    int kk = 0;  // the last wanted cloud whose first tile is at or before r
+    while (kk + 1 < sel.nc && r >= sel.tile0[kk + 1]) ++kk;
+    const LanePackOne s = sel.w[kk];  // (a uniform index into the kernel arguments: scalar loads)
+    const int t0 = (r - sel.tile0[kk]) * kLanePackTile;
+    const uint64_t* row = table + (size_t)s.cloud * (sel.n + 1);
+    const uint64_t o = row[j];
+    const int m = (int)(row[j + 1] - o);
+    const int l = list[j];
+    if (t0 >= m || l < 0 || l >= sel.S) continue;
+    const float4* src = s.src + (size_t)l * s.stride;
+    float4* out = s.dst + o;
+    float4 v[kLanePackPer];
+#pragma unroll
+    for (int k = 0; k < kLanePackPer; ++k) {
+      const int t = t0 + k * kLanePackThreads + (int)threadIdx.x;
+      v[k] = t < m ? src[t] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+#pragma unroll
+    for (int k = 0; k < kLanePackPer; ++k) {
+      const int t = t0 + k * kLanePackThreads + (int)threadIdx.x;
+      if (t < m) out[t] = v[k];
+    }
+  }
+}
+}  // namespace
+
+hipError_t lanes_clouds_alloc(Lanes& L) {
+  if (L.cl_h) return hipSuccess;
+  const size_t tab = (size_t)kLaneClouds * (L.S + 1) * sizeof(uint64_t);
+  hipError_t e = hipHostMalloc((void**)&L.cl_h, (size_t)2 * L.S * sizeof(int), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&L.cl_d, (size_t)2 * L.S * sizeof(int));
+  if (e == hipSuccess) e = hipHostMalloc((void**)&L.cl_tab_h, tab, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&L.cl_tab_d, tab);
+  if (e != hipSuccess) {
+    if (L.cl_h) (void)hipHostFree(L.cl_h);
+    if (L.cl_d) (void)hipFree(L.cl_d);
+    if (L.cl_tab_h) (void)hipHostFree(L.cl_tab_h);
+    if (L.cl_tab_d) (void)hipFree(L.cl_tab_d);
+    L.cl_h = L.cl_d = nullptr;
+    L.cl_tab_h = L.cl_tab_d = nullptr;
+  }
+  return e;
+}
+
+LanePackJob lanes_pack_job(const Lanes& L) {
+  const SrBuffers& s = L.sr;
+  const OdBuffers& o = L.od;
+  const int buf = L.od_last;
+  LanePackJob j;
+  j.S = L.S;
+  j.c[0] = {s.full, s.n_full, s.cap, 1};
+  j.c[1] = {s.sharp, s.cnt + 0, kSharpPerRing * s.R, 4};
+  j.c[2] = {s.lsharp, s.cnt + 1, kLessSharpPerRing * s.R, 4};
+  j.c[3] = {s.flat, s.cnt + 2, kFlatPerRing * s.R, 4};
+  j.c[4] = {s.lflat, s.cnt + 3, s.cap, 4};
+  j.c[5] = {o.lastC + (size_t)buf * o.P * o.capC, o.nlast + buf * 2 + 0, o.capC, 2 * kOdBufs};
+  j.c[6] = {o.lastS + (size_t)buf * o.P * o.capS, o.nlast + buf * 2 + 1, o.capS, 2 * kOdBufs};
+  j.c[7] = {o.fullEnd + (size_t)buf * o.P * o.capS, o.nfullEnd + buf, o.capS, kOdBufs};
+  j.c[8] = {L.mp.reg, L.mp.nreg, L.mp.capS, 1};
+  return j;
+}
+
+hipError_t lanes_pack_offsets(const LanePackJob& job, const int* mask, const int* list, int n, uint64_t* table,
+                              hipStream_t st) {
+  if (n <= 0 || job.S <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_lanes_pack_offsets, dim3(1), dim3(kLanePackOffThreads), 0, st, job, mask, list, n, table);
+  return hipGetLastError();
+}
+
+hipError_t lanes_pack(const LanePackJob& job, const uint64_t* table, const int* list, int n, int j0, int nj,
+                      unsigned clouds, const LanePackDst& d, hipStream_t st) {
+  if (n <= 0 || j0 < 0 || nj <= 0 || j0 + nj > n || n > LOAM_LANES_MAX) return hipErrorInvalidValue;
+  LanePackSel sel;
+  std::memset(&sel, 0, sizeof(sel));
+  sel.n = n; sel.j0 = j0; sel.nj = nj; sel.S = job.S;
+  int tiles = 0;
+  for (int c = 0; c < kLaneClouds; ++c) {
+    if (!(clouds >> c & 1)) continue;
+    if (job.c[c].stride <= 0) return hipErrorInvalidValue;
+    sel.tile0[sel.nc] = tiles;
+    // (point 0 of the selection may lie in front of the buffer: the launch's first point is T[c][j0])
+    float4* dst0 = (float4*)((intptr_t)d.dst[c] + (intptr_t)d.dbase[c] * (intptr_t)sizeof(float4));
+    sel.w[sel.nc++] = {job.c[c].base, dst0, job.c[c].stride, c};
+    tiles += (job.c[c].stride + kLanePackTile - 1) / kLanePackTile;
+  }
+  if (sel.nc == 0) return hipSuccess;
+  for (int k = sel.nc; k <= kLaneClouds; ++k) sel.tile0[k] = tiles;
+  const long long items = (long long)tiles * nj;
+  if (items > 0x7fffffffLL) return hipErrorInvalidValue;  // (the kernel counts its work items in 32 bits)
+  hipLaunchKernelGGL(k_lanes_pack, dim3((unsigned)std::min<long long>(items, kLanePackGridMax)), dim3(kLanePackThreads), 0, st,
+                     sel, table, list);
+  return hipGetLastError();
+}
+
 void lanes_free(Lanes& L) {
   lanes_imu_free(L);
+  if (L.cl_h) (void)hipHostFree(L.cl_h);
+  if (L.cl_d) (void)hipFree(L.cl_d);
+  if (L.cl_tab_h) (void)hipHostFree(L.cl_tab_h);
+  if (L.cl_tab_d) (void)hipFree(L.cl_tab_d);
+  if (L.cl_done) (void)hipEventDestroy(L.cl_done);
   sr_free(L.sr);
   od_free(L.od);
   mp_free(L.mp);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "lanes_clouds_plan.hpp"
 #include "lanes_feed_plan.hpp"
 #include "mp.hpp"
 #include "od.hpp"
@@ -112,6 +113,14 @@ struct Lanes {
   // lanes' last pulled frames are in the map already (cleared by every pull)
   MpCommit cm;
   std::vector<char> committed;  // [S]
+  // loam_lanes_clouds, allocated by the first call: the lanes' validity masks (bit c:
+  // cloud c of the lane is there) and the lane list up, the offsets table down, and the event a
+  // consumer's stream waits for (created by the first call that is given one)
+  int* cl_h = nullptr;            // pinned [2S]: masks by lane, then the list
+  int* cl_d = nullptr;            // device [2S]
+  uint64_t* cl_tab_h = nullptr;   // pinned [kLaneClouds][S + 1]
+  uint64_t* cl_tab_d = nullptr;   // device [kLaneClouds][S + 1]
+  hipEvent_t cl_done = nullptr;
   // the protocol: a step pushed and not yet pulled; what that step published; whether the last
   // pulled step left registered clouds
   bool in_flight = false, step_ran = false, have_reg = false;
@@ -252,6 +261,36 @@ hipError_t lanes_surround_run(Lanes& L, int n, bool pack, hipStream_t st, Prof* 
 inline int lanes_surround_count(const Lanes& L, int lane) {
   return std::min(std::max(L.su_h[L.S + lane], 0), L.mp.map_cap);
 }
+
+
+// ---- loam_lanes_clouds: the lanes' clouds packed back to back over a list of lanes
+// cloud c of lane l: count[l * count_stride] points (clamped to [0, stride]) from base + l * stride
+struct LanePackSrc {
+  const float4* base;
+  const int* count;
+  int stride, count_stride;
+};
+struct LanePackJob {
+  LanePackSrc c[kLaneClouds];
+  int S;
+};
+// where a launch puts cloud c: point k of its selection over the list at dst[c][dbase[c] + k]
+struct LanePackDst {
+  float4* dst[kLaneClouds];
+  long long dbase[kLaneClouds];
+};
+constexpr int kLanePackTile = 1024;  // points a workgroup moves per pass (dev_hooks.h LOAM_DEV_LANES_PACK_TILE)
+// the masks / list block, the table and its pinned copy (the first loam_lanes_clouds)
+hipError_t lanes_clouds_alloc(Lanes& L);
+// the nine clouds of the last step where they lie: L.sr, the odometry's buffer L.od_last, mp.reg
+LanePackJob lanes_pack_job(const Lanes& L);
+// k_lanes_pack_offsets: table [kLaneClouds][n + 1] (device), table[c][j] = points of cloud c in list
+// entries [0, j), an entry counting where bit c of mask[list[j]] is set.  mask [job.S], list [n]: device.
+hipError_t lanes_pack_offsets(const LanePackJob& job, const int* mask, const int* list, int n, uint64_t* table,
+                              hipStream_t st);
+// k_lanes_pack: entries [j0, j0 + nj) of that table, the clouds in the bit mask `clouds`
+hipError_t lanes_pack(const LanePackJob& job, const uint64_t* table, const int* list, int n, int j0, int nj,
+                      unsigned clouds, const LanePackDst& d, hipStream_t st);
 
 }  // namespace loam
 #endif

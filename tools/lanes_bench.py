@@ -107,7 +107,17 @@ lanes hand out no feature clouds, so the cost of S downloads is reported from lo
 Also: hipMemGetInfo around the first commit against the derived working set, the map's size after
 every commit, and the mapping steps' wall time with commits against one more run without.
 --profile-s S: one more fleet at that S with every timed commit under loam_set_profiling (device ms per
-stage, summed over the commits)."""
+stage, summed over the commits).
+
+--clouds (instead of the above): S own-store lanes over 33 sweeps (15 mapping steps: a
+warm-up of four, eleven timed).  Behind every mapping step, each call into room made beforehand: --pairs
+times alternating the yardstick (the parent's only way: S loam_lanes_registered calls) and one
+loam_lanes_clouds of the registered cloud alone; then one loam_lanes_clouds of all nine clouds and one
+loam_lanes_clouds_device of all nine (no consumer stream: the call waits).  Wall ms of each, median and
+range over the timed steps; GB/s of the nine clouds' packed bytes beside hipMemcpy device-to-host of one
+pinned 32 MiB block in the same process; the last timed step once more under loam_set_profiling (device
+ms per stage; the device form's traffic = read + written bytes over k_lanes_pack's time).  One process
+per row: --s 64, --s 1024."""
 import argparse
 import importlib
 import json
@@ -981,6 +991,145 @@ def run_localize(S, k, streams, name, M, from_cap, pairs=3, reps=5):
     return line
 
 
+def _d2h_ceiling_gbs(nbytes=32 << 20, reps=5, warm=2):
+    """hipMemcpy device-to-host of one pinned block of nbytes: GB/s, median of reps"""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    hip.hipMemcpy.argtypes = [vp, vp, sz, ctypes.c_int]
+    hip.hipHostMalloc.argtypes = [ctypes.POINTER(vp), sz, ctypes.c_uint]
+    hip.hipMalloc.argtypes = [ctypes.POINTER(vp), sz]
+    hip.hipMemset.argtypes = [vp, ctypes.c_int, sz]
+    hip.hipFree.argtypes = [vp]
+    hip.hipHostFree.argtypes = [vp]
+    d, h = vp(), vp()
+    if hip.hipMalloc(ctypes.byref(d), nbytes) or hip.hipHostMalloc(ctypes.byref(h), nbytes, 0) or hip.hipMemset(d, 1, nbytes):
+        raise RuntimeError("HIP allocation failed")
+    ts = []
+    for r in range(warm + reps):
+        t0 = time.perf_counter()
+        if hip.hipMemcpy(h, d, nbytes, 2):
+            raise RuntimeError("hipMemcpy failed")
+        if r >= warm:
+            ts.append(time.perf_counter() - t0)
+    hip.hipFree(d)
+    hip.hipHostFree(h)
+    return round(nbytes / sorted(ts)[len(ts) // 2] / 1e9, 2)
+
+
+def run_clouds(S, streams, K, map_cap, pairs=3, measured=11):
+    """one JSON line: see --clouds in the module text"""
+    import ctypes
+    L = loam.lib()
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+    hip.hipFree.argtypes = [ctypes.c_void_p]
+    eng = loam.Engine(loam.default_config(system_delay=1))
+    eng.lanes_open(S, map_cap)
+    yard = [[] for _ in range(pairs)]
+    one = [[] for _ in range(pairs)]
+    nine, dev, nine_bytes, reg_bytes = [], [], [], []
+    host = {c: np.empty((0, 4), np.float32) for c in loam.LANE_CLOUDS}
+    dbuf = {c: [None, 0] for c in loam.LANE_CLOUDS}  # device pointer, points
+    offs = {c: np.zeros(S + 1, np.uint32) for c in loam.LANE_CLOUDS}
+    prof, n_map = None, 0
+
+    def sizes():
+        o = loam.LanesCloudsOut()
+        for c in loam.LANE_CLOUDS:
+            getattr(o, c).offset = offs[c].ctypes.data
+        loam._check(L.loam_lanes_clouds(eng.h, S, None, ctypes.byref(o)))
+        return {c: int(getattr(o, c).count) for c in loam.LANE_CLOUDS}
+
+    def call_host(clouds):
+        o = loam.LanesCloudsOut()
+        for c in clouds:
+            b = getattr(o, c)
+            b.pts, b.capacity, b.offset = host[c].ctypes.data, host[c].shape[0], offs[c].ctypes.data
+        t0 = time.perf_counter()
+        rc = L.loam_lanes_clouds(eng.h, S, None, ctypes.byref(o))
+        dt = (time.perf_counter() - t0) * 1e3
+        loam._check(rc)
+        return dt
+
+    def call_dev():
+        o = loam.LanesCloudsOut()
+        for c in loam.LANE_CLOUDS:
+            b = getattr(o, c)
+            b.pts, b.capacity, b.offset = dbuf[c][0], dbuf[c][1], offs[c].ctypes.data
+        t0 = time.perf_counter()
+        rc = L.loam_lanes_clouds_device(eng.h, S, None, ctypes.byref(o), None)
+        dt = (time.perf_counter() - t0) * 1e3
+        loam._check(rc)
+        return dt
+
+    for k in range(K):
+        o = eng.lanes_step([streams[l % N_STREAMS][k] for l in range(S)], stamp=0.1 * k)
+        if k >= 2 and not np.all(o["status"] == 0):
+            raise RuntimeError(f"step {k}: lane status {np.unique(o['status'])}")
+        if not o["mapped"][0]:
+            continue
+        n_map += 1
+        if n_map > WARM + measured:
+            continue
+        # room for this step's clouds, outside the timed calls
+        need = sizes()
+        for c, n in need.items():
+            if host[c].shape[0] < n:
+                host[c] = np.empty((n + n // 8, 4), np.float32)
+                host[c][:] = 0  # (touched: no page faults inside the timed copy)
+            if dbuf[c][1] < n:
+                if dbuf[c][0]:
+                    hip.hipFree(dbuf[c][0])
+                p = ctypes.c_void_p()
+                if hip.hipMalloc(ctypes.byref(p), (n + n // 8) * 16) != 0:
+                    raise RuntimeError("hipMalloc failed")
+                dbuf[c] = [p.value, n + n // 8]
+        # the parent's way: S loam_lanes_registered calls, each into its own room
+        nreg = o["n_registered"].astype(np.int64)
+        start = np.concatenate([[0], np.cumsum(nreg)])
+        outs = [loam.CloudOut(host["registered"].ctypes.data + int(start[l]) * 16, 0, int(nreg[l])) for l in range(S)]
+        ty, ta = [], []
+        for p in range(pairs):
+            t0 = time.perf_counter()
+            for l in range(S):
+                rc = L.loam_lanes_registered(eng.h, l, ctypes.byref(outs[l]))
+                if rc:
+                    loam._check(rc)
+            ty.append((time.perf_counter() - t0) * 1e3)
+            ta.append(call_host(("registered",)))
+        tb = call_host(loam.LANE_CLOUDS)
+        tc = call_dev()
+        if n_map == WARM + measured:  # the last timed step once more under profiling (not timed)
+            prof = dict(host_all=_profiled(eng, lambda: call_host(loam.LANE_CLOUDS)), device_all=_profiled(eng, call_dev))
+        if n_map > WARM:
+            for p in range(pairs):
+                yard[p].append(ty[p])
+                one[p].append(ta[p])
+            nine.append(tb)
+            dev.append(tc)
+            nine_bytes.append(sum(need.values()) * 16)
+            reg_bytes.append(need["registered"] * 16)
+    for c in dbuf:
+        if dbuf[c][0]:
+            hip.hipFree(dbuf[c][0])
+    eng.lanes_close()
+    eng.close()
+    nb = float(np.median(nine_bytes))
+    line = dict(clouds_S=S, sweeps=K, mapping_steps_timed=len(nine), warm_up=WARM,
+                yardstick_registered_calls_ms=[spread(t) for t in yard], registered_one_call_ms=[spread(t) for t in one],
+                registered_bytes=int(np.median(reg_bytes)), all_nine_host_ms=spread(nine), all_nine_bytes=int(nb),
+                all_nine_host_gbs=round(nb / spread(nine)["median"] / 1e6, 2),
+                d2h_pinned_32mib_gbs=_d2h_ceiling_gbs(), all_nine_device_wall_ms=spread(dev), profiled_device_ms=prof)
+    line["one_call_below_yardstick_every_pair"] = all(a["max"] < y["min"] for a, y in zip(line["registered_one_call_ms"],
+                                                                                        line["yardstick_registered_calls_ms"]))
+    if prof and prof["device_all"].get("k_lanes_pack"):
+        ms = prof["device_all"]["k_lanes_pack"]
+        line["all_nine_device_pack_ms"] = ms
+        line["all_nine_device_traffic_gbs"] = round(2 * nb / ms / 1e6, 1)  # read + written
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--s", default="1,16,64")
@@ -1005,10 +1154,11 @@ def main():
     ap.add_argument("--feed", default="host", choices=("host", "device"),
                     help="device: steps fed from host and from device memory (lanes_push_device), alternating")
     ap.add_argument("--pairs", type=int, default=3, help="--feed device: alternating runs of each feed")
+    ap.add_argument("--clouds", action="store_true", help="loam_lanes_clouds against S loam_lanes_registered calls")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     a.shared = a.shared or a.score or a.localize or a.commit
-    K = 40 if a.occupancy else 23 if a.surround else a.sweeps
+    K = 40 if a.occupancy else 23 if a.surround else 2 + 2 * (WARM + 11) + 1 if a.clouds else a.sweeps
     streams = [sg.stream_sweeps(K, 1 + i) for i in range(N_STREAMS)]
     imu = imu_schedules(K) if a.imu else None
     pts = int(np.mean([sw.shape[0] for sw in streams[0]]))
@@ -1025,6 +1175,10 @@ def main():
 
     if a.occupancy:
         emit(run_occupancy(a.occupancy, streams, a.map_cap))
+        return
+    if a.clouds:
+        for S in [int(v) for v in a.s.split(",") if v]:
+            emit(run_clouds(S, streams, K, a.map_cap, pairs=a.pairs))
         return
     if a.shared:
         e = loam.Engine(loam.default_config(system_delay=1))
