@@ -509,14 +509,17 @@ LOAM_D uint64_t shfl_xor_u64(uint64_t v, int m) {
   const int lo = __shfl_xor((int)(uint32_t)v, m, 64), hi = __shfl_xor((int)(uint32_t)(v >> 32), m, 64);
   return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
 }
-template <int E, int S>
-LOAM_D void reg_cmpx_intra(uint64_t (&v)[E], int base, int size) {
+// (the sorts below take 64-bit keys or, at half the exchange traffic, 32-bit ones)
+LOAM_D uint64_t shfl_xor_key(uint64_t v, int m) { return shfl_xor_u64(v, m); }
+LOAM_D uint32_t shfl_xor_key(uint32_t v, int m) { return (uint32_t)__shfl_xor((int)v, m, 64); }
+template <int E, int S, typename K>
+LOAM_D void reg_cmpx_intra(K (&v)[E], int base, int size) {
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     if constexpr (S < E) {
       if ((e & S) == 0) {
         const bool up = ((base + e) & size) == 0;
-        const uint64_t a = v[e], b = v[e + S];
+        const K a = v[e], b = v[e + S];
         const bool sw = (a > b) == up;
         v[e] = sw ? b : a;
         v[e + S] = sw ? a : b;
@@ -525,32 +528,32 @@ LOAM_D void reg_cmpx_intra(uint64_t (&v)[E], int base, int size) {
   }
 }
 // WAVE: one wave sorts alone (NT = 64; every stride stays inside the wave, no workgroup barrier)
-template <int NT, int E, bool WAVE = false>
-LOAM_D void reg_bitonic_sort_n(uint64_t* k, int n) {
+template <int NT, int E, bool WAVE = false, typename K = uint64_t>
+LOAM_D void reg_bitonic_sort_n(K* k, int n) {
   static_assert(!WAVE || NT == 64, "a wave sort has 64 lanes");
   const int lane = __lane_id(), tid = WAVE ? lane : (int)threadIdx.x, base = tid * E;
   constexpr int N = NT * E;
-  uint64_t v[E];
+  K v[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const int g = e * NT + tid;
-    v[e] = g < n ? k[g] : ~0ull;
+    v[e] = g < n ? k[g] : (K)~(K)0;
   }
   if (!WAVE) __syncthreads();  // k becomes scratch
   for (int size = 2; size <= N; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
       if (stride < E) {
-        if (stride == 1) reg_cmpx_intra<E, 1>(v, base, size);
-        else if (stride == 2) reg_cmpx_intra<E, 2>(v, base, size);
-        else if (stride == 4) reg_cmpx_intra<E, 4>(v, base, size);
-        else reg_cmpx_intra<E, 8>(v, base, size);
+        if (stride == 1) reg_cmpx_intra<E, 1, K>(v, base, size);
+        else if (stride == 2) reg_cmpx_intra<E, 2, K>(v, base, size);
+        else if (stride == 4) reg_cmpx_intra<E, 4, K>(v, base, size);
+        else reg_cmpx_intra<E, 8, K>(v, base, size);
       } else if (stride < 64 * E) {
         const int m = stride / E;
         const bool lower = (lane & m) == 0;
 #pragma unroll
         for (int e = 0; e < E; ++e) {
           const bool up = ((base + e) & size) == 0;
-          const uint64_t o = shfl_xor_u64(v[e], m);
+          const K o = shfl_xor_key(v[e], m);
           const bool keep_min = lower == up;
           v[e] = keep_min ? (o < v[e] ? o : v[e]) : (o > v[e] ? o : v[e]);
         }
@@ -563,7 +566,7 @@ LOAM_D void reg_bitonic_sort_n(uint64_t* k, int n) {
 #pragma unroll
         for (int e = 0; e < E; ++e) {
           const bool up = ((base + e) & size) == 0;
-          const uint64_t o = k[e * NT + (tid ^ m)];
+          const K o = k[e * NT + (tid ^ m)];
           const bool keep_min = lower == up;
           v[e] = keep_min ? (o < v[e] ? o : v[e]) : (o > v[e] ? o : v[e]);
         }
@@ -590,13 +593,13 @@ LOAM_D void wave_sort_u64(uint64_t* k, int n) {
   else reg_bitonic_sort_n<64, 8, true>(k, n);
 }
 // n: power of two <= NT * EMAX (EMAX a power of two <= 16)
-template <int NT, int EMAX>
-LOAM_D void reg_bitonic_sort(uint64_t* k, int n) {
-  if (n <= NT || EMAX == 1) reg_bitonic_sort_n<NT, 1>(k, n);
-  else if (n <= 2 * NT || EMAX == 2) reg_bitonic_sort_n<NT, (EMAX < 2 ? EMAX : 2)>(k, n);
-  else if (n <= 4 * NT || EMAX == 4) reg_bitonic_sort_n<NT, (EMAX < 4 ? EMAX : 4)>(k, n);
-  else if (n <= 8 * NT || EMAX == 8) reg_bitonic_sort_n<NT, (EMAX < 8 ? EMAX : 8)>(k, n);
-  else reg_bitonic_sort_n<NT, (EMAX < 16 ? EMAX : 16)>(k, n);
+template <int NT, int EMAX, typename K>
+LOAM_D void reg_bitonic_sort(K* k, int n) {
+  if (n <= NT || EMAX == 1) reg_bitonic_sort_n<NT, 1, false, K>(k, n);
+  else if (n <= 2 * NT || EMAX == 2) reg_bitonic_sort_n<NT, (EMAX < 2 ? EMAX : 2), false, K>(k, n);
+  else if (n <= 4 * NT || EMAX == 4) reg_bitonic_sort_n<NT, (EMAX < 4 ? EMAX : 4), false, K>(k, n);
+  else if (n <= 8 * NT || EMAX == 8) reg_bitonic_sort_n<NT, (EMAX < 8 ? EMAX : 8), false, K>(k, n);
+  else reg_bitonic_sort_n<NT, (EMAX < 16 ? EMAX : 16), false, K>(k, n);
 }
 
 // ------------------------------------------------------------------ block radix sort (stable)

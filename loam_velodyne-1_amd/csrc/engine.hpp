@@ -152,6 +152,8 @@ struct SrBuffers {
   int* tileF = nullptr;      // [S][ntiles] first halfPassed flip index of each tile (tile-parallel ring sort)
   int* ring_sync = nullptr;  // the fused ring sort's tile ticket
   float* sweep_ori = nullptr;  // [S][2] startOri, endOri
+  int4* sweep_ends = nullptr;  // [S] the fused ring sort's sweep ends, found once per sweep by k_sr_ring_prep:
+                               // (last finite point or -1, startOri bits, raw end orientation bits, -)
   float4* full = nullptr;    // ring-sorted cloud (camera frame, intensity = ring + 0.1 relTime)
   int* n_full = nullptr;
   float* curv = nullptr;

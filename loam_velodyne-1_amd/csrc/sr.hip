@@ -40,8 +40,13 @@ namespace loam {
 // phase, summed over the workgroups: [0] workgroups, [1] ticket, [2] raw loads issued + the sweep-end
 // scans and orientations, [3] ring ID + orientation + counts, [4] publish + ballot ranks, [5] slot
 // prefix + the wait for the sweep's other tiles, [6] ring bases, [7] scatter issued.
+// The same for k_sr_ringvg (g_vg_ph), per workgroup that downsamples a ring with candidates:
+// [0] workgroups, [1] candidate copy + gather + bounding box, [2] voxel keys + run heads + run
+// lengths, [3] sort, [4] voxel heads, [5] member means; [6] workgroups that sorted 32-bit keys,
+// [7] runs sorted (a count, not a time).
 #ifdef LOAM_SR_PHASES
 __device__ unsigned long long g_sr_ph[8];
+__device__ unsigned long long g_vg_ph[8];
 #define SR_PH(k)                                                                  \
   do {                                                                            \
     if (threadIdx.x == 0) {                                                       \
@@ -50,8 +55,12 @@ __device__ unsigned long long g_sr_ph[8];
       ph_last = now;                                                              \
     }                                                                             \
   } while (0)
+#define SR_PH_PARAM , unsigned long long ph0 = 0
+#define SR_PH_ARG(x) , x
 #else
 #define SR_PH(k) ((void)0)
+#define SR_PH_PARAM
+#define SR_PH_ARG(x)
 #endif
 
 namespace {
@@ -677,12 +686,67 @@ constexpr bool kSrRingFused = LOAM_SR_RING_FUSED;
 // ... for launches of at least this many sweeps (its three presets are launches of their own: a
 // one-sweep chain keeps the two-kernel form)
 constexpr int kSrRingFusedMin = 64;
+// A sweep's ends once per sweep instead of once per tile (LOAM_SR_ENDS_ONCE, 0: every tile of
+// k_sr_ring_fused scans them itself, for A/B builds): k_sr_ring_prep, one workgroup of two waves
+// per sweep in front of every k_sr_ring_fused launch (raw is rewritten between steps), finds
+// :230-238's first and last finite point as the tiles did (waves 0 / 1 scan from either end, the
+// lane that holds the point hands its coordinates over, -atan2 on lane 0: the same instructions
+// on the same values) and leaves (last or -1, startOri, raw end orientation) in sweep_ends[s],
+// which a tile loads together with raw_n[s].  It also does the launch's presets, which were three
+// memsets: the sweep's tilecnt / tileF rows to -1 and the ticket to 0.
+#ifndef LOAM_SR_ENDS_ONCE
+#define LOAM_SR_ENDS_ONCE 1
+#endif
+constexpr int kPrepThreads = 128;
+__global__ __launch_bounds__(kPrepThreads) void k_sr_ring_prep(SrBuffers b, int R, int rtiles) {
+  const int s = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  const int n = b.raw_n[s];
+  const float4* raw = b.raw + (size_t)s * b.cap;
+  __shared__ int sh_last;
+  __shared__ float sh_start, sh_end_raw;
+  if (tid == 0) { sh_last = -1; sh_start = 0.0f; sh_end_raw = 0.0f; }
+  int* tc = b.tilecnt + (size_t)s * rtiles * R;
+  for (int k = tid; k < rtiles * R; k += kPrepThreads) tc[k] = -1;
+  for (int k = tid; k < rtiles; k += kPrepThreads) b.tileF[(size_t)s * rtiles + k] = -1;
+  if (s == 0 && tid == 0) b.ring_sync[0] = 0;
+  __syncthreads();
+  if (LOAM_SR_ENDS_ONCE) {
+    int f = -1;
+    float4 v = make_float4(0, 0, 0, 0);
+    for (int k = 0; k < n; k += 64) {
+      const int i = w == 0 ? k + lane : n - 1 - k - lane;
+      const bool in = w == 0 ? i < n : i >= 0;
+      v = in ? raw[i] : make_float4(0, 0, 0, 0);
+      const uint64_t m = __ballot(in && finite3(v));
+      if (m) {
+        const int src = __ffsll((unsigned long long)m) - 1;
+        f = w == 0 ? k + src : n - 1 - k - src;
+        v.x = __shfl(v.x, src, 64);
+        v.y = __shfl(v.y, src, 64);
+        break;
+      }
+    }
+    if (lane == 0) {
+      if (w == 0) {
+        sh_start = f >= 0 ? -atan2f_fdlibm(v.y, v.x) : 0.0f;
+      } else {
+        sh_last = f;
+        if (f >= 0) sh_end_raw = -atan2f_fdlibm(v.y, v.x);
+      }
+    }
+    __syncthreads();
+    if (tid == 0) b.sweep_ends[s] = make_int4(sh_last, __float_as_int(sh_start), __float_as_int(sh_end_raw), 0);
+  }
+}
 __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrParams p, int rtiles) {
   constexpr int kW = kSrThreads / 64, kSlots = kRingE * kW;
   static_assert(kSlots <= 64 && (kSlots & (kSlots - 1)) == 0, "slot scan width");
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
-  __shared__ int sh_ticket, sh_last, sh_F;
+  __shared__ int sh_ticket, sh_F;
+#if !LOAM_SR_ENDS_ONCE
+  __shared__ int sh_last;
   __shared__ float sh_start, sh_end_raw;
+#endif
   __shared__ int sh_cnt[64], sh_tot[64], sh_pre[64], sh_base[64];
   __shared__ int sh_wcnt[64][kSlots];
 #ifdef LOAM_SR_PHASES
@@ -691,8 +755,31 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
   if (tid == 0) sh_ticket = atomicAdd(&b.ring_sync[0], 1);
   __syncthreads();
   SR_PH(1);
-  const int s = sh_ticket / rtiles, t = sh_ticket % rtiles;
+#if LOAM_SR_ENDS_ONCE
+  const int ticket = __builtin_amdgcn_readfirstlane(sh_ticket);  // (uniform: s, t and the row addresses stay scalar)
+#else
+  const int ticket = sh_ticket;
+#endif
+  const int s = ticket / rtiles, t = ticket % rtiles;
+  const float4* raw = b.raw + (size_t)s * b.cap;
+#if LOAM_SR_ENDS_ONCE
+  // The tile's points, the sweep's ends and raw_n in one round trip: the point loads do not wait
+  // for raw_n.  t < rtiles = ceil(cap / kRingTile), so a tile may reach past cap (and, in the last
+  // sweep, past the allocation): the loads are masked by i < cap, which keeps them inside the
+  // sweep's own row of raw, and points at or beyond n (stale rows of an earlier upload) are
+  // dropped by the i < n tests below.
+  const int n = b.raw_n[s];
+  const int4 ends = b.sweep_ends[s];
+  float4 q[kRingE];
+#pragma unroll
+  for (int e = 0; e < kRingE; ++e) {
+    const int i = t * kRingTile + e * kSrThreads + tid;
+    q[e] = i < b.cap ? raw[i] : make_float4(0, 0, 0, 0);
+  }
+  const int R = p.R, nt = (n + kRingTile - 1) / kRingTile;
+#else
   const int n = b.raw_n[s], R = p.R, nt = (n + kRingTile - 1) / kRingTile;
+#endif
   const int nb = key_bits(R);
   if (t == 0) {  // the sweep's error bits and ring bounds start here (tile 0 alone writes err in this launch)
     if (tid < 2 * R) b.ring_se[s * 2 * R + tid] = 0;
@@ -706,7 +793,10 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
     return;
   }
   if (t >= nt) return;
-  const float4* raw = b.raw + (size_t)s * b.cap;
+#if LOAM_SR_ENDS_ONCE
+  const int last = ends.x;
+  const float startOri = __int_as_float(ends.y), end_raw = __int_as_float(ends.z);
+#else
   float4 q[kRingE];
 #pragma unroll
   for (int e = 0; e < kRingE; ++e) {
@@ -740,6 +830,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
       }
     }
   }
+#endif
   __shared__ float4 sh_rtab[kRingTabMax];
   ring_tab_load(p, sh_rtab);
   if (tid < R) sh_cnt[tid] = 0;
@@ -747,15 +838,18 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
   for (int k = tid; k < 64 * kSlots; k += kSrThreads) (&sh_wcnt[0][0])[k] = 0;
   __syncthreads();
   SR_PH(2);
-  const float startOri = sh_start;
+#if !LOAM_SR_ENDS_ONCE
+  const float startOri = sh_start, end_raw = sh_end_raw;
+  const int last = sh_last;
+#endif
   float endOri = 0.0f;
-  if (sh_last >= 0) {
-    endOri = (float)(D(sh_end_raw) + 2 * M_PI);
+  if (last >= 0) {
+    endOri = (float)(D(end_raw) + 2 * M_PI);
     if (D(endOri - startOri) > 3 * M_PI) endOri = (float)(D(endOri) - 2 * M_PI);
     else if (D(endOri - startOri) < M_PI) endOri = (float)(D(endOri) + 2 * M_PI);
   }
   if (tid == 0 && t == 0) {
-    if (sh_last < 0) b.err[s] |= ERR_EMPTY;
+    if (last < 0) b.err[s] |= ERR_EMPTY;
     b.sweep_ori[2 * s] = startOri;
     b.sweep_ori[2 * s + 1] = endOri;
   }
@@ -993,13 +1087,34 @@ constexpr int kVgGather = LOAM_VG_GATHER;
 #ifndef LOAM_RINGVG_HOLD
 #define LOAM_RINGVG_HOLD 1
 #endif
+// The held path sorts its runs on 32-bit keys, (voxel << rb) | run number with rb =
+// ceil(log2(runs)), whenever the ring's voxel count fits the 32 - rb bits left (chosen per ring,
+// workgroup-uniform; 0: always the 64-bit keys, for A/B builds).  The run number orders a voxel's
+// runs by their first candidate as (first << 16) did, and replaces it in the key: the runs' first
+// candidates stay where the run pass wrote them, as 16-bit words in the upper half of the same key
+// array (first[j], first[j + 1]) = run j's members, so the run-length pass and its two barriers go),
+// and a compare-exchange moves, compares and shuffles one word instead of two.
+#ifndef LOAM_RINGVG_K32
+#define LOAM_RINGVG_K32 1
+#endif
+// k_sr_ringvg loads the ring's candidates together with its header words, one round trip to memory
+// instead of two before the gather (0: the copy to LDS first, for A/B builds)
+#ifndef LOAM_RINGVG_CREG
+#define LOAM_RINGVG_CREG 1
+#endif
 // PCL VoxelGrid 0.2 of one ring's lessFlat candidates pts[lo + cand[0..nc)) into
 // outp (capacity outcap), the whole workgroup (:575-579): bbox, (voxel, candidate) keys, sort,
 // ordered per-voxel float means.  Returns the voxel count (clamped to outcap, *err flagged).
+// creg (the held path, LOAM_RINGVG_CREG): the thread's candidates e * NT + tid as the caller loaded
+// them from memory, cand not yet written: they go to cand here, behind the bounding box's barrier,
+// and the gather does not wait for an LDS round trip.
 template <int CAP, bool BIG, typename CandT>
-LOAM_D int ring_vg(const float4* pts, int lo, const CandT* cand, int nc, uint64_t* keys, float4* outp, int outcap,
-                   float (*red)[kSelThreads / 64], int* scratch, int* err) {
+LOAM_D int ring_vg(const float4* pts, int lo, CandT* cand, int nc, uint64_t* keys, float4* outp, int outcap,
+                   float (*red)[kSelThreads / 64], int* scratch, int* err, const CandT* creg = nullptr SR_PH_PARAM) {
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+#ifdef LOAM_SR_PHASES
+  unsigned long long ph_t[8] = {0}, ph_last = ph0 ? ph0 : __builtin_amdgcn_s_memrealtime();
+#endif
   float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
   // HOLD: the thread's candidates stay in registers from the bbox pass to the key pass (one read of
   // the candidates from memory instead of two)
@@ -1010,7 +1125,12 @@ LOAM_D int ring_vg(const float4* pts, int lo, const CandT* cand, int nc, uint64_
 #pragma unroll
     for (int e = 0; e < RH; ++e) {
       const int t = e * kSelThreads + tid;
-      held[e] = t < nc ? pts[lo + cand[t]] : make_float4(0, 0, 0, 0);
+      if (creg) {
+        held[e] = t < nc ? pts[lo + creg[e]] : make_float4(0, 0, 0, 0);
+        if (t < nc) cand[t] = creg[e];
+      } else {
+        held[e] = t < nc ? pts[lo + cand[t]] : make_float4(0, 0, 0, 0);
+      }
     }
 #pragma unroll
     for (int e = 0; e < RH; ++e)
@@ -1041,6 +1161,7 @@ LOAM_D int ring_vg(const float4* pts, int lo, const CandT* cand, int nc, uint64_
   int nout = 0;
   if (nc > 0) {
     const float inv = 1.0f / 0.2f;
+    SR_PH(1);
     if (vg_leaf_too_small(mn, mx, inv)) {  // "leaf size too small": output = input
       for (int t = tid; t < nc; t += kSelThreads)
         if (t < outcap) outp[t] = pts[lo + cand[t]];
@@ -1060,6 +1181,11 @@ LOAM_D int ring_vg(const float4* pts, int lo, const CandT* cand, int nc, uint64_
         // the stable (voxel, candidate) sort, so the means are summed in the same order.
         constexpr int NW = kSelThreads / 64;
         int nruns = 0;
+        constexpr bool K32 = HOLD && LOAM_RINGVG_K32;
+        [[maybe_unused]] int rb = 0;       // bits of the run number in a 32-bit key
+        [[maybe_unused]] bool k32 = false;
+        uint32_t* const key32 = reinterpret_cast<uint32_t*>(keys);       // [CAP]
+        uint16_t* const first = reinterpret_cast<uint16_t*>(key32 + CAP);  // [runs + 1] <= CAP + 1 of the 2 CAP left
         if constexpr (HOLD) {
           // all chunks at once: the thread's held candidates e * NT + tid, their run heads ranked by
           // wave ballots and the (chunk, wave) slots' counts prefixed in candidate order (two
@@ -1097,10 +1223,27 @@ LOAM_D int ring_vg(const float4* pts, int lo, const CandT* cand, int nc, uint64_
           const int c = lane < RH * NW ? rs_cnt[lane] : 0;
           const int incl = wave_incl_scan_x(c);
           nruns = __shfl(incl, RH * NW - 1, 64);
+          if constexpr (K32) {
+            rb = nruns > 1 ? 32 - __clz(nruns - 1) : 0;
+            const uint64_t nvox = (uint64_t)divx * (uint64_t)divy * (uint64_t)(maxb[2] - minb[2] + 1);  // every idx is below it
+            k32 = nvox <= (1ull << (32 - rb));
+          }
+          if (k32) {
+#pragma unroll
+            for (int e = 0; e < RH; ++e) {
+              const int j = __shfl(incl - c, e * NW + w, 64) + ex[e];
+              if (ex[e] >= 0) {
+                key32[j] = (idx[e] << rb) | (uint32_t)j;
+                first[j] = (uint16_t)(e * kSelThreads + tid);
+              }
+            }
+            if (tid == 0) first[nruns] = (uint16_t)nc;
+          } else {
 #pragma unroll
           for (int e = 0; e < RH; ++e) {
             const int base = __shfl(incl - c, e * NW + w, 64);
             if (ex[e] >= 0) keys[base + ex[e]] = ((uint64_t)idx[e] << 32) | ((uint32_t)(e * kSelThreads + tid) << 16);
+          }
           }
         } else {
         uint32_t* edge = reinterpret_cast<uint32_t*>(&red[0][0]);  // last voxel of each wave's chunk
@@ -1136,6 +1279,7 @@ LOAM_D int ring_vg(const float4* pts, int lo, const CandT* cand, int nc, uint64_
         }
         __syncthreads();
         constexpr int RE = CAP / kSelThreads;
+        if (!k32) {
         uint32_t nxt[RE];
 #pragma unroll
         for (int e = 0; e < RE; ++e) {
@@ -1149,69 +1293,102 @@ LOAM_D int ring_vg(const float4* pts, int lo, const CandT* cand, int nc, uint64_
           if (r < nruns) keys[r] |= nxt[e] - ((uint32_t)keys[r] >> 16);
         }
         __syncthreads();
-        reg_bitonic_sort<kSelThreads, CAP / kSelThreads>(keys, nruns);
+        }
+        SR_PH(2);
+        if (k32) reg_bitonic_sort<kSelThreads, CAP / kSelThreads>(key32, nruns);
+        else reg_bitonic_sort<kSelThreads, CAP / kSelThreads>(keys, nruns);
+        SR_PH(3);
         // voxel heads among the sorted runs r = e * NT + tid, ranked like the runs above (one barrier)
         static_assert(RE * NW <= 64, "slot prefix over one wave");
         __shared__ int vs_cnt[RE * NW];
-        int vex[RE];
-#pragma unroll
-        for (int e = 0; e < RE; ++e) {
-          const int r = e * kSelThreads + tid;
-          const bool head = r < nruns && (r == 0 || (keys[r] >> 32) != (keys[r - 1] >> 32));
-          const uint64_t m = __ballot(head);
-          vex[e] = head ? __popcll(m & lanemask_lt()) : -1;
-          if (lane == 0) vs_cnt[e * NW + w] = __popcll(m);
-        }
-        __syncthreads();
-        const int vc = lane < RE * NW ? vs_cnt[lane] : 0;
-        const int vincl = wave_incl_scan_x(vc);
-#pragma unroll
-        for (int e = 0; e < RE; ++e) {
-          const int r = e * kSelThreads + tid;
-          const int vbase = __shfl(vincl - vc, e * NW + w, 64);
-          if (vex[e] >= 0) {
-            const int slot_out = vbase + vex[e];
-            const uint32_t vk = (uint32_t)(keys[r] >> 32);
-            float sx = 0, sy = 0, sz = 0, si = 0;
-            int cnt = 0;
-            // the voxel's members over all its runs (in run order, members ascending: the sorted
-            // order), kVgGather gathers in flight per step whatever the run lengths
-            int rr = r;
-            uint32_t kk = (uint32_t)keys[r];
-            int m = (int)(kk >> 16), m1 = m + (int)(kk & 0xffffu);
-            const int mfirst = m;
-            bool more = true;
-            while (more) {
-              int mi[kVgGather];
-#pragma unroll
-              for (int u = 0; u < kVgGather; ++u) {
-                if (more && m >= m1) {  // the voxel's next run
-                  ++rr;
-                  if (rr < nruns && (uint32_t)(keys[rr] >> 32) == vk) {
-                    kk = (uint32_t)keys[rr];
-                    m = (int)(kk >> 16);
-                    m1 = m + (int)(kk & 0xffffu);
-                  } else {
-                    more = false;
-                  }
-                }
-                mi[u] = more ? m++ : -1;
-              }
-              float4 a[kVgGather];
-#pragma unroll
-              for (int u = 0; u < kVgGather; ++u) a[u] = pts[lo + cand[mi[u] >= 0 ? mi[u] : mfirst]];
-#pragma unroll
-              for (int u = 0; u < kVgGather; ++u)
-                if (mi[u] >= 0) { sx += a[u].x; sy += a[u].y; sz += a[u].z; si += a[u].w; ++cnt; }
-              if (more && m >= m1)  // run consumed: go on only when the voxel has another
-                more = rr + 1 < nruns && (uint32_t)(keys[rr + 1] >> 32) == vk;
+        auto means = [&](auto wide) {  // wide: std::false_type for the 32-bit keys
+          constexpr bool K = !decltype(wide)::value;
+          auto vox = [&](int r) -> uint32_t {
+            if constexpr (K) return key32[r] >> rb;
+            else return (uint32_t)(keys[r] >> 32);
+          };
+          auto span = [&](int r, int& m, int& m1) {  // the run's members [m, m1)
+            if constexpr (K) {
+              const int j = (int)(key32[r] & ((1u << rb) - 1u));
+              m = first[j];
+              m1 = first[j + 1];
+            } else {
+              const uint32_t kk = (uint32_t)keys[r];
+              m = (int)(kk >> 16);
+              m1 = m + (int)(kk & 0xffffu);
             }
-            const float fc = (float)cnt;
-            if (slot_out < outcap) outp[slot_out] = make_float4(sx / fc, sy / fc, sz / fc, si / fc);
+          };
+          int vex[RE];
+#pragma unroll
+          for (int e = 0; e < RE; ++e) {
+            const int r = e * kSelThreads + tid;
+            const bool head = r < nruns && (r == 0 || vox(r) != vox(r - 1));
+            const uint64_t m = __ballot(head);
+            vex[e] = head ? __popcll(m & lanemask_lt()) : -1;
+            if (lane == 0) vs_cnt[e * NW + w] = __popcll(m);
           }
+          __syncthreads();
+          SR_PH(4);
+          const int vc = lane < RE * NW ? vs_cnt[lane] : 0;
+          const int vincl = wave_incl_scan_x(vc);
+#pragma unroll
+          for (int e = 0; e < RE; ++e) {
+            const int r = e * kSelThreads + tid;
+            const int vbase = __shfl(vincl - vc, e * NW + w, 64);
+            if (vex[e] >= 0) {
+              const int slot_out = vbase + vex[e];
+              const uint32_t vk = vox(r);
+              float sx = 0, sy = 0, sz = 0, si = 0;
+              int cnt = 0;
+              // the voxel's members over all its runs (in run order, members ascending: the sorted
+              // order), kVgGather gathers in flight per step whatever the run lengths
+              int rr = r, m, m1;
+              span(r, m, m1);
+              const int mfirst = m;
+              bool more = true;
+              while (more) {
+                int mi[kVgGather];
+#pragma unroll
+                for (int u = 0; u < kVgGather; ++u) {
+                  if (more && m >= m1) {  // the voxel's next run
+                    ++rr;
+                    if (rr < nruns && vox(rr) == vk) span(rr, m, m1);
+                    else more = false;
+                  }
+                  mi[u] = more ? m++ : -1;
+                }
+                float4 a[kVgGather];
+#pragma unroll
+                for (int u = 0; u < kVgGather; ++u) a[u] = pts[lo + cand[mi[u] >= 0 ? mi[u] : mfirst]];
+#pragma unroll
+                for (int u = 0; u < kVgGather; ++u)
+                  if (mi[u] >= 0) { sx += a[u].x; sy += a[u].y; sz += a[u].z; si += a[u].w; ++cnt; }
+                if (more && m >= m1)  // run consumed: go on only when the voxel has another
+                  more = rr + 1 < nruns && vox(rr + 1) == vk;
+              }
+              const float fc = (float)cnt;
+              if (slot_out < outcap) outp[slot_out] = make_float4(sx / fc, sy / fc, sz / fc, si / fc);
+            }
+          }
+          __syncthreads();  // the keys are read until here (a caller may reuse them)
+          SR_PH(5);
+          nout = __shfl(vincl, RE * NW - 1, 64);
+        };
+        if constexpr (K32) {
+          if (k32) means(std::false_type{});
+          else means(std::true_type{});
+        } else {
+          means(std::true_type{});
         }
-        __syncthreads();  // the keys are read until here (a caller may reuse them)
-        nout = __shfl(vincl, RE * NW - 1, 64);
+#ifdef LOAM_SR_PHASES
+        if constexpr (HOLD)
+          if (tid == 0) {
+            atomicAdd(&g_vg_ph[0], 1ull);
+            for (int k = 1; k < 6; ++k) atomicAdd(&g_vg_ph[k], ph_t[k]);
+            atomicAdd(&g_vg_ph[6], k32 ? 1ull : 0ull);
+            atomicAdd(&g_vg_ph[7], (unsigned long long)nruns);
+          }
+#endif
       } else
       {
         const int P2c = next_pow2(nc);
@@ -1802,11 +1979,23 @@ __global__ __launch_bounds__(64 * kPickWaves) __attribute__((amdgpu_waves_per_eu
 }
 
 __global__ __launch_bounds__(kSelThreads) void k_sr_ringvg(SrBuffers b, SrParams p) {
+#ifdef LOAM_SR_PHASES
+  const unsigned long long ph0 = __builtin_amdgcn_s_memrealtime();
+#endif
   const int q = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, R = p.R;
   // the ring's words loaded together (one round trip), then the early exits
   const int big = b.sel_big[s], n = b.n_full[s];
   int lo = b.ring_se[s * 2 * R + q], en = b.ring_se[s * 2 * R + R + q];
   const int nc = min(b.st_ncand[s * R + q], kPickCap);
+  const uint16_t* cg = b.st_cand + (size_t)(s * R + q) * kRingCap;
+#if LOAM_RINGVG_CREG
+  // ... and the thread's candidates with them: t < kPickCap <= kRingCap stays inside the ring's row of
+  // st_cand whatever nc turns out to be (words at or beyond nc are stale and dropped by t < nc)
+  static_assert(kPickCap <= kRingCap, "candidate row");
+  uint16_t creg[kPickCap / kSelThreads];
+#pragma unroll
+  for (int e = 0; e < kPickCap / kSelThreads; ++e) creg[e] = cg[e * kSelThreads + tid];
+#endif
   if (big != 0 || n <= 0) return;
   if (q == 0) lo = 5;
   if (q == R - 1) en = n - 5;
@@ -1815,12 +2004,16 @@ __global__ __launch_bounds__(kSelThreads) void k_sr_ringvg(SrBuffers b, SrParams
   __shared__ uint16_t cand[kPickCap];
   __shared__ float red[6][kSelThreads / 64];
   __shared__ int scratch[16];
-  const uint16_t* cg = b.st_cand + (size_t)(s * R + q) * kRingCap;
+#if LOAM_RINGVG_CREG
+  const uint16_t* cr = creg;
+#else
+  const uint16_t* cr = nullptr;
   for (int t = tid; t < nc; t += kSelThreads) cand[t] = cg[t];
   __syncthreads();
+#endif
   const int nout = ring_vg<kPickCap, false>(b.full + (size_t)s * b.cap, lo, cand, nc, keys,
                                             b.st_lflat + (size_t)s * R * kRingCap + q * kRingCap, kRingCap, red,
-                                            scratch, b.err + s);
+                                            scratch, b.err + s, cr SR_PH_ARG(ph0));
   if (tid == 0) b.st_cnt[(size_t)(s * R + q) * 4 + 3] = nout;
 }
 
@@ -2081,6 +2274,7 @@ hipError_t sr_alloc(SrBuffers& b, int S, int cap, int R) {
   A(&b.tileF, (size_t)S * b.ntiles() * sizeof(int));
   A(&b.ring_sync, sizeof(int));
   A(&b.sweep_ori, (size_t)S * 2 * sizeof(float));
+  A(&b.sweep_ends, (size_t)S * sizeof(int4));
   A(&b.full, n * sizeof(float4));
   A(&b.n_full, S * sizeof(int));
   A(&b.curv, n * sizeof(float));
@@ -2212,7 +2406,7 @@ void sr_ring_tab_free(SrRingTab& t) {
 }
 
 void sr_free(SrBuffers& b) {
-  void* ptrs[] = {b.raw, b.raw_n, b.tmp_ori, b.tmp_sid, b.tilecnt, b.tileF, b.ring_sync, b.sweep_ori, b.full, b.n_full, b.curv,
+  void* ptrs[] = {b.raw, b.raw_n, b.tmp_ori, b.tmp_sid, b.tilecnt, b.tileF, b.ring_sync, b.sweep_ori, b.sweep_ends, b.full, b.n_full, b.curv,
                   b.picked, b.sortind, b.label, b.ring_se, b.st_sharp, b.st_lsharp, b.st_flat,
                   b.st_lflat, b.st_cnt, b.st_cand, b.st_ncand, b.sharp, b.lsharp, b.flat, b.lflat, b.cnt, b.err, b.sel_big, b.sel_list, b.st_loff, b.big_keys, b.big_sidx, b.big_cand};
   for (void* q : ptrs)
@@ -2257,9 +2451,7 @@ void sr_launch(const SrBuffers& b, const SrParams& p, hipStream_t st, Prof* prof
     // (a margin of 2: a sweep's tiles fit in half the co-resident slots; HDL-64E's 160k-point
     // sweeps are 79 tiles against several per CU x 256 CUs on MI355X)
     if (kSrRingFused && b.S >= kSrRingFusedMin && 2 * rtiles <= sr_ring_fused_capacity()) {
-      HIPCHK(hipMemsetAsync(b.ring_sync, 0, sizeof(int), st));
-      HIPCHK(hipMemsetAsync(b.tilecnt, 0xff, (size_t)b.S * rtiles * b.R * sizeof(int), st));
-      HIPCHK(hipMemsetAsync(b.tileF, 0xff, (size_t)b.S * rtiles * sizeof(int), st));
+      hipLaunchKernelGGL(k_sr_ring_prep, dim3(b.S), dim3(kPrepThreads), 0, st, b, b.R, rtiles);
       hipLaunchKernelGGL(k_sr_ring_fused, dim3(rtiles * b.S), dim3(kSrThreads), 0, st, b, p, rtiles);
     } else {
       hipLaunchKernelGGL(k_sr_ring_count<false>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
@@ -2347,5 +2539,12 @@ extern "C" int loam_debug_phases_sr(unsigned long long* out) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(loam::g_sr_ph), sizeof(loam::g_sr_ph)) != hipSuccess) return -1;
   const unsigned long long zero[8] = {0};
   return hipMemcpyToSymbol(HIP_SYMBOL(loam::g_sr_ph), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
+}
+// the same for k_sr_ringvg (g_vg_ph)
+extern "C" int loam_debug_phases_ringvg(unsigned long long* out) {
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(loam::g_vg_ph), sizeof(loam::g_vg_ph)) != hipSuccess) return -1;
+  const unsigned long long zero[8] = {0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(loam::g_vg_ph), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
 }
 #endif
