@@ -295,7 +295,8 @@ struct Staging {
   }
 };
 
-// the thread-local message loam_last_error() returns (engine.cpp)
+// the thread-local message loam_last_error() returns (kept in engine.cpp; the engine's own files set it through
+// fail(), engine_ctx.hpp)
 void set_last_error(const std::string& msg);
 
 // The ring model's threshold table, built once per context from ring_id itself (sr.hip).

@@ -1,5 +1,5 @@
 // Lanes: the working set of S sequences stepped in lockstep and the kernel that gathers a step's
-// per-lane results (lanes.hpp; the step itself is composed in engine.cpp from the batch kernels).
+// per-lane results (lanes.hpp; the step itself is composed in engine_lanes.cpp from the batch kernels).
 #include "lanes.hpp"
 
 namespace loam {
