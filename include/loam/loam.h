@@ -46,6 +46,8 @@ extern "C" {
 /* ring-ID models for scan registration */
 #define LOAM_RING_VLP16 0  /* reference: round(angle) -> r>0 ? r : r+(N-1)  src/scanRegistration.cpp:248-260 */
 #define LOAM_RING_LINEAR 1 /* bk HDL-64E hint: int((angle-lo)/step + 0.5f), bk src/scanRegistration.cpp:268-275 */
+#define LOAM_RING_TABLE 2  /* a table of elevation intervals (loam_set_ring_table), not a value of loam_config::ring_model */
+#define LOAM_RING_TABLE_MAX 64 /* intervals of a ring table */
 
 /* PCL PointXYZI payload in a 16-byte record (PCL's in-memory PointXYZI is 32 B with padding).
  * intensity = ring + 0.1*relTime out of scan registration (src/scanRegistration.cpp:283-284),
@@ -120,6 +122,39 @@ void loam_config_default(loam_config *cfg);               /* reference constants
 int loam_create(loam_ctx **out, const loam_config *cfg, int device);
 void loam_destroy(loam_ctx *ctx);
 const char *loam_last_error(void);
+
+/* ---- ring tables: a ring model stated as data, for lidars whose beams are not evenly spaced
+ * (VLP-32C, Pandar40/64, calibrated elevations) ----
+ * A table is n intervals, 1 <= n <= LOAM_RING_TABLE_MAX, given as bound_deg[n + 1] (strictly
+ * ascending) and ring[n].  With a = the reference's float vertical angle
+ * (atan(y / sqrt(x^2 + z^2)) * 180 / pi in the camera frame, src/scanRegistration.cpp:241-247), a
+ * point's ring is ring[i] for the i with bound_deg[i] <= a < bound_deg[i + 1], compared as floats.
+ * The point is dropped (the reference's scanID < 0 || scanID > N_SCANS - 1 skip, :262-265) when a is
+ * below bound_deg[0], at or above bound_deg[n] or NaN, and when ring[i] == -1.  Ring order should
+ * follow elevation: the odometry associates across neighbouring rings (+-2.5).
+ *
+ * loam_ring_table_check (host only, no context): LOAM_OK, or LOAM_E_INVAL with the rule broken in
+ * loam_last_error(): pointers non-null; n_rings in [2, 64]; n in range; every bound finite and
+ * inside (-89, 89); bounds strictly ascending; every interval at least 1/32 degree wide; every
+ * ring[i] in [-1, n_rings); at least one ring[i] not -1.
+ *
+ * loam_ring_table_of_model (host only): the table that restates cfg's built-in model (cfg->n_rings,
+ * ring_model, ring_lo_deg, ring_hi_deg): the intervals from the first to the last valid ring, each
+ * bound the first float at which the new ring holds, so the table gives the model's ring on every
+ * float in [bound_deg[0], bound_deg[*n]).  bound_deg holds LOAM_RING_TABLE_MAX + 1 floats, ring
+ * LOAM_RING_TABLE_MAX.  LOAM_E_INVAL (nothing written) for a model that needs more than
+ * LOAM_RING_TABLE_MAX intervals or whose table the check refuses.
+ *
+ * loam_set_ring_table: the context's ring model becomes a copy of the table, whatever
+ * cfg.ring_model said; n_rings (loam_create) still sizes everything.  Every service of the context
+ * then uses it: the node calls, the chain, the batch, the lanes.  Allowed only while the context has
+ * seen no sweep: after a successful loam_scan_registration, loam_chain_sweep, loam_batch_upload,
+ * loam_batch_feed, loam_lanes_open or loam_lanes_open_shared it returns LOAM_E_INVAL and changes
+ * nothing (a sensor does not change during a context's life).  Argument errors are the check's
+ * (against the context's n_rings); LOAM_E_NOMEM / LOAM_E_HIP leave the old model intact. */
+int loam_ring_table_check(uint32_t n_rings, uint32_t n, const float *bound_deg, const int32_t *ring);
+int loam_ring_table_of_model(const loam_config *cfg, uint32_t *n, float *bound_deg, int32_t *ring);
+int loam_set_ring_table(loam_ctx *ctx, uint32_t n, const float *bound_deg, const int32_t *ring);
 
 /* = the /imu/data handlers of scanRegistration (src/scanRegistration.cpp:638-660: queue entry, gravity
  * removal, AccumulateIMUShift) and laserMapping (src/laserMapping.cpp:323-335).  quat_xyzw = the

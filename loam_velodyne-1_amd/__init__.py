@@ -24,6 +24,7 @@ _LIB = None
 LOAM_OK, LOAM_E_INVAL, LOAM_E_CAPACITY, LOAM_E_HIP, LOAM_E_NOT_READY, LOAM_E_NOMEM = 0, -1, -2, -3, -4, -5
 PUB_POSE, PUB_CLOUDS, PUB_FULL = 1, 2, 4
 RING_VLP16, RING_LINEAR = 0, 1
+RING_TABLE_MAX = 64  # LOAM_RING_TABLE_MAX: intervals of a ring table (Engine.set_ring_table)
 
 
 class LoamError(RuntimeError):
@@ -209,6 +210,7 @@ class LanesCloudsOut(ctypes.Structure):
 EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_error", "loam_imu",
            "loam_scan_registration", "loam_odometry", "loam_mapping", "loam_mapping_surround",
            "loam_maintenance", "loam_chain_sweep",
+           "loam_ring_table_check", "loam_ring_table_of_model", "loam_set_ring_table",
            "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_map_localize", "loam_map_score", "loam_get_stats",
            "loam_lanes_open", "loam_lanes_push", "loam_lanes_pull", "loam_lanes_registered", "loam_lanes_map_export",
            "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
@@ -245,6 +247,9 @@ def lib():
         L.loam_mapping_surround.argtypes = [PP, P(CloudOut), P(ctypes.c_int)]
         L.loam_chain_sweep.argtypes = [PP, ctypes.c_double, CloudIn, P(ChainOut)]
         L.loam_maintenance.argtypes = [P(Pose6)] * 4
+        L.loam_ring_table_check.argtypes = [ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_float), P(ctypes.c_int32)]
+        L.loam_ring_table_of_model.argtypes = [P(Config), P(ctypes.c_uint32), P(ctypes.c_float), P(ctypes.c_int32)]
+        L.loam_set_ring_table.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_float), P(ctypes.c_int32)]
         L.loam_batch_upload.argtypes = [PP, ctypes.c_uint32, P(CloudIn), P(CloudIn)]
         L.loam_batch_feed.argtypes = [PP, ctypes.c_uint32, P(CloudIn), P(CloudIn)]
         L.loam_batch_run.argtypes = [PP]
@@ -307,6 +312,48 @@ def default_config(**kw):
     for k, v in kw.items():
         setattr(c, k, v)
     return c
+
+
+def _ring_table_args(bounds, rings):
+    b = np.ascontiguousarray(bounds, np.float32).reshape(-1)
+    r = np.ascontiguousarray(rings, np.int32).reshape(-1)
+    if len(b) != len(r) + 1:
+        raise ValueError("a ring table of n intervals has n + 1 bounds and n rings")
+    return (b.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), r.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            len(r), (b, r))
+
+
+def ring_table_check(n_rings, bounds, rings):
+    """loam_ring_table_check: raises LoamError with the rule a table (bounds [n + 1] degrees, rings [n]) breaks"""
+    pb, pr, n, _keep = _ring_table_args(bounds, rings)
+    _check(lib().loam_ring_table_check(n_rings, n, pb, pr))
+
+
+def ring_table_of_model(cfg):
+    """loam_ring_table_of_model: (bounds float32 [n + 1], rings int32 [n]) restating cfg's built-in ring model"""
+    b = np.zeros(RING_TABLE_MAX + 1, np.float32)
+    r = np.zeros(RING_TABLE_MAX, np.int32)
+    n = ctypes.c_uint32(0)
+    _check(lib().loam_ring_table_of_model(ctypes.byref(cfg), ctypes.byref(n),
+                                          b.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                          r.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return b[:n.value + 1].copy(), r[:n.value].copy()
+
+
+def ring_table_from_elevations(elev_deg):
+    """the ring table of a lidar from its beams' elevations (degrees, any order, 2 .. 64 distinct values; ValueError otherwise):
+    the beams sorted by ascending elevation are rings 0 .. R - 1 (the odometry's neighbouring-ring test
+    needs ring order to follow elevation), the bounds are the midpoints between neighbouring beams,
+    and each outer bound lies half the nearest spacing beyond its end beam.
+    Returns (bounds float32 [R + 1], rings int32 [R]); ring i is beam np.argsort(elev_deg)[i]."""
+    e = np.sort(np.asarray(elev_deg, np.float64).reshape(-1))
+    if not 2 <= len(e) <= RING_TABLE_MAX:
+        raise ValueError(f"2 .. {RING_TABLE_MAX} beams, not {len(e)}")
+    if not np.all(np.isfinite(e)) or np.any(np.diff(e) <= 0):
+        raise ValueError("the elevations must be finite and distinct")
+    mid = 0.5 * (e[:-1] + e[1:])
+    bounds = np.concatenate([[e[0] - 0.5 * (e[1] - e[0])], mid, [e[-1] + 0.5 * (e[-1] - e[-2])]])
+    return bounds.astype(np.float32), np.arange(len(e), dtype=np.int32)
 
 
 def _cloud_in(a):
@@ -381,6 +428,12 @@ class Engine:
         s = Stats()
         _check(lib().loam_get_stats(self.h, ctypes.byref(s)))
         return s.as_dict()
+
+    def set_ring_table(self, bounds, rings):
+        """loam_set_ring_table: the context's ring model becomes the table (bounds [n + 1] degrees,
+        rings [n]; ring_table_from_elevations builds one), before the context's first sweep"""
+        pb, pr, n, _keep = _ring_table_args(bounds, rings)
+        _check(lib().loam_set_ring_table(self.h, n, pb, pr))
 
     # --- the node bodies
     def imu(self, stamp, quat_xyzw, lin_acc):

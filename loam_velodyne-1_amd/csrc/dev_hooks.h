@@ -123,6 +123,13 @@ int loam_dev_od_nn_destroy(loam_dev_od_nn* h);
 int loam_dev_sr_ring_of(int device, int32_t n_rings, int32_t ring_model, float ring_lo_deg, float ring_hi_deg,
                         const float* pts, int32_t n, int32_t* ring, int32_t* exact, int32_t* fast);
 
+/* The same under a ring table (include/loam/loam.h loam_set_ring_table: n_tab intervals,
+ * bound_deg [n_tab + 1], ring_tab [n_tab]) in place of the model arguments; ring, exact and fast as
+ * above.  LOAM_E_INVAL also for a table loam_ring_table_check refuses. */
+int loam_dev_sr_ring_of_table(int device, int32_t n_rings, uint32_t n_tab, const float* bound_deg,
+                              const int32_t* ring_tab, const float* pts, int32_t n, int32_t* ring, int32_t* exact,
+                              int32_t* fast);
+
 /* loam_lanes_push_device's validation and gather (lanes_feed_plan.hpp, lanes.hip k_lanes_gather_dev) on
  * S caller sweeps in device memory: raw [S] is a loam_cloud_in array (include/loam/loam.h) whose data
  * are device pointers; every lane counts as running.  out_raw [S][cap][4] words: first filled with

@@ -15,6 +15,7 @@
 #include <cstdio>
 
 #include "engine_ctx.hpp"
+#include "ring_table.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -198,6 +199,46 @@ int loam_create(loam_ctx** out, const loam_config* cfg, int device) {
     return fail(LOAM_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(he));
   }
   *out = x;
+  return LOAM_OK;
+}
+
+// ------------------------------------------------------------------ ring tables (ring_table.hpp)
+int loam_ring_table_check(uint32_t n_rings, uint32_t n, const float* bound_deg, const int32_t* ring) {
+  const int why = ring_table_check_why(n_rings, n, bound_deg, ring);
+  if (why != kRingTableOk) return fail(LOAM_E_INVAL, std::string("loam_ring_table_check: ") + ring_table_why_text(why));
+  return LOAM_OK;
+}
+
+int loam_ring_table_of_model(const loam_config* cfg, uint32_t* n, float* bound_deg, int32_t* ring) {
+  const std::string who = "loam_ring_table_of_model: ";
+  if (!cfg) return fail(LOAM_E_INVAL, who + "null argument");
+  if (cfg->n_rings < 2 || cfg->n_rings > 64) return fail(LOAM_E_INVAL, who + ring_table_why_text(kRingTableRings));
+  const int why = ring_table_of_model_why((int)cfg->ring_model, (int)cfg->n_rings, cfg->ring_lo_deg, cfg->ring_hi_deg, n,
+                                          bound_deg, ring);
+  if (why != kRingTableOk) return fail(LOAM_E_INVAL, who + ring_table_why_text(why));
+  return LOAM_OK;
+}
+
+int loam_set_ring_table(loam_ctx* x, uint32_t n, const float* bound_deg, const int32_t* ring) {
+  const std::string who = "loam_set_ring_table: ";
+  if (!x) return fail(LOAM_E_INVAL, who + "null argument");
+  if (x->seen_sweep)
+    return fail(LOAM_E_INVAL, who + "the context has seen a sweep (the ring model is set before the first one)");
+  const int why = ring_table_check_why((uint32_t)x->R, n, bound_deg, ring);
+  if (why != kRingTableOk) return fail(LOAM_E_INVAL, who + ring_table_why_text(why));
+  HIP_TRY(hipSetDevice(x->device));
+  SrParams p;
+  p.R = x->R;
+  p.ring_model = LOAM_RING_TABLE;
+  SrRingTab t;
+  const hipError_t he = sr_ring_tab_alloc(t, p, bound_deg, ring, (int)n);  // (synchronous copies: nothing of the caller's is read later)
+  if (he == hipErrorOutOfMemory) return nomem(who + "allocation failed");
+  if (he != hipSuccess) return fail(LOAM_E_HIP, who + hipGetErrorString(he));
+  sr_ring_tab_free(x->ring_tab);  // (no launch has read it: the context has seen no sweep)
+  x->ring_tab = t;
+  x->tb_n = (int)n;
+  std::memcpy(x->tb_bound, bound_deg, ((size_t)n + 1) * sizeof(float));
+  std::memcpy(x->tb_ring, ring, (size_t)n * sizeof(int32_t));
   return LOAM_OK;
 }
 
@@ -523,7 +564,9 @@ int loam_scan_registration(loam_ctx* x, double stamp, loam_cloud_in raw, loam_fe
   if (!x || !out) return fail(LOAM_E_INVAL, "null argument");
   int cnt5[5];
   float imu12[12];
-  return sr_frame(x, stamp, raw, out, cnt5, imu12);
+  const int rc = sr_frame(x, stamp, raw, out, cnt5, imu12);
+  if (rc == LOAM_OK) x->seen_sweep = true;  // (loam_set_ring_table)
+  return rc;
 }
 
 int loam_odometry(loam_ctx* x, double stamp, const loam_features* in, loam_pose6* sum_out,
@@ -785,6 +828,7 @@ int loam_chain_sweep(loam_ctx* x, double stamp, loam_cloud_in raw, loam_chain_ou
   bool sr_pending = false;
   int rc = sr_frame(x, stamp, raw, nullptr, cnt5, imu12, x->od_inited && x->tune.stream_defer ? &sr_pending : nullptr);
   if (rc) return rc;
+  x->seen_sweep = true;  // (loam_set_ring_table: the sweep's rings are the model's from here on)
   int nl3[3] = {0, 0, 0};
   rc = od_frame(x, feat_view(x->sr1, 0, 1), cnt5, imu12, nullptr, &out->od_sum, nullptr, nullptr, nullptr,
                 &out->published, nl3, /*defer=*/true, sr_pending);

@@ -194,6 +194,8 @@ struct SrParams {
   const float4* ring_tab = nullptr;
   int ring_n = 0;
   float ring_a0 = 0.0f, ring_ainv = 0.0f;  // interval guess: (degrees - ring_a0) * ring_ainv
+  // (ring_model LOAM_RING_TABLE: ring_tab points to a block of the fixed layout SrRingTab describes,
+  // which also holds the guess LUT and the table itself; the ring kernels' table instantiations read it)
   loamimu::SrQueue* imu = nullptr;  // device IMU queue of sweep 0 (streaming), nullptr = no IMU
   double time_scan = 0.0;           // timeScanCur: the sweep's stamp
   // lanes, all four or none: imu is then a queue per sweep, and sweep s is
@@ -300,6 +302,10 @@ struct Staging {
 void set_last_error(const std::string& msg);
 
 // The ring model's threshold table, built once per context from ring_id itself (sr.hip).
+// A built-in model's device block is its n intervals.  A table model's (LOAM_RING_TABLE) has a
+// fixed layout in float4 units, so that SrParams stays as it was: kRingTabMax intervals (n used),
+// one header (x: LUT cells as int bits, 0 = the linear guess fits; y: the table's interval count),
+// kRingLutMax LUT bytes, then the table's bounds (kRingTabMax + 1 floats) and rings (kRingTabMax ints).
 struct SrRingTab {
   float4* dev = nullptr;
   int n = 0;
@@ -311,9 +317,11 @@ struct SrRingTab {
     p.ring_ainv = ainv;
   }
 };
-// p: R, ring_model, ring_lo, ring_hi.  A model that cannot be tabulated gives n = 0 (every point
-// then takes the exact evaluation); an error only for a failed allocation or copy.
-hipError_t sr_ring_tab_alloc(SrRingTab& t, const SrParams& p);
+// p: R, ring_model, ring_lo, ring_hi; for LOAM_RING_TABLE the table itself as host arrays (tb_bound
+// [tb_n + 1], tb_ring [tb_n]).  A model whose thresholds cannot be tabulated gives n = 0 (every
+// point then takes the exact evaluation); an error only for a failed allocation or copy.
+hipError_t sr_ring_tab_alloc(SrRingTab& t, const SrParams& p, const float* tb_bound = nullptr,
+                             const int32_t* tb_ring = nullptr, int tb_n = 0);
 void sr_ring_tab_free(SrRingTab& t);
 hipError_t sr_alloc(SrBuffers& b, int S, int cap, int R);  // on failure: freed, b empty
 // S sweeps packed back to back in src (sweep s at off[s], n[s] points) into raw at stride cap

@@ -114,6 +114,7 @@ int loam_batch_upload(loam_ctx* x, uint32_t n, const loam_cloud_in* prev, const 
       HIP_TRY(hipMemcpy(o->raw, x->srb.raw, (size_t)2 * n * x->cap * sizeof(float4), hipMemcpyDeviceToDevice));
       HIP_TRY(hipMemcpy(o->raw_n, x->srb.raw_n, counts.size() * sizeof(int), hipMemcpyDeviceToDevice));
     }
+  x->seen_sweep = true;  // (loam_set_ring_table)
   return LOAM_OK;
 }
 
@@ -510,6 +511,7 @@ int loam_batch_feed(loam_ctx* x, uint32_t n, const loam_cloud_in* prev, const lo
   x->feed_rec[i] = true;
   HIP_TRY(enqueue_ahead(x, i, x->od_s, seed_free_last(x, i, pipe_slots(x, true))));
   x->fed = true;
+  x->seen_sweep = true;  // (loam_set_ring_table)
   return LOAM_OK;
 }
 

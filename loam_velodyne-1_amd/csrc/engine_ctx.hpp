@@ -34,6 +34,12 @@ struct loam_ctx {
   bool sr_inited = false;
   SrBuffers sr1;        // one sweep
   SrRingTab ring_tab;   // the ring model's tangent thresholds (sr_params)
+  // loam_set_ring_table: the table that replaced cfg.ring_model (tb_n = 0: none), allowed until the
+  // context has seen a sweep
+  int tb_n = 0;
+  float tb_bound[LOAM_RING_TABLE_MAX + 1];
+  int32_t tb_ring[LOAM_RING_TABLE_MAX];
+  bool seen_sweep = false;
   SrBuffers odin;       // odometry input feature set (host topics uploaded here)
   OdBuffers od1;        // one odometry problem
   bool od_inited = false;
@@ -235,10 +241,12 @@ inline FeatView feat_view(const SrBuffers& b, int first, int step) {
 inline SrParams sr_params(const loam_ctx* c) {
   SrParams p;
   p.R = c->R;
-  p.ring_model = (int)c->cfg.ring_model;
+  // (any cfg.ring_model but LOAM_RING_LINEAR has always meant the VLP-16 rule; a table comes only
+  // through loam_set_ring_table)
+  p.ring_model = c->tb_n ? LOAM_RING_TABLE : (c->cfg.ring_model == LOAM_RING_LINEAR ? LOAM_RING_LINEAR : LOAM_RING_VLP16);
   p.ring_lo = c->cfg.ring_lo_deg;
   p.ring_hi = c->cfg.ring_hi_deg;
-  c->ring_tab.fill(p);
+  c->ring_tab.fill(p);  // (a table's bounds and rings too: the device copies)
   return p;
 }
 

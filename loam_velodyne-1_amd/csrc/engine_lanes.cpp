@@ -127,6 +127,7 @@ int lanes_open_tail(loam_ctx* x, const std::string& who, uint32_t n_lanes, uint3
   Lanes& L = x->lanes;
   L.od.tune = L.mp.tune = lanes_tuning(x->tune);
   L.od_frame_count = (int)x->cfg.skip_frame_num;  // frameCount = skipFrameNum (src/laserOdometry.cpp:407)
+  x->seen_sweep = true;  // (loam_set_ring_table: the lanes' sweeps take the context's ring model as it is now)
   return LOAM_OK;
 }
 }  // namespace

@@ -29,6 +29,7 @@
 #include "dev_common.hpp"
 #include "dev_hooks.h"
 #include "engine.hpp"
+#include "ring_table.hpp"
 
 using namespace loamdev;
 
@@ -66,24 +67,42 @@ __device__ unsigned long long g_vg_ph[8];
 namespace {
 
 
-LOAM_HD int ring_id(const SrParams& p, float angle) {
-  if (p.ring_model == LOAM_RING_LINEAR) {
-    const float step = (p.ring_hi - p.ring_lo) / (float)(p.R - 1);
-    const float angleID = (angle - p.ring_lo) / step;
-    return (int)(angleID + 0.5f);
+// The ring kernels exist twice (template parameter TAB): for the built-in models, whose code, LDS
+// and arguments are what they were before ring tables, and for a LOAM_RING_TABLE model, whose
+// device block (p.ring_tab, the fixed layout SrRingTab describes) also holds the guess LUT and the
+// table's bounds and rings.  sr_launch picks the instantiation from p.ring_model.
+constexpr int kRingTabMax = kRingTableMax;  // intervals (65 boundaries: the linear model's 64 rings)
+constexpr int kRingLutMax = 2048;           // cells (bytes) of a table model's guess LUT
+constexpr int kRingHdr = kRingTabMax;                       // float4 index of the block's header
+constexpr int kRingLutAt = kRingTabMax + 1;                 // ... of the LUT
+constexpr int kRingTbAt = kRingLutAt + kRingLutMax / 16;    // ... of the bounds, then the rings
+constexpr int kRingBlock = kRingTbAt + (2 * kRingTabMax + 1 + 3) / 4;  // float4 of a table model's block
+template <bool TAB>
+constexpr int kRingLds = TAB ? kRingTbAt : kRingTabMax;     // float4 of a workgroup's LDS copy
+
+LOAM_HD int ring_id(const SrParams& p, float angle) {  // the built-in models
+  return ring_id_model(p.ring_model, p.R, p.ring_lo, p.ring_hi, angle);
+}
+template <bool TAB>
+LOAM_D int ring_id_dev(const SrParams& p, float angle) {
+  if constexpr (TAB) {
+    const float* bound = (const float*)(p.ring_tab + kRingTbAt);
+    return ring_table_lookup(bound, (const int32_t*)(bound + kRingTabMax + 1), __float_as_int(p.ring_tab[kRingHdr].y),
+                             angle);
+  } else {
+    return ring_id(p, angle);
   }
-  int rounded = (int)(D(angle) + (D(angle) < 0.0 ? -0.5 : +0.5));
-  return rounded > 0 ? rounded : rounded + (p.R - 1);
 }
 
 // The reference computes the vertical angle in double (:241-247).  The float evaluation is within
 // 1e-4 degrees of it, so whenever a +-1e-3 degree bracket around it maps to one ring the double
 // evaluation cannot land elsewhere; only points that close to a ring boundary pay for it.
+template <bool TAB>
 LOAM_D int ring_of_exact(const SrParams& p, float px, float py, float pz) {
   const float af = atanf(py / sqrtf(px * px + pz * pz)) * 57.2957795f;
-  const int lo = ring_id(p, af - 1e-3f), hi = ring_id(p, af + 1e-3f);
+  const int lo = ring_id_dev<TAB>(p, af - 1e-3f), hi = ring_id_dev<TAB>(p, af + 1e-3f);
   if (lo == hi) return lo;
-  return ring_id(p, (float)(atan(D(py) / sqrt(D(px * px + pz * pz))) * 180 / M_PI));
+  return ring_id_dev<TAB>(p, (float)(atan(D(py) / sqrt(D(px * px + pz * pz))) * 180 / M_PI));
 }
 
 // The ring from the tangent of the vertical angle, without atan, sqrt or division.  ring_id is a
@@ -98,28 +117,48 @@ LOAM_D int ring_of_exact(const SrParams& p, float px, float py, float pz) {
 // Everything else goes there too: t within 1e-3 degrees of a boundary, beyond the table, not
 // finite, r2 zero, tiny or infinite, or no table (a ring model the host could not tabulate).
 // tab: the workgroup's LDS copy of p.ring_tab (ring_tab_load).
+// A table model's intervals may be of uneven width; they are then guessed in two
+// levels: the polynomial angle indexes a uniform grid no coarser than half the narrowest interval,
+// whose byte names the lowest interval the cell touches; the point's interval is that one or the
+// next (the point's t is at or beyond the first's upper tangent).  The comparison still decides alone.
 #ifndef LOAM_SR_RING_TAB
 #define LOAM_SR_RING_TAB 1  // (0: every point takes ring_of_exact, for A/B builds)
 #endif
+template <bool TAB>
 LOAM_D int ring_of(const SrParams& p, const float4* tab, float px, float py, float pz, bool* fast = nullptr) {
   const float r2 = px * px + pz * pz;
   if (fast) *fast = false;
   if (LOAM_SR_RING_TAB && p.ring_n > 0 && r2 >= 1e-30f && r2 <= 3e38f) {
     const float t = py * __builtin_amdgcn_rsqf(r2);
     const float t2 = t * t;
-    const float a = t * fmaf(t2, fmaf(t2, fmaf(t2, -1.0f / 7, 0.2f), -1.0f / 3), 1.0f) * 57.2957795f;
-    const float g = fminf(fmaxf((a - p.ring_a0) * p.ring_ainv, 0.0f), (float)(p.ring_n - 1));
-    const float4 e = tab[(int)g];
+    const float a = t * fmaf(t2, fmaf(t2, fmaf(t2, -1.0f / 7, 0.2f), -1.0f / 3), 1.0f) * 57.2957795f;  // ring_guess_deg
+    float4 e;
+    const int lut_n = TAB ? __float_as_int(tab[kRingHdr].x) : 0;
+    if (lut_n == 0) {  // evenly spaced intervals (the built-in models): the guess is the interval
+      const float g = fminf(fmaxf((a - p.ring_a0) * p.ring_ainv, 0.0f), (float)(p.ring_n - 1));
+      e = tab[(int)g];
+    } else {  // a cell of the fine grid names the lowest interval it touches; it touches at most two
+      const uint8_t* lut = (const uint8_t*)(tab + kRingLutAt);
+      const float g = fminf(fmaxf((a - p.ring_a0) * p.ring_ainv, 0.0f), (float)(lut_n - 1));
+      const int k = lut[(int)g];
+      e = tab[k];
+      if (!(t < e.y) && k + 1 < p.ring_n) e = tab[k + 1];
+    }
     if (t > e.x && t < e.y) {
       if (fast) *fast = true;
       return __float_as_int(e.z);
     }
   }
-  return ring_of_exact(p, px, py, pz);
+  return ring_of_exact<TAB>(p, px, py, pz);
 }
-constexpr int kRingTabMax = 64;  // intervals (65 boundaries: the linear model's 64 rings)
+template <bool TAB>
 LOAM_D void ring_tab_load(const SrParams& p, float4* tab) {  // a barrier before the first ring_of
   if ((int)threadIdx.x < p.ring_n) tab[threadIdx.x] = p.ring_tab[threadIdx.x];
+  if constexpr (TAB) {  // the header and the LUT's cells in use
+    if (threadIdx.x == 0) tab[kRingHdr] = p.ring_tab[kRingHdr];
+    const int cells16 = (__float_as_int(p.ring_tab[kRingHdr].x) + 15) >> 4;
+    for (int i = threadIdx.x; i < cells16; i += blockDim.x) tab[kRingLutAt + i] = p.ring_tab[kRingLutAt + i];
+  }
 }
 
 using loamimu::kNoOri;
@@ -131,7 +170,7 @@ LOAM_D bool finite3(const float4& q) {
 }
 
 // ---------------------------------------------------------------- ring sort
-template <bool IMU>
+template <bool IMU, bool TAB>
 __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrParams p) {
   const int s = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int n = b.raw_n[s];
@@ -146,8 +185,8 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
   __shared__ int sh_cnt[64];
   __shared__ int sh_wcnt[kSrThreads / 64][64];
   __shared__ int sh_base[64];
-  __shared__ float4 sh_rtab[kRingTabMax];
-  ring_tab_load(p, sh_rtab);
+  __shared__ float4 sh_rtab[kRingLds<TAB>];
+  ring_tab_load<TAB>(p, sh_rtab);
   if (tid == 0) { sh_first = 0x7fffffff; sh_last = -1; sh_F = 0x7fffffff; }
   __syncthreads();
   int f = 0x7fffffff, l = -1;
@@ -185,7 +224,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
       float ori = 0.0f;
       if (finite3(q)) {
         const float px = q.y, py = q.z, pz = q.x;
-        int scanID = ring_of(p, sh_rtab, px, py, pz);
+        int scanID = ring_of<TAB>(p, sh_rtab, px, py, pz);
         if (scanID >= 0 && scanID <= R - 1) {
           sid = (uint8_t)scanID;
           ori = -atan2f_fdlibm(px, pz);
@@ -361,7 +400,7 @@ constexpr int kRingTile = kSrThreads * kRingE;
 // loamimu::tile_ori_key picks among them (imu.hpp; tests/lanes_imu_walk_check.cpp runs the rule on
 // the host against the sequential walk).
 
-template <bool IMU>
+template <bool IMU, bool TAB>
 __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrParams p) {
   const int s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int n = b.raw_n[s], R = p.R;
@@ -402,8 +441,8 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
     }
     if (lane == 0) sh_last = l;
   }
-  __shared__ float4 sh_rtab[kRingTabMax];
-  ring_tab_load(p, sh_rtab);
+  __shared__ float4 sh_rtab[kRingLds<TAB>];
+  ring_tab_load<TAB>(p, sh_rtab);
   if (tid < R) sh_cnt[tid] = 0;
   if (tid == 0) sh_F = 0x7fffffff;
   __syncthreads();
@@ -449,7 +488,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
       float ori = 0.0f;
       if (finite3(q[e])) {
         const float px = q[e].y, py = q[e].z, pz = q[e].x;
-        const int scanID = ring_of(p, sh_rtab, px, py, pz);
+        const int scanID = ring_of<TAB>(p, sh_rtab, px, py, pz);
         if (scanID >= 0 && scanID <= R - 1) {
           sid = (uint8_t)scanID;
           ori = -atan2f_fdlibm(px, pz);
@@ -738,6 +777,7 @@ __global__ __launch_bounds__(kPrepThreads) void k_sr_ring_prep(SrBuffers b, int 
     if (tid == 0) b.sweep_ends[s] = make_int4(sh_last, __float_as_int(sh_start), __float_as_int(sh_end_raw), 0);
   }
 }
+template <bool TAB>
 __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrParams p, int rtiles) {
   constexpr int kW = kSrThreads / 64, kSlots = kRingE * kW;
   static_assert(kSlots <= 64 && (kSlots & (kSlots - 1)) == 0, "slot scan width");
@@ -831,8 +871,8 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
     }
   }
 #endif
-  __shared__ float4 sh_rtab[kRingTabMax];
-  ring_tab_load(p, sh_rtab);
+  __shared__ float4 sh_rtab[kRingLds<TAB>];
+  ring_tab_load<TAB>(p, sh_rtab);
   if (tid < R) sh_cnt[tid] = 0;
   if (tid == 0) sh_F = 0x7fffffff;
   for (int k = tid; k < 64 * kSlots; k += kSrThreads) (&sh_wcnt[0][0])[k] = 0;
@@ -863,7 +903,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
     ori[e] = 0.0f;
     if (i < n && finite3(q[e])) {
       const float px = q[e].y, py = q[e].z, pz = q[e].x;
-      const int scanID = ring_of(p, sh_rtab, px, py, pz);
+      const int scanID = ring_of<TAB>(p, sh_rtab, px, py, pz);
       if (scanID >= 0 && scanID <= R - 1) {
         sid[e] = scanID;
         ori[e] = -atan2f_fdlibm(px, pz);
@@ -2313,46 +2353,26 @@ hipError_t sr_alloc(SrBuffers& b, int S, int cap, int R) {
 // more float inward for the double's own error) and the ring as bits.  Empty when the model
 // cannot be tabulated: a degenerate linear model, two changes within 1/128 degree, more than
 // kRingTabMax intervals, or intervals so uneven that the kernel's linear guess misses their
-// midpoints (every point then takes ring_of_exact, as before the table existed).
-static std::vector<float4> sr_ring_tab_build(const SrParams& p, float& a0, float& ainv) {
+// midpoints and the fine grid of the second level cannot serve them either: more than kRingLutMax
+// cells at half the narrowest interval, or a bound beyond +-44 degrees, where the guess polynomial
+// flattens (every point then takes ring_of_exact, as before the table existed).
+// lut: empty when the linear guess fits (the built-in models), else the second level's cells.
+// tb_bound, tb_ring, tb_n: the table of a LOAM_RING_TABLE model (host arrays).
+static std::vector<float4> sr_ring_tab_build(const SrParams& p, const float* tb_bound, const int32_t* tb_ring, int tb_n,
+                                             float& a0, float& ainv, std::vector<uint8_t>& lut) {
   std::vector<float4> none;
+  lut.clear();
   if (p.R < 1) return none;
-  if (p.ring_model == LOAM_RING_LINEAR) {
-    const float step = (p.ring_hi - p.ring_lo) / (float)(p.R - 1);
-    if (!(step >= 0.01f) || !(fabsf(p.ring_lo) <= 1e4f) || !(fabsf(p.ring_hi) <= 1e4f)) return none;
-  }
-  constexpr int G = 128;
-  std::vector<float> last_old, first_new;  // per boundary: the neighbouring floats around the change
-  std::vector<int> val;                    // val[i]: the ring between boundary i - 1 and boundary i
-  float a = -89.0f;
-  int va = ring_id(p, a);
-  val.push_back(va);
-  for (int i = 1; i <= 178 * G; ++i) {
-    const float c = -89.0f + (float)i / G;
-    const int vc = ring_id(p, c);
-    if (vc != va) {
-      float lo = a, hi = c;
-      for (;;) {
-        const float mid = lo + (hi - lo) * 0.5f;
-        if (!(mid > lo && mid < hi)) break;
-        if (ring_id(p, mid) == va) lo = mid; else hi = mid;
-      }
-      if (ring_id(p, hi) != vc) return none;
-      last_old.push_back(lo);
-      first_new.push_back(hi);
-      val.push_back(vc);
-    }
-    a = c;
-    va = vc;
-  }
-  const int nbnd = (int)first_new.size();
-  int i0 = -1, i1 = -1;  // inner intervals are 1 .. nbnd - 1
-  for (int i = 1; i <= nbnd - 1; ++i)
-    if (val[i] >= 0 && val[i] <= p.R - 1) {
-      if (i0 < 0) i0 = i;
-      i1 = i;
-    }
-  if (i0 < 0 || i1 - i0 + 1 > kRingTabMax) return none;
+  if (p.ring_model == LOAM_RING_LINEAR && !ring_linear_model_ok(p.R, p.ring_lo, p.ring_hi)) return none;
+  RingSteps st;
+  auto id = [&](float a) {
+    return p.ring_model == LOAM_RING_TABLE ? ring_table_lookup(tb_bound, tb_ring, tb_n, a) : ring_id(p, a);
+  };
+  if (!ring_steps_scan(id, st)) return none;
+  const std::vector<float>&last_old = st.last_old, &first_new = st.first_new;  // per boundary: the neighbouring floats around the change
+  const std::vector<int>& val = st.val;  // val[i]: the ring between boundary i - 1 and boundary i
+  int i0 = -1, i1 = -1;                  // inner intervals are 1 .. boundaries - 1
+  if (!ring_steps_valid_span(st, p.R, i0, i1) || i1 - i0 + 1 > kRingTabMax) return none;
   const int n = i1 - i0 + 1;
   auto tan_deg = [](double deg) { return tan(deg * M_PI / 180.0); };
   std::vector<float4> tab(n);
@@ -2379,19 +2399,71 @@ static std::vector<float4> sr_ring_tab_build(const SrParams& p, float& a0, float
     }
     if (ok) return tab;
   }
-  return none;
+  // the second level: a uniform grid of the guess polynomial's angle over the table's own span, its
+  // step half the narrowest interval (as the polynomial sees them), so a cell holds at most one
+  // boundary and a point's interval is the cell's lowest or the next.  A cell's lowest interval is
+  // the one 1e-3 degrees below its lower edge: the device's angle (t from rsq, relative error below
+  // 2^-22) differs from the one computed here by far less.
+  std::vector<float> pa(n + 1);
+  for (int k = 0; k <= n; ++k) {
+    const float b = first_new[i0 - 1 + k];
+    if (!(fabsf(b) <= 44.0f)) return none;
+    pa[k] = ring_guess_deg((float)tan_deg(D(b)));
+  }
+  float wmin = INFINITY;
+  for (int k = 0; k < n; ++k) wmin = fminf(wmin, pa[k + 1] - pa[k]);
+  if (!(wmin >= 8e-3f)) return none;
+  const float w = 0.5f * wmin;
+  const double cells_d = ceil(D(pa[n] - pa[0]) / D(w)) + 1.0;
+  if (!(cells_d <= (double)(kRingLutMax - 3))) return none;
+  const int cells = ((int)cells_d + 3) & ~3;
+  a0 = pa[0];
+  ainv = 1.0f / w;
+  lut.assign(cells, 0);
+  for (int c = 0, k = 0; c < cells; ++c) {
+    const float edge = a0 + (float)c * w - 1e-3f;
+    while (k + 1 < n && pa[k + 1] <= edge) ++k;
+    lut[c] = (uint8_t)k;
+  }
+  // every interval's ends (inside the 1e-3 degree guard) and middle must find it, as ring_of looks.
+  // (A cross-check of the construction at three angles per interval, not the proof: that every point
+  // of an interval finds it rests on the cell width plus the 1e-3 degree margin staying below the
+  // narrowest interval, w + 1e-3 < wmin, which wmin >= 8e-3 and w = wmin / 2 give.)
+  auto cell_of = [&](float a) { return (int)fminf(fmaxf((a - a0) * ainv, 0.0f), (float)(cells - 1)); };
+  for (int k = 0; k < n; ++k)
+    for (float a : {pa[k] + 5e-4f, 0.5f * (pa[k] + pa[k + 1]), pa[k + 1] - 5e-4f}) {
+      const int g = lut[cell_of(a)];
+      if (g != k && g + 1 != k) {
+        lut.clear();
+        return none;
+      }
+    }
+  return tab;
 }
 
-hipError_t sr_ring_tab_alloc(SrRingTab& t, const SrParams& p) {
+hipError_t sr_ring_tab_alloc(SrRingTab& t, const SrParams& p, const float* tb_bound, const int32_t* tb_ring, int tb_n) {
   t = SrRingTab();
-  const std::vector<float4> tab = sr_ring_tab_build(p, t.a0, t.ainv);
-  if (tab.empty()) return hipSuccess;
-  hipError_t e = hipMalloc((void**)&t.dev, tab.size() * sizeof(float4));
+  const bool table = p.ring_model == LOAM_RING_TABLE;
+  if (table && (!tb_bound || !tb_ring || tb_n < 1 || tb_n > kRingTabMax)) return hipErrorInvalidValue;
+  std::vector<uint8_t> lut;
+  const std::vector<float4> tab = sr_ring_tab_build(p, tb_bound, tb_ring, table ? tb_n : 0, t.a0, t.ainv, lut);
+  if (tab.empty() && !table) return hipSuccess;
+  // a built-in model: its intervals; a table model: the fixed layout SrRingTab describes
+  std::vector<float4> blk(table ? (size_t)kRingBlock : tab.size(), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+  if (!tab.empty()) memcpy(blk.data(), tab.data(), tab.size() * sizeof(float4));
+  if (table) {
+    blk[kRingHdr] = make_float4(__builtin_bit_cast(float, (int)lut.size()), __builtin_bit_cast(float, tb_n), 0.0f, 0.0f);
+    if (!lut.empty()) memcpy(blk.data() + kRingLutAt, lut.data(), lut.size());
+    float* q = (float*)(blk.data() + kRingTbAt);
+    memcpy(q, tb_bound, ((size_t)tb_n + 1) * sizeof(float));
+    memcpy(q + kRingTabMax + 1, tb_ring, (size_t)tb_n * sizeof(int32_t));
+  }
+  hipError_t e = hipMalloc((void**)&t.dev, blk.size() * sizeof(float4));
   if (e != hipSuccess) {
     t.dev = nullptr;
     return e;
   }
-  e = hipMemcpy(t.dev, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice);
+  e = hipMemcpy(t.dev, blk.data(), blk.size() * sizeof(float4), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     sr_ring_tab_free(t);
     return e;
@@ -2418,18 +2490,44 @@ void sr_free(SrBuffers& b) {
 // whole sweep's tiles can be resident at once: its workgroups per CU (the occupancy its registers
 // and LDS allow, queried once per device) times the CUs.  Other streams' kernels may hold slots
 // for a while, but they never wait on this launch, so the bound is the idle device's.
-int sr_ring_fused_capacity() {
+// (per instantiation: a table model's carries the LUT in LDS)
+template <bool TAB>
+static int sr_ring_fused_capacity_of() {
   static int cap[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
   if (cap[dev] == 0) {
     int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sr_ring_fused, kSrThreads, 0) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sr_ring_fused<TAB>, kSrThreads, 0) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       per_cu = cus = 0;
     cap[dev] = std::max(1, per_cu * cus);  // (1: a failed query keeps the two-kernel form below)
   }
   return cap[dev];
+}
+int sr_ring_fused_capacity() { return sr_ring_fused_capacity_of<false>(); }
+
+// the ring sort of sr_launch for the built-in models (TAB = false) or a table model
+template <bool TAB>
+static void sr_launch_ring_sort(const SrBuffers& b, const SrParams& p, hipStream_t st, bool lanes_imu) {
+  if (lanes_imu) {  // (never the fused kernel: its tiles wait for each other)
+    const int rtiles = (b.cap + kRingTile - 1) / kRingTile;
+    hipLaunchKernelGGL((k_sr_ring_count<true, TAB>), dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+    hipLaunchKernelGGL(k_sr_ring_scatter<true>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+  } else if (p.imu) {
+    hipLaunchKernelGGL((k_sr_ring_sort<true, TAB>), dim3(b.S), dim3(kSrThreads), 0, st, b, p);
+  } else {
+    const int rtiles = (b.cap + kRingTile - 1) / kRingTile;  // <= b.ntiles(): tilecnt rows fit
+    // (a margin of 2: a sweep's tiles fit in half the co-resident slots; HDL-64E's 160k-point
+    // sweeps are 79 tiles against several per CU x 256 CUs on MI355X)
+    if (kSrRingFused && b.S >= kSrRingFusedMin && 2 * rtiles <= sr_ring_fused_capacity_of<TAB>()) {
+      hipLaunchKernelGGL(k_sr_ring_prep, dim3(b.S), dim3(kPrepThreads), 0, st, b, b.R, rtiles);
+      hipLaunchKernelGGL(k_sr_ring_fused<TAB>, dim3(rtiles * b.S), dim3(kSrThreads), 0, st, b, p, rtiles);
+    } else {
+      hipLaunchKernelGGL((k_sr_ring_count<false, TAB>), dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+      hipLaunchKernelGGL(k_sr_ring_scatter<false>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+    }
+  }
 }
 
 void sr_launch(const SrBuffers& b, const SrParams& p, hipStream_t st, Prof* prof, hipEvent_t sorted) {
@@ -2440,24 +2538,8 @@ void sr_launch(const SrBuffers& b, const SrParams& p, hipStream_t st, Prof* prof
     HIPCHK(hipMemsetAsync(b.err, 0, (size_t)b.S * sizeof(int), st));
   }
   mark("sr_memset");
-  if (lanes_imu) {  // (never the fused kernel: its tiles wait for each other)
-    const int rtiles = (b.cap + kRingTile - 1) / kRingTile;
-    hipLaunchKernelGGL(k_sr_ring_count<true>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
-    hipLaunchKernelGGL(k_sr_ring_scatter<true>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
-  } else if (p.imu) {
-    hipLaunchKernelGGL(k_sr_ring_sort<true>, dim3(b.S), dim3(kSrThreads), 0, st, b, p);
-  } else {
-    const int rtiles = (b.cap + kRingTile - 1) / kRingTile;  // <= b.ntiles(): tilecnt rows fit
-    // (a margin of 2: a sweep's tiles fit in half the co-resident slots; HDL-64E's 160k-point
-    // sweeps are 79 tiles against several per CU x 256 CUs on MI355X)
-    if (kSrRingFused && b.S >= kSrRingFusedMin && 2 * rtiles <= sr_ring_fused_capacity()) {
-      hipLaunchKernelGGL(k_sr_ring_prep, dim3(b.S), dim3(kPrepThreads), 0, st, b, b.R, rtiles);
-      hipLaunchKernelGGL(k_sr_ring_fused, dim3(rtiles * b.S), dim3(kSrThreads), 0, st, b, p, rtiles);
-    } else {
-      hipLaunchKernelGGL(k_sr_ring_count<false>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
-      hipLaunchKernelGGL(k_sr_ring_scatter<false>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
-    }
-  }
+  if (p.ring_model == LOAM_RING_TABLE) sr_launch_ring_sort<true>(b, p, st, lanes_imu);
+  else sr_launch_ring_sort<false>(b, p, st, lanes_imu);
   mark("k_sr_ring_sort");
   if (sorted) HIPCHK(hipEventRecord(sorted, st));  // the ring-sorted full cloud is final here
   hipLaunchKernelGGL(k_sr_features, dim3((b.cap + kFeatSpan - 1) / kFeatSpan, b.S), dim3(kFeatTile), 0,
@@ -2476,51 +2558,50 @@ void sr_launch(const SrBuffers& b, const SrParams& p, hipStream_t st, Prof* prof
 
 // ---------------------------------------------------------------- diagnostic hook (dev_hooks.h)
 namespace {
+template <bool TAB>
 __global__ __launch_bounds__(256) void k_dev_sr_ring_of(SrParams p, const float4* pts, int n, int* ring, int* exact,
                                                          int* fast) {
-  __shared__ float4 sh_rtab[kRingTabMax];
-  ring_tab_load(p, sh_rtab);
+  __shared__ float4 sh_rtab[kRingLds<TAB>];
+  ring_tab_load<TAB>(p, sh_rtab);
   __syncthreads();
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float4 q = pts[i];
   const float px = q.y, py = q.z, pz = q.x;  // the axis swap of :225-229
   bool f;
-  ring[i] = ring_of(p, sh_rtab, px, py, pz, &f);
-  exact[i] = ring_of_exact(p, px, py, pz);
+  ring[i] = ring_of<TAB>(p, sh_rtab, px, py, pz, &f);
+  exact[i] = ring_of_exact<TAB>(p, px, py, pz);
   fast[i] = f ? 1 : 0;
 }
 }  // namespace
 
 }  // namespace loam
 
-extern "C" int loam_dev_sr_ring_of(int device, int32_t n_rings, int32_t ring_model, float ring_lo_deg,
-                                   float ring_hi_deg, const float* pts, int32_t n, int32_t* ring, int32_t* exact,
-                                   int32_t* fast) {
+namespace {
+// both hooks behind their argument checks: p holds the model, tb_* a table model's table
+int dev_sr_ring_of(int device, loam::SrParams p, const float* tb_bound, const int32_t* tb_ring, int tb_n, const float* pts, int32_t n, int32_t* ring, int32_t* exact,
+                   int32_t* fast) {
   using namespace loam;
-  if (!pts || !ring || !exact || !fast || n < 1 || n > LOAM_DEV_SR_RING_MAX) return LOAM_E_INVAL;
-  if (n_rings < 2 || n_rings > 64 || (ring_model != LOAM_RING_VLP16 && ring_model != LOAM_RING_LINEAR)) return LOAM_E_INVAL;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return LOAM_E_HIP;  // (no CPU path, as loam_create)
   if (device < 0 || device >= ndev) return LOAM_E_INVAL;
   if (hipSetDevice(device) != hipSuccess) return LOAM_E_HIP;
-  SrParams p;
-  p.R = n_rings;
-  p.ring_model = ring_model;
-  p.ring_lo = ring_lo_deg;
-  p.ring_hi = ring_hi_deg;
   SrRingTab tab;
   float4* dpts = nullptr;
   int* dout = nullptr;
-  hipError_t e = sr_ring_tab_alloc(tab, p);
+  hipError_t e = sr_ring_tab_alloc(tab, p, tb_bound, tb_ring, tb_n);
   if (e == hipSuccess) e = hipMalloc((void**)&dpts, (size_t)n * sizeof(float4));
   if (e == hipSuccess) e = hipMalloc((void**)&dout, 3 * (size_t)n * sizeof(int));
   const bool nomem = e == hipErrorOutOfMemory;
   if (e == hipSuccess) e = hipMemcpy(dpts, pts, (size_t)n * sizeof(float4), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     tab.fill(p);
-    hipLaunchKernelGGL(k_dev_sr_ring_of, dim3((n + 255) / 256), dim3(256), 0, nullptr, p, dpts, n, dout, dout + n,
-                       dout + 2 * (size_t)n);
+    if (p.ring_model == LOAM_RING_TABLE)
+      hipLaunchKernelGGL(k_dev_sr_ring_of<true>, dim3((n + 255) / 256), dim3(256), 0, nullptr, p, dpts, n, dout, dout + n,
+                         dout + 2 * (size_t)n);
+    else
+      hipLaunchKernelGGL(k_dev_sr_ring_of<false>, dim3((n + 255) / 256), dim3(256), 0, nullptr, p, dpts, n, dout, dout + n,
+                         dout + 2 * (size_t)n);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(ring, dout, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
@@ -2530,6 +2611,33 @@ extern "C" int loam_dev_sr_ring_of(int device, int32_t n_rings, int32_t ring_mod
   if (dout) (void)hipFree(dout);
   sr_ring_tab_free(tab);
   return e == hipSuccess ? LOAM_OK : (nomem ? LOAM_E_NOMEM : LOAM_E_HIP);
+}
+}  // namespace
+
+extern "C" int loam_dev_sr_ring_of(int device, int32_t n_rings, int32_t ring_model, float ring_lo_deg,
+                                   float ring_hi_deg, const float* pts, int32_t n, int32_t* ring, int32_t* exact,
+                                   int32_t* fast) {
+  using namespace loam;
+  if (!pts || !ring || !exact || !fast || n < 1 || n > LOAM_DEV_SR_RING_MAX) return LOAM_E_INVAL;
+  if (n_rings < 2 || n_rings > 64 || (ring_model != LOAM_RING_VLP16 && ring_model != LOAM_RING_LINEAR)) return LOAM_E_INVAL;
+  SrParams p;
+  p.R = n_rings;
+  p.ring_model = ring_model;
+  p.ring_lo = ring_lo_deg;
+  p.ring_hi = ring_hi_deg;
+  return dev_sr_ring_of(device, p, nullptr, nullptr, 0, pts, n, ring, exact, fast);
+}
+
+extern "C" int loam_dev_sr_ring_of_table(int device, int32_t n_rings, uint32_t n_tab, const float* bound_deg,
+                                         const int32_t* ring_tab, const float* pts, int32_t n, int32_t* ring,
+                                         int32_t* exact, int32_t* fast) {
+  using namespace loam;
+  if (!pts || !ring || !exact || !fast || n < 1 || n > LOAM_DEV_SR_RING_MAX) return LOAM_E_INVAL;
+  if (n_rings < 2 || ring_table_check_why((uint32_t)n_rings, n_tab, bound_deg, ring_tab) != kRingTableOk) return LOAM_E_INVAL;
+  SrParams p;
+  p.R = n_rings;
+  p.ring_model = LOAM_RING_TABLE;
+  return dev_sr_ring_of(device, p, bound_deg, ring_tab, (int)n_tab, pts, n, ring, exact, fast);
 }
 
 #ifdef LOAM_SR_PHASES

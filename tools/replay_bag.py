@@ -5,6 +5,12 @@ odometry / mapping poses and (with --oracle) the largest pose difference.
 
     python tools/replay_bag.py BAG [--cloud-topic /velodyne_points] [--imu-topic /imu/data]
                                [--max-sweeps N] [--oracle] [--trajectory out.csv]
+                               [--elevations a,b,c,...]
+
+--elevations: the lidar's beam elevations in degrees (any order, 2 .. 64 of them), for a sensor
+whose beams are not evenly spaced (VLP-32C, Pandar40/64, calibrated values): the engine runs on
+the ring table loam.ring_table_from_elevations builds from them, with one ring per beam.  The CPU
+oracle knows only the two built-in ring models, so --oracle cannot be combined with it.
 """
 import argparse
 import importlib
@@ -27,12 +33,23 @@ def main():
     ap.add_argument("--max-sweeps", type=int, default=0)
     ap.add_argument("--oracle", action="store_true", help="also run the CPU oracle (test infrastructure)")
     ap.add_argument("--trajectory", default="", help="write stamp + mapping pose per published frame (CSV)")
+    ap.add_argument("--elevations", default="", help="beam elevations in degrees, comma separated: a ring table")
     args = ap.parse_args()
+    if args.elevations and args.oracle:
+        ap.error("--oracle knows only the built-in ring models; drop it or --elevations")
     loam = importlib.import_module("loam_velodyne-1_amd")
     rb = importlib.import_module("loam_velodyne-1_amd.rosbag")
+    kw = {}
+    table = None
+    if args.elevations:
+        table = loam.ring_table_from_elevations([float(v) for v in args.elevations.split(",")])
+        kw["n_rings"] = len(table[1])
+        loam.ring_table_check(kw["n_rings"], *table)
+    eng = loam.Engine(loam.default_config(**kw))
+    if table is not None:
+        eng.set_ring_table(*table)
     t0 = time.perf_counter()
-    out = rb.replay(args.bag, loam.Engine(loam.default_config()), args.cloud_topic, args.imu_topic,
-                    args.max_sweeps or None)
+    out = rb.replay(args.bag, eng, args.cloud_topic, args.imu_topic, args.max_sweeps or None)
     dt = time.perf_counter() - t0
     res = {"bag": args.bag, "sweeps": out["sweeps"], "seconds": dt, "scans_per_s": out["sweeps"] / dt if dt else None,
            "odometry_frames": len(out["odometry"]), "mapping_frames": len(out["mapping"]),
