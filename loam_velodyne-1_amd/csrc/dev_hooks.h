@@ -113,6 +113,62 @@ int loam_dev_od_nn_run(loam_dev_od_nn* h, const loam_dev_od_nn_job* job, uint64_
 
 int loam_dev_od_nn_destroy(loam_dev_od_nn* h);
 
+/* One association round of the odometry (od.hip od_assoc_round: k_od_sel / k_od_sel_nn and k_od_assoc,
+ * the launches od_solve makes every fifth iteration) on up to LOAM_DEV_OD_ASSOC_MAX_P caller-made
+ * problems.  A handle owns an OdBuffers of the product's od_alloc and the feature buffers of a FeatView;
+ * consecutive jobs reuse it.  The transform is zero, so TransformToStart leaves the queries as given. */
+typedef struct loam_dev_od_assoc loam_dev_od_assoc;
+
+#define LOAM_DEV_OD_ASSOC_MAX_P 4
+#define LOAM_DEV_OD_ASSOC_MAX_CLOUD 16384
+#define LOAM_DEV_OD_ASSOC_MAX_QUERIES 8192 /* per kind: the forward walk ends at min(queries of the kind, cloud
+                                              size) (Q11), so a walk past 4096 points takes as many queries */
+#define LOAM_DEV_OD_ASSOC_MAX_GRID 16384
+#define LOAM_DEV_OD_ASSOC_SENTINEL (-0x5a5a5a5b) /* neither -1 nor an index */
+
+typedef struct {
+  const float* corner_last;    /* [n_corner_last][4] x, y, z, intensity: its integer part is the ring, 0 .. 63 */
+  int32_t n_corner_last;       /* 1 .. LOAM_DEV_OD_ASSOC_MAX_CLOUD */
+  const float* surf_last;      /* [n_surf_last][4] */
+  int32_t n_surf_last;         /* 1 .. LOAM_DEV_OD_ASSOC_MAX_CLOUD */
+  const float* corner_q;       /* [n_corner_q][4] raw sharp points (w: a whole number), NULL when there are none */
+  int32_t n_corner_q;          /* 0 .. LOAM_DEV_OD_ASSOC_MAX_QUERIES */
+  const float* surf_q;         /* [n_surf_q][4] raw flat points */
+  int32_t n_surf_q;            /* 0 .. LOAM_DEV_OD_ASSOC_MAX_QUERIES; n_corner_q + n_surf_q >= 1 */
+  const int32_t* corner_seeds; /* NULL or [n_corner_q][3]: the previous round's ind1, ind2, ind3 (indices of */
+  const int32_t* surf_seeds;   /* the kind's Last cloud, -1: none); [n_surf_q][3] */
+} loam_dev_od_assoc_problem;
+
+typedef struct {
+  const loam_dev_od_assoc_problem* prob; /* [P] */
+  int32_t P;                             /* 1 .. LOAM_DEV_OD_ASSOC_MAX_P */
+  /* the tuning values od_assoc_round and the kernels read (loam_set_tuning's ranges) */
+  int32_t od_sel_min, od_nn_lane, od_nn_lane_min, od_win_mono, od_win_mono_min;
+  int32_t grid;      /* k_od_assoc's workgroups per problem, 0 .. LOAM_DEV_OD_ASSOC_MAX_GRID; 0: the product's rule */
+  int32_t count;     /* 1: the COUNT instantiations (the work counters), 0: the plain ones */
+  int32_t hash_form; /* od_build_hashes' form: 0 the product's rule (a grid per cloud for P <= 4), 1 the grid
+                        per cloud, 2 a workgroup per cloud */
+} loam_dev_od_assoc_job;
+
+/* LOAM_E_HIP without a GPU (no CPU path), LOAM_E_NOMEM */
+int loam_dev_od_assoc_create(int device, loam_dev_od_assoc** out);
+
+/* A job with any seeds runs as a seeded round (kIsIters > 0, iteration 5; a problem or kind without
+ * seeds then has -1 everywhere), one without as the first round (iteration 0).
+ * ind [P][3][Q], Q = the job's largest n_corner_q + n_surf_q: problem p's ind1 / ind2 / ind3 of its
+ * corner queries, then of its surface queries; the device array is first filled with
+ * LOAM_DEV_OD_ASSOC_SENTINEL and then holds the seeds, so in an unseeded job an entry no kernel wrote
+ * shows (in a seeded one it shows as its seed); entries beyond a problem's queries are the sentinel.
+ * mono [P][2], rstart [P][2][66]: the hash build's ring-monotone flags and ring start tables of the
+ * corner and the surface Last cloud; counters [P][2]: kIsGathered, kIsBoxes (zero unless count).
+ * LOAM_E_HIP also when a kernel raised a problem's error flags (kIsErr).
+ * LOAM_E_INVAL, before the handle is touched, for null pointers, sizes, tuning values, grid, count or
+ * hash_form out of range, a ring outside 0 .. 63, a query w with a fraction, a seed outside [-1, n). */
+int loam_dev_od_assoc_run(loam_dev_od_assoc* h, const loam_dev_od_assoc_job* job, int32_t* ind, int32_t* mono,
+                          int32_t* rstart, int32_t* counters);
+
+int loam_dev_od_assoc_destroy(loam_dev_od_assoc* h);
+
 /* Scan registration's ring ID (sr.hip) of n caller points (sensor frame: x, y, z, -) under a ring
  * model (n_rings in [2, 64], ring_model LOAM_RING_*, the linear model's two angles; what loam_create
  * takes from its loam_config): ring [n] from the production ring_of (tangent thresholds, falling

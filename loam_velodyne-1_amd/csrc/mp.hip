@@ -2269,7 +2269,7 @@ void mp_hash_from(MpBuffers& b, int P, hipStream_t st, bool spread = false) {
   hs.pts_off = b.nfrom; hs.pts_off_stride = 2;
   hs.count = b.nfrom + 1; hs.start = b.hS_start; hs.out = b.hS_pts; hs.tsize = b.hS_T;
   hs.fill = b.h_fill + (size_t)P * b.tmax;  // (the two indexes are built in one launch / concurrently)
-  hash_build_pair(hc, hs, P, st, false, spread);
+  hash_build_pair(hc, hs, P, st, false, spread ? HashForm::kGrid : HashForm::kAuto);
 }
 
 // k_mp_lm_begin, the iterations, k_mp_lm_end; persist: one instance may take the persistent launch

@@ -355,8 +355,8 @@ __global__ __launch_bounds__(256) void k_hash_scatter(HashPair hp) {
   }
 }
 
-void hash_build_pair(const HashJob& a, const HashJob& b, int P, hipStream_t st, bool wide, bool spread) {
-  if (P > 4 && !spread) {  // batches: a workgroup per cloud fills the chip
+void hash_build_pair(const HashJob& a, const HashJob& b, int P, hipStream_t st, bool wide, HashForm form) {
+  if (form == HashForm::kSingle || (P > 4 && form == HashForm::kAuto)) {  // batches: a workgroup per cloud fills the chip
     HashPair hp;
     hp.j[0] = a;
     hp.j[1] = b;
@@ -2235,7 +2235,7 @@ hipError_t od_wait_hashes(OdBuffers& b, hipStream_t st) {
   return hipStreamWaitEvent(st, b.hash_done, 0);
 }
 
-void od_build_hashes(const OdBuffers& b, int buf, hipStream_t st) {
+void od_build_hashes(const OdBuffers& b, int buf, hipStream_t st, HashForm form) {
   HashJob jc;
   jc.pts = b.lastC + (size_t)buf * b.P * b.capC;
   jc.pts_stride = b.capC;
@@ -2269,12 +2269,45 @@ void od_build_hashes(const OdBuffers& b, int buf, hipStream_t st) {
   js.tmax = b.tS;
   js.chunks = b.cS + (size_t)buf * b.P * 2 * chunks_of(b.capS);
   js.fine = b.fS + (size_t)buf * b.P * 2 * subs_of(b.capS);
-  hash_build_pair(jc, js, b.P, st, true);
+  hash_build_pair(jc, js, b.P, st, true, form);
 }
 
 }  // namespace loam
 
 namespace loam {
+// One association round's launches (od_solve's `it % 5 == 0`, Q10; the diagnostic hook
+// loam_dev_od_assoc_run): the queries' TransformToStart (and nearest neighbour) where it is a launch
+// of its own, then k_od_assoc.  it: the L-M iteration (0: the unseeded round); count: the profiling
+// instantiations (the work counters); ga_wg: the association's workgroups per problem, 0 = the rule below
+void od_assoc_round(const OdBuffers& b, const FeatView& f, int last_buf, int it, bool count, hipStream_t st, int ga_wg) {
+  const int P = b.P;
+  const Tuning& tn = b.tune;
+  // one wave per query when the batch is small (streaming: TransformToStart in the wave), 64
+  // waves per problem otherwise (the queries transformed by k_od_sel first)
+  // (batches: about nine query capacity per wave — 64 waves per VLP-16 problem, 256 per HDL-64E
+  // one; round 5, config 5: 64 -> 256 waves took k_od_assoc 4.09 -> 2.48 ms/step, while at
+  // VLP-16 batches 32 / 128 / 256 measured equal / slower)
+  const int ga = ga_wg > 0 ? ga_wg
+                 : P >= 64 ? (tn.od_assoc_wg > 0 ? tn.od_assoc_wg : std::max(16, std::min(1024, b.cap_q / 9)))
+                           : (b.cap_q + kAsWaves - 1) / kAsWaves;
+  if (P >= tn.od_sel_min) {
+    // the nearest neighbour on a lane per query in the k_od_sel launch (od_nn_lane: 1 the seeded
+    // rounds, 2 every round; iteration 0 is the unseeded one) for batches of od_nn_lane_min or more
+    const int nnl = P >= tn.od_nn_lane_min && (tn.od_nn_lane == 2 || (tn.od_nn_lane == 1 && it > 0)) ? 1 : 0;
+    if (!nnl) hipLaunchKernelGGL(k_od_sel, dim3(b.gq, P), dim3(kOdThreads), 0, st, b, f);
+    else if (count) hipLaunchKernelGGL(k_od_sel_nn<true>, dim3(b.gq, P), dim3(kOdThreads), 0, st, b, f, last_buf);
+    else hipLaunchKernelGGL(k_od_sel_nn<false>, dim3(b.gq, P), dim3(kOdThreads), 0, st, b, f, last_buf);
+    if (count) {
+      hipLaunchKernelGGL((k_od_assoc<true, false>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, nnl);
+    } else {
+      hipLaunchKernelGGL((k_od_assoc<false, false>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, nnl);
+    }
+  } else {
+    if (count) hipLaunchKernelGGL((k_od_assoc<true, true>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, 0);
+    else hipLaunchKernelGGL((k_od_assoc<false, true>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, 0);
+  }
+}
+
 void od_solve(const OdBuffers& b, const FeatView& f, int last_buf, hipStream_t st, Prof* prof, bool device_fini) {
   const int P = b.P;
   auto mark = [&](const char* n) { if (prof) prof->mark(n); };
@@ -2288,29 +2321,7 @@ void od_solve(const OdBuffers& b, const FeatView& f, int last_buf, hipStream_t s
   }
   for (int it = 0; it < (gls > 0 ? 0 : b.max_iter); ++it) {
     if (it % 5 == 0) {  // Q10
-      // one wave per query when the batch is small (streaming: TransformToStart in the wave), 64
-      // waves per problem otherwise (the queries transformed by k_od_sel first)
-      // (batches: about nine query capacity per wave — 64 waves per VLP-16 problem, 256 per HDL-64E
-      // one; round 5, config 5: 64 -> 256 waves took k_od_assoc 4.09 -> 2.48 ms/step, while at
-      // VLP-16 batches 32 / 128 / 256 measured equal / slower)
-      const int ga = P >= 64 ? (tn.od_assoc_wg > 0 ? tn.od_assoc_wg : std::max(16, std::min(1024, b.cap_q / 9)))
-                             : (b.cap_q + kAsWaves - 1) / kAsWaves;
-      if (P >= tn.od_sel_min) {
-        // the nearest neighbour on a lane per query in the k_od_sel launch (od_nn_lane: 1 the seeded
-        // rounds, 2 every round; iteration 0 is the unseeded one) for batches of od_nn_lane_min or more
-        const int nnl = P >= tn.od_nn_lane_min && (tn.od_nn_lane == 2 || (tn.od_nn_lane == 1 && it > 0)) ? 1 : 0;
-        if (!nnl) hipLaunchKernelGGL(k_od_sel, dim3(b.gq, P), dim3(kOdThreads), 0, st, b, f);
-        else if (prof) hipLaunchKernelGGL(k_od_sel_nn<true>, dim3(b.gq, P), dim3(kOdThreads), 0, st, b, f, last_buf);
-        else hipLaunchKernelGGL(k_od_sel_nn<false>, dim3(b.gq, P), dim3(kOdThreads), 0, st, b, f, last_buf);
-        if (prof) {
-          hipLaunchKernelGGL((k_od_assoc<true, false>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, nnl);
-        } else {
-          hipLaunchKernelGGL((k_od_assoc<false, false>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, nnl);
-        }
-      } else {
-        if (prof) hipLaunchKernelGGL((k_od_assoc<true, true>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, 0);
-        else hipLaunchKernelGGL((k_od_assoc<false, true>), dim3(ga, P), dim3(kAsThreads), 0, st, b, f, last_buf, 0);
-      }
+      od_assoc_round(b, f, last_buf, it, prof != nullptr, st);
       mark("k_od_assoc");
     }
     if (P <= tn.od_small_max) {  // measured: the fused step loses for large batches (its serial tail)
@@ -2507,6 +2518,196 @@ extern "C" int loam_dev_od_nn_destroy(loam_dev_od_nn* h) {
   (void)hipSetDevice(h->device);
   if (h->st) (void)hipStreamSynchronize(h->st);
   dev_od_nn_free(h);
+  return LOAM_OK;
+}
+
+// ---------------------------------------------------------------- the association round's diagnostic hook
+// Host code only: the product's od_alloc, od_build_hashes and od_assoc_round on a caller's problems.
+struct loam_dev_od_assoc {
+  int device = 0;
+  hipStream_t st = nullptr;
+  loam::OdBuffers b;  // od_alloc for LOAM_DEV_OD_ASSOC_MAX_P problems; a job of P problems uses it as [P]
+  float4 *sharp = nullptr, *flat = nullptr;  // [MAX_P][LOAM_DEV_OD_ASSOC_MAX_QUERIES] each
+  int *cnt = nullptr, *nfull = nullptr;      // [MAX_P][4], [MAX_P]
+};
+
+namespace {
+// rings per od_alloc: the query capacity (36 per ring) holds both kinds' LOAM_DEV_OD_ASSOC_MAX_QUERIES,
+// which also makes the corner capacity (120 per ring) more than LOAM_DEV_OD_ASSOC_MAX_CLOUD
+constexpr int kDevAssocRings = (2 * LOAM_DEV_OD_ASSOC_MAX_QUERIES + loam::kSharpPerRing + loam::kFlatPerRing - 1) /
+                               (loam::kSharpPerRing + loam::kFlatPerRing);
+static_assert(loam::kLessSharpPerRing * kDevAssocRings >= LOAM_DEV_OD_ASSOC_MAX_CLOUD, "corner capacity");
+
+void dev_od_assoc_free(loam_dev_od_assoc* h) {
+  loam::od_free(h->b);
+  void* ptrs[] = {h->sharp, h->flat, h->cnt, h->nfull};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  if (h->st) (void)hipStreamDestroy(h->st);
+  delete h;
+}
+}  // namespace
+
+extern "C" int loam_dev_od_assoc_create(int device, loam_dev_od_assoc** out) {
+  if (!out) return LOAM_E_INVAL;
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return LOAM_E_HIP;  // (no CPU path, as loam_create)
+  if (device < 0 || device >= ndev) return LOAM_E_INVAL;
+  if (hipSetDevice(device) != hipSuccess) return LOAM_E_HIP;
+  loam_dev_od_assoc* h = new loam_dev_od_assoc();
+  h->device = device;
+  const size_t MP = LOAM_DEV_OD_ASSOC_MAX_P, Q = LOAM_DEV_OD_ASSOC_MAX_QUERIES;
+  hipError_t e = loam::od_alloc(h->b, (int)MP, kDevAssocRings, LOAM_DEV_OD_ASSOC_MAX_CLOUD, 1);
+  loam::DevAlloc A;
+  if (e == hipSuccess) {
+    A(&h->sharp, MP * Q * sizeof(float4));
+    A(&h->flat, MP * Q * sizeof(float4));
+    A(&h->cnt, MP * 4 * sizeof(int));
+    A(&h->nfull, MP * sizeof(int));
+    e = A.err;
+  }
+  if (e == hipSuccess) e = hipMemset(h->nfull, 0, MP * sizeof(int));
+  if (e == hipSuccess) e = hipStreamCreate(&h->st);
+  if (e != hipSuccess) {
+    dev_od_assoc_free(h);
+    return e == hipErrorOutOfMemory ? LOAM_E_NOMEM : LOAM_E_HIP;
+  }
+  *out = h;
+  return LOAM_OK;
+}
+
+extern "C" int loam_dev_od_assoc_run(loam_dev_od_assoc* h, const loam_dev_od_assoc_job* job, int32_t* ind,
+                                     int32_t* mono, int32_t* rstart, int32_t* counters) {
+  using namespace loam;
+  if (!h || !job || !ind || !mono || !rstart || !counters) return LOAM_E_INVAL;
+  const int P = job->P;
+  if (!job->prob || P < 1 || P > LOAM_DEV_OD_ASSOC_MAX_P) return LOAM_E_INVAL;
+  Tuning tn;
+  if (!tn.set("od_sel_min", job->od_sel_min) || !tn.set("od_nn_lane", job->od_nn_lane) ||
+      !tn.set("od_nn_lane_min", job->od_nn_lane_min) || !tn.set("od_win_mono", job->od_win_mono) ||
+      !tn.set("od_win_mono_min", job->od_win_mono_min))
+    return LOAM_E_INVAL;
+  if (job->grid < 0 || job->grid > LOAM_DEV_OD_ASSOC_MAX_GRID || job->count < 0 || job->count > 1 ||
+      job->hash_form < 0 || job->hash_form > 2)
+    return LOAM_E_INVAL;
+  bool seeded = false;
+  int Q = 0;
+  for (int p = 0; p < P; ++p) {
+    const loam_dev_od_assoc_problem& pr = job->prob[p];
+    const float* cl[2] = {pr.corner_last, pr.surf_last};
+    const float* qs[2] = {pr.corner_q, pr.surf_q};
+    const int32_t* sd[2] = {pr.corner_seeds, pr.surf_seeds};
+    const int n[2] = {pr.n_corner_last, pr.n_surf_last}, nq[2] = {pr.n_corner_q, pr.n_surf_q};
+    for (int k = 0; k < 2; ++k) {
+      if (!cl[k] || n[k] < 1 || n[k] > LOAM_DEV_OD_ASSOC_MAX_CLOUD) return LOAM_E_INVAL;
+      if (nq[k] < 0 || nq[k] > LOAM_DEV_OD_ASSOC_MAX_QUERIES || (nq[k] > 0 && !qs[k])) return LOAM_E_INVAL;
+      for (int i = 0; i < n[k]; ++i) {  // kRingTab holds rings 0 .. 63 (and two past the last)
+        const float r = cl[k][4 * i + 3];
+        if (!(r >= 0.0f && r < 64.0f)) return LOAM_E_INVAL;
+      }
+      for (int i = 0; i < nq[k]; ++i) {  // TransformToStart's s is 10 times the fraction: zero here
+        const float w = qs[k][4 * i + 3];
+        if (!(w >= 0.0f && w < 65536.0f && w == (float)(int)w)) return LOAM_E_INVAL;
+      }
+      if (sd[k]) {
+        seeded = true;
+        for (int i = 0; i < 3 * nq[k]; ++i)
+          if (sd[k][i] < -1 || sd[k][i] >= n[k]) return LOAM_E_INVAL;
+      }
+    }
+    if (nq[0] + nq[1] < 1) return LOAM_E_INVAL;
+    Q = std::max(Q, nq[0] + nq[1]);
+  }
+  // the handle's buffers as those of P problems (every array of OdBuffers is [.][P][...] or [P][...])
+  OdBuffers b = h->b;
+  b.P = P;
+  b.tune = tn;
+  const int cq = b.cap_q;
+  hipStream_t st = h->st;
+  std::vector<int> hind((size_t)P * 3 * cq, LOAM_DEV_OD_ASSOC_SENTINEL), hist((size_t)P * kOdStateInts, 0),
+      hcnt((size_t)P * 4, 0), hnl((size_t)P * kOdBufs * 2, 0);
+  for (int p = 0; p < P; ++p) {
+    const loam_dev_od_assoc_problem& pr = job->prob[p];
+    const int nc = pr.n_corner_q, ns = pr.n_surf_q;
+    if (seeded)
+      for (int k = 0; k < 3; ++k) {
+        int* row = hind.data() + ((size_t)p * 3 + k) * cq;
+        for (int q = 0; q < nc; ++q) row[q] = pr.corner_seeds ? pr.corner_seeds[3 * q + k] : -1;
+        for (int q = 0; q < ns; ++q) row[nc + q] = pr.surf_seeds ? pr.surf_seeds[3 * q + k] : -1;
+      }
+    int* ist = hist.data() + (size_t)p * kOdStateInts;
+    ist[kIsCornerLastNum] = pr.n_corner_last;
+    ist[kIsSurfLastNum] = pr.n_surf_last;
+    ist[kIsActive] = 1;
+    ist[kIsIters] = seeded ? 5 : 0;
+    hcnt[(size_t)p * 4 + 0] = nc;
+    hcnt[(size_t)p * 4 + 2] = ns;
+    hnl[((size_t)p * kOdBufs + 0) * 2 + 0] = pr.n_corner_last;  // Last buffer 0
+    hnl[((size_t)p * kOdBufs + 0) * 2 + 1] = pr.n_surf_last;
+  }
+  auto up = [&](void* d, const void* s, size_t bytes) {
+    return bytes ? hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+  };
+  hipError_t e = hipSetDevice(h->device);
+  if (e == hipSuccess) e = hipMemsetAsync(b.state, 0, (size_t)P * kOdStateFloats * sizeof(float), st);  // transform 0
+  if (e == hipSuccess) e = up(b.istate, hist.data(), hist.size() * sizeof(int));
+  if (e == hipSuccess) e = up(b.ind, hind.data(), hind.size() * sizeof(int));
+  if (e == hipSuccess) e = up(b.nlast, hnl.data(), hnl.size() * sizeof(int));
+  if (e == hipSuccess) e = up(h->cnt, hcnt.data(), hcnt.size() * sizeof(int));
+  for (int p = 0; p < P && e == hipSuccess; ++p) {
+    const loam_dev_od_assoc_problem& pr = job->prob[p];
+    e = up(b.lastC + (size_t)p * b.capC, pr.corner_last, (size_t)pr.n_corner_last * sizeof(float4));
+    if (e == hipSuccess) e = up(b.lastS + (size_t)p * b.capS, pr.surf_last, (size_t)pr.n_surf_last * sizeof(float4));
+    if (e == hipSuccess)
+      e = up(h->sharp + (size_t)p * LOAM_DEV_OD_ASSOC_MAX_QUERIES, pr.corner_q, (size_t)pr.n_corner_q * sizeof(float4));
+    if (e == hipSuccess)
+      e = up(h->flat + (size_t)p * LOAM_DEV_OD_ASSOC_MAX_QUERIES, pr.surf_q, (size_t)pr.n_surf_q * sizeof(float4));
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    return LOAM_E_HIP;
+  }
+  FeatView f;
+  f.sharp = h->sharp;
+  f.flat = h->flat;
+  f.lsharp = f.lflat = f.full = nullptr;  // (the association reads the queries only)
+  f.sharp_stride = f.flat_stride = LOAM_DEV_OD_ASSOC_MAX_QUERIES;
+  f.lsharp_stride = f.lflat_stride = f.full_stride = 0;
+  f.cnt = h->cnt;
+  f.cnt_stride = 4;
+  f.nfull_p = h->nfull;
+  f.nfull_stride = 1;
+  od_build_hashes(b, 0, st, static_cast<HashForm>(job->hash_form));  // (0 .. 2: HashForm's values)
+  od_assoc_round(b, f, 0, seeded ? 5 : 0, job->count != 0, st, job->grid);
+  e = hipGetLastError();
+  auto down = [&](void* d, const void* s, size_t bytes) { return hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, st); };
+  std::vector<int> hrs((size_t)P * 2 * kRingTab), hmono((size_t)P * 2);
+  if (e == hipSuccess) e = down(hind.data(), b.ind, hind.size() * sizeof(int));
+  if (e == hipSuccess) e = down(hist.data(), b.istate, hist.size() * sizeof(int));
+  if (e == hipSuccess) e = down(hmono.data(), b.mono, hmono.size() * sizeof(int));      // (Last buffer 0: [P][2])
+  if (e == hipSuccess) e = down(hrs.data(), b.rstart, hrs.size() * sizeof(int));        // ([P][2][kRingTab])
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return LOAM_E_HIP;
+  for (int p = 0; p < P; ++p)  // (a capacity or LOAM_CHECK flag of the kernels: none may be raised here)
+    if (hist[(size_t)p * kOdStateInts + kIsErr] != 0) return LOAM_E_HIP;
+  for (int p = 0; p < P; ++p) {
+    for (int k = 0; k < 3; ++k)
+      for (int q = 0; q < Q; ++q) ind[((size_t)p * 3 + k) * Q + q] = hind[((size_t)p * 3 + k) * cq + q];
+    counters[2 * p] = hist[(size_t)p * kOdStateInts + kIsGathered];
+    counters[2 * p + 1] = hist[(size_t)p * kOdStateInts + kIsBoxes];
+  }
+  std::memcpy(mono, hmono.data(), hmono.size() * sizeof(int));
+  std::memcpy(rstart, hrs.data(), hrs.size() * sizeof(int));
+  return LOAM_OK;
+}
+
+extern "C" int loam_dev_od_assoc_destroy(loam_dev_od_assoc* h) {
+  if (!h) return LOAM_E_INVAL;
+  (void)hipSetDevice(h->device);
+  if (h->st) (void)hipStreamSynchronize(h->st);
+  dev_od_assoc_free(h);
   return LOAM_OK;
 }
 

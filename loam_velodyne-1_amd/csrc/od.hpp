@@ -141,15 +141,20 @@ struct OdBuffers {
 // both clouds' indexes: a workgroup per cloud for batches, a grid per cloud for P <= 4
 // wide: 1024-thread workgroups (the odometry Last clouds: 0.28 -> 0.19 ms/step at batch 1024), else
 // 512 (the map clouds: 0.27 -> 0.26; 1024 measured 0.31)
-// spread: the grid per cloud for any P (many large clouds: loam_map_localize's FromMap beyond the LDS
-// counters, where a cloud's single workgroup is a long global-atomic counting sort)
-void hash_build_pair(const HashJob& a, const HashJob& b, int P, hipStream_t st, bool wide, bool spread = false);
+// form: kAuto that rule; kGrid the grid per cloud for any P (many large clouds: loam_map_localize's
+// FromMap beyond the LDS counters, where a cloud's single workgroup is a long global-atomic counting
+// sort); kSingle the workgroup per cloud for any P (the diagnostic hook loam_dev_od_assoc_run: the two
+// forms compute the mono flag, the ring starts and the boxes by different code)
+enum class HashForm { kAuto = 0, kGrid = 1, kSingle = 2 };
+void hash_build_pair(const HashJob& a, const HashJob& b, int P, hipStream_t st, bool wide,
+                     HashForm form = HashForm::kAuto);
 
 __global__ void k_od_end(OdBuffers b, FeatView f, int dst, int mode, int do_full);
 
 hipError_t od_alloc(OdBuffers& b, int P, int R, int cap_pts, int max_iter);  // on failure: freed, b empty
 void od_free(OdBuffers& b);
-void od_build_hashes(const OdBuffers& b, int buf, hipStream_t st);
+// form: hash_build_pair's (kAuto: every product caller)
+void od_build_hashes(const OdBuffers& b, int buf, hipStream_t st, HashForm form = HashForm::kAuto);
 // od_build_hashes on `side` after the work enqueued on st so far (b.hash_pending until od_wait_hashes)
 hipError_t od_build_hashes_deferred(OdBuffers& b, int buf, hipStream_t st, hipStream_t side);
 hipError_t od_wait_hashes(OdBuffers& b, hipStream_t st);
@@ -157,6 +162,11 @@ hipError_t od_wait_hashes(OdBuffers& b, hipStream_t st);
 // device_fini: the pose accumulation (k_od_fini) on the device; the streaming path does it on the host
 void od_solve(const OdBuffers& b, const FeatView& f, int last_buf, hipStream_t st, Prof* prof = nullptr,
               bool device_fini = true);
+// the launches of one association round of od_solve (iteration it, it % 5 == 0) and of the diagnostic
+// hook loam_dev_od_assoc_run; count: the profiling instantiations; ga_wg: k_od_assoc's workgroups per
+// problem, 0 = od_solve's rule
+void od_assoc_round(const OdBuffers& b, const FeatView& f, int last_buf, int it, bool count, hipStream_t st,
+                    int ga_wg = 0);
 // the pose accumulation alone (k_od_fini), for a caller that runs it beside TransformToEnd
 void od_fini(const OdBuffers& b, const FeatView& f, hipStream_t st);
 

@@ -351,7 +351,7 @@ hipError_t mp_score_index(MpScore& S, MpBuffers& s, MapIo& io, int nC, int total
   HashJob hs = hc;
   hs.pts = s.vin + nC; hs.count = S.cnt + 1;
   hs.start = S.start + (S.idx_T + 1); hs.fill = S.fill + S.idx_T; hs.out = S.out + nC; hs.tsize = S.cnt + 3;
-  hash_build_pair(hc, hs, 1, st, false, true);
+  hash_build_pair(hc, hs, 1, st, false, HashForm::kGrid);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (prof) prof->mark("score_index");

@@ -652,6 +652,83 @@ struct OdOut {
   int published = 0;
 };
 
+// The corner association of one query (:478-527): the nearest CornerLast point (below 25 m2) and the
+// closest point of another ring within the index walks from it, which stop at the first ring beyond
+// +-2.5.  fwdEnd: the forward walk's end (Q11, see od_lm).  -1 where there is none.
+void od_assoc_corner(const KdTree& kd, const std::vector<P>& CL, const P& pointSel, int fwdEnd,
+                     int& closestPointInd, int& minPointInd2) {
+  int nnI[2];  // k = 1 results (one spare slot keeps -Warray-bounds provable)
+  float nnD[2];
+  closestPointInd = -1;
+  minPointInd2 = -1;
+  int got = kd.knn(pointSel.x, pointSel.y, pointSel.z, 1, nnI, nnD);
+  if (got > 0 && D(nnD[0]) < 25) {
+    closestPointInd = nnI[0];
+    int closestPointScan = (int)CL[closestPointInd].intensity;
+    float minPointSqDis2 = 25;
+    for (int j = closestPointInd + 1; j < fwdEnd; ++j) {
+      if (D((int)CL[j].intensity) > closestPointScan + 2.5) break;
+      float pointSqDis = (CL[j].x - pointSel.x) * (CL[j].x - pointSel.x) +
+                         (CL[j].y - pointSel.y) * (CL[j].y - pointSel.y) +
+                         (CL[j].z - pointSel.z) * (CL[j].z - pointSel.z);
+      if ((int)CL[j].intensity > closestPointScan && pointSqDis < minPointSqDis2) {
+        minPointSqDis2 = pointSqDis;
+        minPointInd2 = j;
+      }
+    }
+    for (int j = closestPointInd - 1; j >= 0; --j) {
+      if (D((int)CL[j].intensity) < closestPointScan - 2.5) break;
+      float pointSqDis = (CL[j].x - pointSel.x) * (CL[j].x - pointSel.x) +
+                         (CL[j].y - pointSel.y) * (CL[j].y - pointSel.y) +
+                         (CL[j].z - pointSel.z) * (CL[j].z - pointSel.z);
+      if ((int)CL[j].intensity < closestPointScan && pointSqDis < minPointSqDis2) {
+        minPointSqDis2 = pointSqDis;
+        minPointInd2 = j;
+      }
+    }
+  }
+}
+
+// The surface association of one query (:590-650): the nearest SurfLast point, the closest point of
+// its ring side (forward the same or a lower ring, backward the same or a higher one: min2) and of
+// the other rings (min3) within the same walks.
+void od_assoc_surf(const KdTree& kd, const std::vector<P>& SL, const P& pointSel, int fwdEnd, int& closestPointInd,
+                   int& minPointInd2, int& minPointInd3) {
+  int nnI[2];
+  float nnD[2];
+  closestPointInd = -1;
+  minPointInd2 = -1;
+  minPointInd3 = -1;
+  int got = kd.knn(pointSel.x, pointSel.y, pointSel.z, 1, nnI, nnD);
+  if (got > 0 && D(nnD[0]) < 25) {
+    closestPointInd = nnI[0];
+    int closestPointScan = (int)SL[closestPointInd].intensity;
+    float minPointSqDis2 = 25, minPointSqDis3 = 25;
+    for (int j = closestPointInd + 1; j < fwdEnd; ++j) {
+      if (D((int)SL[j].intensity) > closestPointScan + 2.5) break;
+      float pointSqDis = (SL[j].x - pointSel.x) * (SL[j].x - pointSel.x) +
+                         (SL[j].y - pointSel.y) * (SL[j].y - pointSel.y) +
+                         (SL[j].z - pointSel.z) * (SL[j].z - pointSel.z);
+      if ((int)SL[j].intensity <= closestPointScan) {
+        if (pointSqDis < minPointSqDis2) { minPointSqDis2 = pointSqDis; minPointInd2 = j; }
+      } else {
+        if (pointSqDis < minPointSqDis3) { minPointSqDis3 = pointSqDis; minPointInd3 = j; }
+      }
+    }
+    for (int j = closestPointInd - 1; j >= 0; --j) {
+      if (D((int)SL[j].intensity) < closestPointScan - 2.5) break;
+      float pointSqDis = (SL[j].x - pointSel.x) * (SL[j].x - pointSel.x) +
+                         (SL[j].y - pointSel.y) * (SL[j].y - pointSel.y) +
+                         (SL[j].z - pointSel.z) * (SL[j].z - pointSel.z);
+      if ((int)SL[j].intensity >= closestPointScan) {
+        if (pointSqDis < minPointSqDis2) { minPointSqDis2 = pointSqDis; minPointInd2 = j; }
+      } else {
+        if (pointSqDis < minPointSqDis3) { minPointSqDis3 = pointSqDis; minPointInd3 = j; }
+      }
+    }
+  }
+}
+
 // the L-M of :465-828
 void od_lm(const Cfg& cfg, OdState& s, const std::vector<P>& sharp, const std::vector<P>& flat) {
   float* transform = s.transform;
@@ -662,8 +739,6 @@ void od_lm(const Cfg& cfg, OdState& s, const std::vector<P>& sharp, const std::v
       ind3s(surfPointsFlatNum, -1);
   std::vector<P> cloudOri, coeffSel;  // cleared once per frame (:458-459): rows accumulate (Q12)
   std::vector<int> nanIdx;
-  int nnI[2];  // k = 1 results (one spare slot keeps -Warray-bounds provable)
-  float nnD[2];
   const std::vector<P>& CL = s.cornerLast;
   const std::vector<P>& SL = s.surfLast;
   for (int iterCount = 0; iterCount < cfg.od_max_iter; ++iterCount) {
@@ -677,37 +752,12 @@ void od_lm(const Cfg& cfg, OdState& s, const std::vector<P>& sharp, const std::v
         // :476 removeNaNFromPointCloud on the dense CornerLast: an O(C) index fill per query
         nanIdx.resize(CL.size());
         std::iota(nanIdx.begin(), nanIdx.end(), 0);
-        int closestPointInd = -1, minPointInd2 = -1;
-        int got = s.kdCorner.knn(pointSel.x, pointSel.y, pointSel.z, 1, nnI, nnD);
-        if (got > 0 && D(nnD[0]) < 25) {
-          closestPointInd = nnI[0];
-          int closestPointScan = (int)CL[closestPointInd].intensity;
-          float minPointSqDis2 = 25;
-          // Q11: the reference bounds the forward window by this sweep's cornerPointsSharpNum
-          // (:486), reading past CornerLast when that exceeds it (UB).  Defined here, as in the
-          // engine (od.hip k_od_assoc), as min(cornerPointsSharpNum, |CornerLast|).
-          const int fwdEnd = std::min(cornerPointsSharpNum, (int)CL.size());
-          for (int j = closestPointInd + 1; j < fwdEnd; ++j) {
-            if (D((int)CL[j].intensity) > closestPointScan + 2.5) break;
-            float pointSqDis = (CL[j].x - pointSel.x) * (CL[j].x - pointSel.x) +
-                               (CL[j].y - pointSel.y) * (CL[j].y - pointSel.y) +
-                               (CL[j].z - pointSel.z) * (CL[j].z - pointSel.z);
-            if ((int)CL[j].intensity > closestPointScan && pointSqDis < minPointSqDis2) {
-              minPointSqDis2 = pointSqDis;
-              minPointInd2 = j;
-            }
-          }
-          for (int j = closestPointInd - 1; j >= 0; --j) {
-            if (D((int)CL[j].intensity) < closestPointScan - 2.5) break;
-            float pointSqDis = (CL[j].x - pointSel.x) * (CL[j].x - pointSel.x) +
-                               (CL[j].y - pointSel.y) * (CL[j].y - pointSel.y) +
-                               (CL[j].z - pointSel.z) * (CL[j].z - pointSel.z);
-            if ((int)CL[j].intensity < closestPointScan && pointSqDis < minPointSqDis2) {
-              minPointSqDis2 = pointSqDis;
-              minPointInd2 = j;
-            }
-          }
-        }
+        // Q11: the reference bounds the forward window by this sweep's cornerPointsSharpNum
+        // (:486), reading past CornerLast when that exceeds it (UB).  Defined here, as in the
+        // engine (od.hip k_od_assoc), as min(cornerPointsSharpNum, |CornerLast|).
+        const int fwdEnd = std::min(cornerPointsSharpNum, (int)CL.size());
+        int closestPointInd, minPointInd2;
+        od_assoc_corner(s.kdCorner, CL, pointSel, fwdEnd, closestPointInd, minPointInd2);
         ind1c[i] = (float)closestPointInd;
         ind2c[i] = (float)minPointInd2;
       }
@@ -748,37 +798,10 @@ void od_lm(const Cfg& cfg, OdState& s, const std::vector<P>& sharp, const std::v
       transform_to_start(s, flat[i], pointSel);
       if (iterCount % 5 == 0) {
         s.queries++;
-        int got = s.kdSurf.knn(pointSel.x, pointSel.y, pointSel.z, 1, nnI, nnD);
-        int closestPointInd = -1, minPointInd2 = -1, minPointInd3 = -1;
-        if (got > 0 && D(nnD[0]) < 25) {
-          closestPointInd = nnI[0];
-          int closestPointScan = (int)SL[closestPointInd].intensity;
-          float minPointSqDis2 = 25, minPointSqDis3 = 25;
-          // Q11 (:598): same clamp, min(surfPointsFlatNum, |SurfLast|)
-          const int fwdEnd = std::min(surfPointsFlatNum, (int)SL.size());
-          for (int j = closestPointInd + 1; j < fwdEnd; ++j) {
-            if (D((int)SL[j].intensity) > closestPointScan + 2.5) break;
-            float pointSqDis = (SL[j].x - pointSel.x) * (SL[j].x - pointSel.x) +
-                               (SL[j].y - pointSel.y) * (SL[j].y - pointSel.y) +
-                               (SL[j].z - pointSel.z) * (SL[j].z - pointSel.z);
-            if ((int)SL[j].intensity <= closestPointScan) {
-              if (pointSqDis < minPointSqDis2) { minPointSqDis2 = pointSqDis; minPointInd2 = j; }
-            } else {
-              if (pointSqDis < minPointSqDis3) { minPointSqDis3 = pointSqDis; minPointInd3 = j; }
-            }
-          }
-          for (int j = closestPointInd - 1; j >= 0; --j) {
-            if (D((int)SL[j].intensity) < closestPointScan - 2.5) break;
-            float pointSqDis = (SL[j].x - pointSel.x) * (SL[j].x - pointSel.x) +
-                               (SL[j].y - pointSel.y) * (SL[j].y - pointSel.y) +
-                               (SL[j].z - pointSel.z) * (SL[j].z - pointSel.z);
-            if ((int)SL[j].intensity >= closestPointScan) {
-              if (pointSqDis < minPointSqDis2) { minPointSqDis2 = pointSqDis; minPointInd2 = j; }
-            } else {
-              if (pointSqDis < minPointSqDis3) { minPointSqDis3 = pointSqDis; minPointInd3 = j; }
-            }
-          }
-        }
+        // Q11 (:598): same clamp, min(surfPointsFlatNum, |SurfLast|)
+        const int fwdEnd = std::min(surfPointsFlatNum, (int)SL.size());
+        int closestPointInd, minPointInd2, minPointInd3;
+        od_assoc_surf(s.kdSurf, SL, pointSel, fwdEnd, closestPointInd, minPointInd2, minPointInd3);
         ind1s[i] = (float)closestPointInd;
         ind2s[i] = (float)minPointInd2;
         ind3s[i] = (float)minPointInd3;
@@ -1727,6 +1750,22 @@ int oracle_knn(const float* pts, int n, const float* q, int nq, int k, int* idx,
   for (int i = 0; i < nq; ++i) {
     int got = t.knn(q[4 * i], q[4 * i + 1], q[4 * i + 2], k, idx + i * k, d + i * k);
     for (int j = got; j < k; ++j) { idx[i * k + j] = -1; d[i * k + j] = INFINITY; }
+  }
+  return 0;
+}
+// the association of od_lm (od_assoc_corner: kind 0, od_assoc_surf: kind 1) of nq queries (TransformToStart
+// already applied) against a caller's Last cloud with the forward walk's end fwd_end (Q11: the caller's
+// min(queries of the kind, n)); ind [nq][3]: ind1, ind2, ind3 (corner: ind3 = -1).  -1 for bad arguments
+int oracle_od_assoc(const float* cloud, int n, const float* q, int nq, int kind, int fwd_end, int* ind) {
+  if (!cloud || !q || !ind || n < 1 || nq < 0 || kind < 0 || kind > 1 || fwd_end < 0 || fwd_end > n) return -1;
+  std::vector<P> L((const P*)cloud, (const P*)cloud + n);
+  KdTree t;
+  t.build(L);
+  for (int i = 0; i < nq; ++i) {
+    const P sel{q[4 * i], q[4 * i + 1], q[4 * i + 2], q[4 * i + 3]};
+    ind[3 * i + 2] = -1;
+    if (kind == 0) od_assoc_corner(t, L, sel, fwd_end, ind[3 * i], ind[3 * i + 1]);
+    else od_assoc_surf(t, L, sel, fwd_end, ind[3 * i], ind[3 * i + 1], ind[3 * i + 2]);
   }
   return 0;
 }

@@ -116,6 +116,8 @@ def lib():
                                         ctypes.c_void_p, ctypes.c_int]
         L.oracle_knn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        L.oracle_od_assoc.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_void_p]
         L.oracle_qr_solve.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_void_p]
         L.oracle_jacobi.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -270,6 +272,19 @@ def maintenance(odom_sum, bef, aft):
     lib().oracle_maintenance(ctypes.byref(Pose6.of(odom_sum)), ctypes.byref(Pose6.of(bef)),
                              ctypes.byref(Pose6.of(aft)), ctypes.byref(out))
     return out.arr()
+
+
+def od_assoc(cloud, queries, kind, fwd_end):
+    """the odometry's association (oracle.cpp od_assoc_corner: kind 0, od_assoc_surf: kind 1) of queries
+    [nq, 4] against the Last cloud [n, 4] (intensity: the ring) with the forward walk's end fwd_end:
+    ind [nq, 3] int32 (ind1, ind2, ind3; -1: none)"""
+    c = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4)
+    q = np.ascontiguousarray(queries, np.float32).reshape(-1, 4)
+    ind = np.full((len(q), 3), -7, np.int32)
+    rc = lib().oracle_od_assoc(c.ctypes.data, len(c), q.ctypes.data, len(q), int(kind), int(fwd_end),
+                               ind.ctypes.data)
+    assert rc == 0, rc
+    return ind
 
 
 def problem(prev, cur, cfg=None):
