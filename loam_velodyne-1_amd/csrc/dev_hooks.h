@@ -48,7 +48,7 @@ int loam_dev_vg_run(loam_dev_vg* h, const loam_dev_vg_job* job, float* out_pts, 
 
 int loam_dev_vg_destroy(loam_dev_vg* h);
 
-/* The mapping 5-NN search (mp.hip: mp_nn_seed_from + knn5_flat, and the plain knn5) on a caller's
+/* The mapping 5-NN search (mp_nn.hpp: mp_nn_seed_from + knn5_flat, and the plain knn5) on a caller's
  * map points and queries: the map's 1 m voxel hash is built by the product's hash build, then one
  * kernel runs both searches on every query from the same start. */
 typedef struct loam_dev_nn5 loam_dev_nn5;

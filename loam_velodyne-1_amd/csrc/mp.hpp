@@ -104,7 +104,7 @@ struct MpBuffers {
   double* ls_part = nullptr;              // [2][kMpSmallGrid][28]
   unsigned long long* ls_flag = nullptr;  // [kMpSmallGrid]
   unsigned long long* ls_epoch = nullptr; // [1]
-  double* rot = nullptr;      // [P][6] cos / sin of the TobeMapped rotation (rot_store in mp.hip)
+  double* rot = nullptr;      // [P][6] cos / sin of the TobeMapped rotation (rot_store in mp_dev.hpp)
   int* nreg = nullptr;
   // the streaming frame's map update (insertion, per-cube VoxelGrid, compaction) deferred to a side
   // stream (mp_frame's `defer`): upd_done is recorded there; the next frame, the surround cloud

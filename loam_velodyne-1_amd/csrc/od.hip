@@ -518,7 +518,7 @@ LOAM_D uint64_t wave_hash_nn(const int* start, const float4* hp, int T, const fl
 // the cells wave_hash_nn's first stage visits (the same box test with the same bound), or kNnLaneNone
 // when none of them lies closer than 1 m — the query is then left to wave_chunk_nn.  The minimum
 // of a set does not depend on the visiting order, so a settled key equals wave_hash_nn's.
-// As knn5_flat (mp.hip): the 27 bucket ranges are loaded together, the non-empty ones listed in
+// As knn5_flat (mp_nn.hpp): the 27 bucket ranges are loaded together, the non-empty ones listed in
 // the lane's LDS column `lst` (stride S, packed as hash_rec) and the concatenated candidates
 // gathered kLaneNnInFlight per step.  A range that does not pack sends the lane through its cells
 // one by one.  work: the candidates evaluated (wave_hash_nn's `total`).

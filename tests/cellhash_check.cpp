@@ -1,6 +1,6 @@
 // The map search's exactness rests on cell_hash (dev_common.hpp, compiled here for the host) never
 // sending two of the 27 cells around any cell to one bucket of a table of >= 64 buckets: the 5-NN
-// list then meets every map point at most once and needs no duplicate test (mp.hip knn5_flat).
+// list then meets every map point at most once and needs no duplicate test (mp_nn.hpp knn5_flat).
 // Checks random cells over +-2^20 and every table size 2^6 .. 2^20; prints "<checked> <collisions>".
 #include <cstdint>
 #include <cstdio>

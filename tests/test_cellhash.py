@@ -1,5 +1,5 @@
 """The 5-NN search lists the buckets of the 27 cells around a query point and offers every point
-of them once, without a duplicate test (loam_velodyne-1_amd/csrc/mp.hip knn5_flat): that needs
+of them once, without a duplicate test (loam_velodyne-1_amd/csrc/mp_nn.hpp knn5_flat): that needs
 cell_hash to put the 27 cells in 27 different buckets for every table size the map hash uses
 (>= 64 buckets).  tests/cellhash_check.cpp compiles the device function for the host and checks
 random cells (signs included) against every table size 2^6 .. 2^20."""

@@ -399,3 +399,47 @@ def test_empty_map_is_no_lm(world, loam):
     assert np.all(res["stack_corner"] > 0) and np.all(res["stack_surf"] > 0)
     e = eng.map_export()
     assert e["corner"].shape[0] == 0 and e["surf"].shape[0] == 0 and e["surround_phase"] == 4
+
+
+def test_working_set_regrowth_equals_fresh_context(world, loam):
+    """The working set of the call grows and is then reused (it never shrinks): on one context, 1
+    candidate on a small sweep, 5 candidates (beyond the floor of 4 the set starts with), 1 candidate
+    on the whole sweep (larger stacks: the sweep's counts are rounded up to 512 corner / 4096 surf
+    points), the small sweep again (the set is kept), then a map with a larger FromMap (its part of the
+    set grows alone: a quarter more than asked, in steps of 4096 points).  Every call = the same call
+    as the first one of a fresh context, bit for bit."""
+    M, rec = world["M"], world["rec"]
+    small_map = dict(M, corner=M["corner"][::4], surf=M["surf"][::4])
+    rng = np.random.default_rng(20261022)
+    near = np.empty((8000, 4), np.float32)  # inside the centre cube, which holds the sensor
+    near[:, :3] = rng.uniform(-20.0, 20.0, (8000, 3)).astype(np.float32)
+    near[:, 3] = rng.uniform(0, 16, 8000).astype(np.float32)
+    big_map = dict(M, surf=np.concatenate([M["surf"], near]))
+    whole = (rec["corner_last"], rec["surf_last"])
+    part = (np.ascontiguousarray(rec["corner_last"][::3]), np.ascontiguousarray(rec["surf_last"][::5]))
+    assert part[0].shape[0] <= 512 < whole[0].shape[0] and part[1].shape[0] <= 4096 < whole[1].shape[0]
+    bef = M["bef"]
+
+    def call(eng, sweep, n):
+        return eng.map_localize(rec["pose"], sweep[0], sweep[1], world["near"][:n], np.tile(bef, (n, 1)))
+
+    def fresh(m):
+        eng = loam.Engine(loam.default_config(**CFG))
+        assert _import(eng, m, bef=bef) == (0, 0)
+        return eng
+
+    G = fresh(small_map)
+    from_small = 0
+    for tag, sweep, n in (("first", part, 1), ("more candidates", part, 5), ("larger sweep", whole, 1),
+                          ("smaller sweep, set kept", part, 1)):
+        got = call(G, sweep, n)
+        _res_eq(got, call(fresh(small_map), sweep, n), tag)
+        assert np.all(got["status"] == loam.LOC_SOLVED), tag
+        from_small = max(from_small, int((got["map_corner"] + got["map_surf"]).max()))
+    assert _import(G, big_map, bef=bef) == (0, 0)
+    got = call(G, whole, 1)
+    from_big = int(got["map_corner"][0] + got["map_surf"][0])
+    print(f"regrowth: FromMap {from_small} -> {from_big} points, iterations {got['iters'][0]}")
+    assert 0 < from_small and from_small + from_small // 4 <= 4096 < from_big  # the FromMap part had to grow
+    _res_eq(got, call(fresh(big_map), whole, 1), "larger FromMap")
+    assert got["status"][0] == loam.LOC_SOLVED

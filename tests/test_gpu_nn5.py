@@ -1,4 +1,4 @@
-"""The mapping 5-NN search (csrc/mp.hip: mp_nn_seed_from + knn5_flat, with its deferred top-5
+"""The mapping 5-NN search (csrc/mp_nn.hpp: mp_nn_seed_from + knn5_flat, with its deferred top-5
 insertion, pending-list overflow and fallback) through the diagnostic hook loam_dev_nn5_run
 (csrc/dev_hooks.h), in the batch form (a lane per query) and the streaming form (a lane group per
 query): bit for bit against the plain knn5 on every query, and against a numpy brute force (float32

@@ -10,7 +10,7 @@ T=$(mktemp -d)
 git -C "$ROOT" archive "$rev" loam_velodyne-1_amd/csrc include | tar -x -C "$T"
 D="$ROOT/loam_velodyne-1_amd"
 mkdir -p "$D/exp/$name.obj"
-for f in sr.hip od.hip mp.hip vg.hip score.hip lanes.hip engine.cpp engine_batch.cpp engine_map.cpp engine_lanes.cpp bag.cpp msg.cpp; do
+for f in sr.hip od.hip mp.hip mp_map.hip mp_loc.hip mp_commit.hip mp_nn5_hook.hip vg.hip score.hip lanes.hip engine.cpp engine_batch.cpp engine_map.cpp engine_lanes.cpp bag.cpp msg.cpp; do
   [ -f "$T/loam_velodyne-1_amd/csrc/$f" ] || continue  # (an older revision lacks the later modules)
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-function \
     -DLOAM_EXPERIMENT_BUILD "$@" -x hip -c "$T/loam_velodyne-1_amd/csrc/$f" -o "$D/exp/$name.obj/$f.o" &
