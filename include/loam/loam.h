@@ -156,6 +156,57 @@ int loam_ring_table_check(uint32_t n_rings, uint32_t n, const float *bound_deg, 
 int loam_ring_table_of_model(const loam_config *cfg, uint32_t *n, float *bound_deg, int32_t *ring);
 int loam_set_ring_table(loam_ctx *ctx, uint32_t n, const float *bound_deg, const int32_t *ring);
 
+/* ---- ring and time from the sweep's own fields (velodyne PointXYZIRT, Ouster, Hesai) ----
+ * A context may read each point's ring, or its ring and its time, from fields of the caller's
+ * records instead of reconstructing them from the geometry.  r = the ring, v = the ring field's
+ * value read unsigned, t = the time field's value.
+ *
+ * A point is kept only if x, y, z are finite; v < ring_map_n (v < n_rings without a map);
+ * r = ring_map[v] (r = v without a map) is not negative; and, with a time field,
+ * tau = (float)((double)t * time_scale + time_bias) is finite with 0 <= tau <= 0.5 (the product and
+ * the sum rounded to double, the result to float).  Every other point is dropped as the reference
+ * drops a point whose scanID is out of range (src/scanRegistration.cpp:257-260).
+ *
+ * Ring only (time_type == LOAM_FIELD_NONE): the ring from the field, the time from the azimuth as
+ * under a ring model: intensity = (float)(r + 0.1 * relTime).
+ * Ring and time: intensity = (float)r + tau (one float addition), and the point's time for the IMU
+ * de-skew is intensity - (float)r, which is tau again: the time the odometry reads back out of the
+ * point (src/laserOdometry.cpp:103, s = 10 * tau for the reference's 0.1 s scan period).  Azimuth,
+ * the sweep's ends and halfPassed are not computed.  A time field without a ring field is not offered.
+ *
+ * loam_point_fields_check (host only, no context): LOAM_OK, or LOAM_E_INVAL with the rule broken in
+ * loam_last_error(): f non-null; ring_type U8 | U16 | U32; time_type NONE | F32 | U32 | F64; each
+ * offset at least 12 and a multiple of its field's size; each field ends at or below byte 65536;
+ * the fields do not overlap; with a time field time_scale and time_bias finite and time_scale != 0;
+ * ring_map == NULL requires ring_map_n == 0; a given map has 1 .. LOAM_RING_MAP_MAX entries, each
+ * in [-1, n_rings), at least one of them >= 0.
+ *
+ * loam_set_point_fields: the context copies the fields and the map; f == NULL returns to the ring
+ * model (or table), which is kept but not consulted while fields are set.  Allowed only while the
+ * context has seen no sweep, as loam_set_ring_table is, and in either order with it; n_rings still
+ * sizes everything.  LOAM_E_NOMEM / LOAM_E_HIP leave the previous state intact.  Every cloud then
+ * handed to the context needs stride_bytes at or above the end of both fields (else the call's or
+ * the lane's LOAM_E_INVAL, as for a bad stride); host clouds are read at any alignment;
+ * loam_lanes_push_device keeps its alignment rules, and its range check covers each field's end. */
+#define LOAM_FIELD_NONE 0
+#define LOAM_FIELD_U8   1
+#define LOAM_FIELD_U16  2
+#define LOAM_FIELD_U32  3
+#define LOAM_FIELD_F32  4
+#define LOAM_FIELD_F64  5
+#define LOAM_RING_MAP_MAX 256
+
+typedef struct {
+  uint32_t ring_type, ring_offset;    /* U8 | U16 | U32; byte offset inside a record */
+  uint32_t time_type, time_offset;    /* NONE | F32 | U32 | F64 */
+  double   time_scale, time_bias;     /* tau = (float)((double)t * time_scale + time_bias), seconds after the sweep's stamp */
+  const int32_t *ring_map;            /* NULL = identity; else ring_map[v] = ring of field value v, or -1 = drop */
+  uint32_t ring_map_n;                /* entries, <= LOAM_RING_MAP_MAX */
+} loam_point_fields;
+
+int loam_point_fields_check(uint32_t n_rings, const loam_point_fields *f);
+int loam_set_point_fields(loam_ctx *ctx, const loam_point_fields *f);
+
 /* = the /imu/data handlers of scanRegistration (src/scanRegistration.cpp:638-660: queue entry, gravity
  * removal, AccumulateIMUShift) and laserMapping (src/laserMapping.cpp:323-335).  quat_xyzw = the
  * sensor_msgs/Imu orientation (x, y, z, w), lin_acc_xyz = linear_acceleration, both float64 as in the

@@ -68,6 +68,15 @@ int loam_pc2_parse(const uint8_t *msg, uint32_t size, loam_pc2 *out);
  * they are at whatever alignment the message gives them. */
 int loam_pc2_cloud(const loam_pc2 *pc, loam_point *scratch, uint32_t scratch_cap, loam_cloud_in *out);
 
+/* the ring and time fields of a serialized PointCloud2, as loam_set_point_fields takes them
+ * (loam.h): ring = the field named "ring" of datatype UINT8, UINT16 or UINT32; time = a field named
+ * "time" (FLOAT32 or FLOAT64: seconds, scale 1, bias 0) or "t" (UINT32: nanoseconds, scale 1e-9,
+ * bias 0), time_type = LOAM_FIELD_NONE when the message has neither; ring_map = NULL.  The caller
+ * may edit scale, bias and map before setting them.  LOAM_E_INVAL when there is no usable ring
+ * field or when x, y, z are not FLOAT32 at offsets 0 / 4 / 8: the fields are read in place from the
+ * message's records (loam_pc2_cloud's zero-copy form); its packing path loses them. */
+int loam_pc2_point_fields(const uint8_t *msg, uint32_t size, loam_point_fields *out);
+
 /* parses a serialized sensor_msgs/Imu: header.stamp, orientation (x, y, z, w), linear_acceleration */
 int loam_imu_parse(const uint8_t *msg, uint32_t size, double *stamp, double quat_xyzw[4], double lin_acc_xyz[3]);
 

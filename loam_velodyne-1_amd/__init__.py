@@ -25,6 +25,9 @@ LOAM_OK, LOAM_E_INVAL, LOAM_E_CAPACITY, LOAM_E_HIP, LOAM_E_NOT_READY, LOAM_E_NOM
 PUB_POSE, PUB_CLOUDS, PUB_FULL = 1, 2, 4
 RING_VLP16, RING_LINEAR = 0, 1
 RING_TABLE_MAX = 64  # LOAM_RING_TABLE_MAX: intervals of a ring table (Engine.set_ring_table)
+# LOAM_FIELD_*: the type of a record's ring or time field (Engine.set_point_fields)
+FIELD_NONE, FIELD_U8, FIELD_U16, FIELD_U32, FIELD_F32, FIELD_F64 = 0, 1, 2, 3, 4, 5
+RING_MAP_MAX = 256   # LOAM_RING_MAP_MAX: entries of a ring map
 
 
 class LoamError(RuntimeError):
@@ -35,6 +38,31 @@ class LoamError(RuntimeError):
 
 class CloudIn(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("count", ctypes.c_uint32), ("stride_bytes", ctypes.c_uint32)]
+
+
+class PointFields(ctypes.Structure):
+    """include/loam/loam.h loam_point_fields: where a record keeps its ring and its time"""
+    _fields_ = [("ring_type", ctypes.c_uint32), ("ring_offset", ctypes.c_uint32),
+                ("time_type", ctypes.c_uint32), ("time_offset", ctypes.c_uint32),
+                ("time_scale", ctypes.c_double), ("time_bias", ctypes.c_double),
+                ("ring_map", ctypes.POINTER(ctypes.c_int32)), ("ring_map_n", ctypes.c_uint32)]
+
+    @staticmethod
+    def of(ring, time=None, ring_map=None):
+        """ring = (type, offset); time = None or (type, offset, scale, bias); ring_map = None or ints
+        (-1 = drop).  The structure keeps the map's storage alive."""
+        f = PointFields()
+        f.ring_type, f.ring_offset = int(ring[0]), int(ring[1])
+        f.time_scale = 1.0
+        if time is not None:
+            f.time_type, f.time_offset = int(time[0]), int(time[1])
+            f.time_scale, f.time_bias = float(time[2]), float(time[3])
+        if ring_map is not None:
+            m = np.ascontiguousarray(ring_map, np.int32).reshape(-1)
+            f._map = m
+            f.ring_map = m.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            f.ring_map_n = len(m)
+        return f
 
 
 class CloudOut(ctypes.Structure):
@@ -211,6 +239,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_scan_registration", "loam_odometry", "loam_mapping", "loam_mapping_surround",
            "loam_maintenance", "loam_chain_sweep",
            "loam_ring_table_check", "loam_ring_table_of_model", "loam_set_ring_table",
+           "loam_point_fields_check", "loam_set_point_fields",
            "loam_batch_upload", "loam_batch_feed", "loam_batch_run", "loam_batch_sync", "loam_batch_download", "loam_batch_lm_info", "loam_batch_features", "loam_map_export", "loam_map_import", "loam_map_localize", "loam_map_score", "loam_get_stats",
            "loam_lanes_open", "loam_lanes_push", "loam_lanes_pull", "loam_lanes_registered", "loam_lanes_map_export",
            "loam_lanes_close", "loam_lanes_imu", "loam_lanes_push_stamped", "loam_lanes_imu_trans",
@@ -221,7 +250,7 @@ EXPORTS = ("loam_config_default", "loam_create", "loam_destroy", "loam_last_erro
            "loam_set_profiling", "loam_get_kernel_times", "loam_set_stream_priority", "loam_set_tuning",
            "loam_get_tuning",
            # include/loam/loam_bag.h: recorded-sweep ingest (rosbag v2, PointCloud2, Imu)
-           "loam_bag_open", "loam_bag_close", "loam_bag_next", "loam_pc2_parse", "loam_pc2_cloud",
+           "loam_bag_open", "loam_bag_close", "loam_bag_next", "loam_pc2_parse", "loam_pc2_cloud", "loam_pc2_point_fields",
            "loam_imu_parse",
            # include/loam/loam_msg.h: the reference's pose message conventions
            "loam_msg_from_pose", "loam_pose_from_msg")
@@ -250,6 +279,8 @@ def lib():
         L.loam_ring_table_check.argtypes = [ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_float), P(ctypes.c_int32)]
         L.loam_ring_table_of_model.argtypes = [P(Config), P(ctypes.c_uint32), P(ctypes.c_float), P(ctypes.c_int32)]
         L.loam_set_ring_table.argtypes = [PP, ctypes.c_uint32, P(ctypes.c_float), P(ctypes.c_int32)]
+        L.loam_point_fields_check.argtypes = [ctypes.c_uint32, P(PointFields)]
+        L.loam_set_point_fields.argtypes = [PP, P(PointFields)]
         L.loam_batch_upload.argtypes = [PP, ctypes.c_uint32, P(CloudIn), P(CloudIn)]
         L.loam_batch_feed.argtypes = [PP, ctypes.c_uint32, P(CloudIn), P(CloudIn)]
         L.loam_batch_run.argtypes = [PP]
@@ -356,6 +387,25 @@ def ring_table_from_elevations(elev_deg):
     return bounds.astype(np.float32), np.arange(len(e), dtype=np.int32)
 
 
+def point_fields_check(n_rings, fields):
+    """loam_point_fields_check: raises LoamError with the rule a PointFields breaks"""
+    _check(lib().loam_point_fields_check(n_rings, ctypes.byref(fields) if fields is not None else None))
+
+
+def records(xyz, ring, time=None):
+    """velodyne-layout (PointXYZIRT) records of a sweep: 32 bytes each, x, y, z float32 at 0 / 4 / 8,
+    ring uint16 at 20, time float32 at 24 (0 when time is None), everything else 0.  Returns
+    (CloudIn, keep-alive); the fields are ring=(FIELD_U16, 20), time=(FIELD_F32, 24, 1.0, 0.0)."""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    n = xyz.shape[0]
+    rec = np.zeros((max(n, 1), 32), np.uint8)
+    rec[:n, 0:12] = np.ascontiguousarray(xyz).view(np.uint8).reshape(n, 12)
+    rec[:n, 20:22] = np.ascontiguousarray(ring, np.uint16).reshape(n, 1).view(np.uint8)
+    if time is not None:
+        rec[:n, 24:28] = np.ascontiguousarray(time, np.float32).reshape(n, 1).view(np.uint8)
+    return CloudIn(rec.ctypes.data, n, 32), rec
+
+
 def _cloud_in(a):
     """an (n, >= 3) float array, or a ready loam_cloud_in (a strided view of caller memory, e.g. a
     PointCloud2 message's records: rosbag.pc2_cloud_in) passed through as is"""
@@ -434,6 +484,14 @@ class Engine:
         rings [n]; ring_table_from_elevations builds one), before the context's first sweep"""
         pb, pr, n, _keep = _ring_table_args(bounds, rings)
         _check(lib().loam_set_ring_table(self.h, n, pb, pr))
+
+    def set_point_fields(self, ring=None, time=None, ring_map=None, fields=None):
+        """loam_set_point_fields, before the context's first sweep: ring = (type, offset), time =
+        None or (type, offset, scale, bias), ring_map = None or ints (-1 = drop); or a ready
+        PointFields as `fields`.  Neither ring nor fields: back to the ring model."""
+        if fields is None and ring is not None:
+            fields = PointFields.of(ring, time, ring_map)
+        _check(lib().loam_set_point_fields(self.h, ctypes.byref(fields) if fields is not None else None))
 
     # --- the node bodies
     def imu(self, stamp, quat_xyzw, lin_acc):

@@ -390,6 +390,51 @@ int loam_pc2_cloud(const loam_pc2* pc, loam_point* scratch, uint32_t scratch_cap
   return LOAM_OK;
 }
 
+// The ring and time fields of a serialized PointCloud2 as loam_set_point_fields takes them.
+// sensor_msgs/PointField datatypes: 2 UINT8, 4 UINT16, 6 UINT32, 7 FLOAT32, 8 FLOAT64.
+int loam_pc2_point_fields(const uint8_t* msg, uint32_t size, loam_point_fields* out) {
+  if (!msg || !out) return bag_fail(LOAM_E_INVAL, "null argument");
+  Rd r{msg, size};
+  (void)r.stamp();
+  (void)r.u32();
+  (void)r.u32();
+  const uint32_t nf = r.u32();
+  loam_point_fields f;
+  std::memset(&f, 0, sizeof(f));
+  f.time_scale = 1.0;
+  uint32_t off_xyz[3] = {~0u, ~0u, ~0u};
+  bool xyz_f32 = true, ring = false;
+  for (uint32_t k = 0; k < nf && r.ok; ++k) {
+    const std::string name = r.str();
+    const uint32_t off = r.u32();
+    const uint8_t dtype = r.u8();
+    (void)r.u32();  // count
+    if (name == "x" || name == "y" || name == "z") {
+      if (dtype != 7) xyz_f32 = false;
+      off_xyz[name[0] - 'x'] = off;
+    } else if (name == "ring" && (dtype == 2 || dtype == 4 || dtype == 6)) {
+      ring = true;
+      f.ring_type = dtype == 2 ? LOAM_FIELD_U8 : dtype == 4 ? LOAM_FIELD_U16 : LOAM_FIELD_U32;
+      f.ring_offset = off;
+    } else if (name == "time" && (dtype == 7 || dtype == 8)) {  // velodyne: seconds
+      f.time_type = dtype == 7 ? LOAM_FIELD_F32 : LOAM_FIELD_F64;
+      f.time_offset = off;
+      f.time_scale = 1.0;
+    } else if (name == "t" && dtype == 6) {  // Ouster: nanoseconds
+      f.time_type = LOAM_FIELD_U32;
+      f.time_offset = off;
+      f.time_scale = 1e-9;
+    }
+  }
+  if (!r.ok) return bag_fail(LOAM_E_INVAL, "PointCloud2: truncated message");
+  if (!xyz_f32 || off_xyz[0] != 0 || off_xyz[1] != 4 || off_xyz[2] != 8)
+    return bag_fail(LOAM_E_INVAL, "PointCloud2: point fields need x / y / z FLOAT32 at offsets 0 / 4 / 8 (the records are read in place)");
+  if (!ring) return bag_fail(LOAM_E_INVAL, "PointCloud2: no ring field of type UINT8, UINT16 or UINT32");
+  if (f.time_type == LOAM_FIELD_NONE) f.time_offset = 0;
+  *out = f;
+  return LOAM_OK;
+}
+
 int loam_imu_parse(const uint8_t* msg, uint32_t size, double* stamp, double quat_xyzw[4], double lin_acc[3]) {
   if (!msg || !stamp || !quat_xyzw || !lin_acc) return bag_fail(LOAM_E_INVAL, "null argument");
   Rd r{msg, size};

@@ -31,19 +31,31 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-int check_cloud_in(const loam_cloud_in& c, int cap) {
+int check_cloud_in(const loam_cloud_in& c, int cap, const PointFields& pf) {
   if (c.count > 0 && c.data == nullptr) return fail(LOAM_E_INVAL, "cloud data is null");
   if (c.stride_bytes < 12 || c.stride_bytes % 4 != 0) return fail(LOAM_E_INVAL, "bad stride_bytes");
+  if (pf.on && c.stride_bytes < pf.end) return fail(LOAM_E_INVAL, "bad stride_bytes: a record ends before the context's point fields do");
   if (c.count > (uint32_t)cap) return fail(LOAM_E_CAPACITY, "cloud exceeds max_points");
   return LOAM_OK;
 }
 
 // (records need not be 4-byte aligned: a PointCloud2's data follows a variable-length header in
 // the message, and loam_pc2_cloud hands it over in place)
-// points [i0, i1) of c into dst[i0 ..) as float4 (w is not read by the device: a 16-byte stride
-// is copied as is)
-void pack(const loam_cloud_in& c, float4* dst, size_t i0, size_t i1) {
+// points [i0, i1) of c into dst[i0 ..) as float4.  Without point fields w is not read by the
+// device: a 16-byte stride is copied as is.  With them w is the point's word (its ring, or ring +
+// tau, negative = dropped: point_fields.hpp), which the ring kernels' field instantiations read;
+// the caller's own fourth word never reaches it.
+void pack(const loam_cloud_in& c, float4* dst, size_t i0, size_t i1, const PointFields& pf) {
   const char* base = (const char*)c.data;
+  if (pf.on) {
+    for (size_t i = i0; i < i1; ++i) {
+      const unsigned char* rec = (const unsigned char*)base + i * c.stride_bytes;
+      float q[3];
+      std::memcpy(q, rec, sizeof(q));
+      dst[i] = make_float4(q[0], q[1], q[2], field_word_of_record(pf, rec));
+    }
+    return;
+  }
   if (c.stride_bytes == 16) {
     std::memcpy(dst + i0, base + i0 * 16, (i1 - i0) * 16);
     return;
@@ -242,6 +254,40 @@ int loam_set_ring_table(loam_ctx* x, uint32_t n, const float* bound_deg, const i
   return LOAM_OK;
 }
 
+// ------------------------------------------------------------------ point fields (point_fields.hpp)
+int loam_point_fields_check(uint32_t n_rings, const loam_point_fields* f) {
+  const int why = point_fields_check_why(n_rings, f);
+  if (why != kFieldsOk) return fail(LOAM_E_INVAL, std::string("loam_point_fields_check: ") + point_fields_why_text(why));
+  return LOAM_OK;
+}
+
+int loam_set_point_fields(loam_ctx* x, const loam_point_fields* f) {
+  const std::string who = "loam_set_point_fields: ";
+  if (!x) return fail(LOAM_E_INVAL, who + "null argument");
+  if (x->seen_sweep)
+    return fail(LOAM_E_INVAL, who + "the context has seen a sweep (the point fields are set before the first one)");
+  if (!f) {  // back to the ring model or table
+    x->pf = PointFields();
+    return LOAM_OK;
+  }
+  const int why = point_fields_check_why((uint32_t)x->R, f);
+  if (why != kFieldsOk) return fail(LOAM_E_INVAL, who + point_fields_why_text(why));
+  HIP_TRY(hipSetDevice(x->device));
+  const PointFields pf = point_fields_of((uint32_t)x->R, *f);
+  if (!x->pf_map_d) {
+    const hipError_t he = hipMalloc((void**)&x->pf_map_d, sizeof(pf.map));
+    if (he != hipSuccess) {
+      x->pf_map_d = nullptr;
+      if (he == hipErrorOutOfMemory) return nomem(who + "allocation failed");
+      return fail(LOAM_E_HIP, who + hipGetErrorString(he));
+    }
+  }
+  // (a synchronous copy, and no launch reads the map: the context has seen no sweep)
+  HIP_TRY(hipMemcpy(x->pf_map_d, pf.map, sizeof(pf.map), hipMemcpyHostToDevice));
+  x->pf = pf;
+  return LOAM_OK;
+}
+
 void loam_destroy(loam_ctx* x) {
   if (!x) return;
   (void)hipSetDevice(x->device);
@@ -250,6 +296,7 @@ void loam_destroy(loam_ctx* x) {
   if (x->st3) (void)hipStreamSynchronize(x->st3);
   if (x->st4) (void)hipStreamSynchronize(x->st4);
   sr_ring_tab_free(x->ring_tab);
+  if (x->pf_map_d) (void)hipFree(x->pf_map_d);
   sr_free(x->sr1);
   sr_free(x->odin);
   od_free(x->od1);
@@ -428,7 +475,7 @@ int sr_frame(loam_ctx* x, double stamp, const loam_cloud_in& raw, loam_features*
     if (x->sr_init_count >= (int)x->cfg.system_delay) x->sr_inited = true;
     return fail(LOAM_E_NOT_READY, "inside systemDelay");
   }
-  int rc = check_cloud_in(raw, x->cap);
+  int rc = check_cloud_in(raw, x->cap, x->pf);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(x->device));
   SrBuffers& b = x->sr1;
@@ -442,7 +489,7 @@ int sr_frame(loam_ctx* x, double stamp, const loam_cloud_in& raw, loam_features*
   constexpr size_t kPackChunk = 8192;
   for (size_t i0 = 0; i0 < (size_t)n; i0 += kPackChunk) {
     const size_t i1 = std::min((size_t)n, i0 + kPackChunk);
-    pack(raw, praw, i0, i1);
+    pack(raw, praw, i0, i1, x->pf);
     HIP_TRY(hipMemcpyAsync(b.raw + i0, praw + i0, (i1 - i0) * sizeof(float4), hipMemcpyHostToDevice, x->st));
   }
   {

@@ -185,6 +185,13 @@ struct SrBuffers {
   __host__ __device__ int ntiles() const { return (cap + kSrThreads - 1) / kSrThreads; }
 };
 
+// Where the ring kernels take a point's ring from, beside the header's LOAM_RING_* models: values
+// of SrParams::ring_model that only sr_params sets (loam_set_point_fields).  The
+// ring, or the ring and the time, are then in the w of the raw point: (float)r, or (float)r + tau,
+// negative for a dropped point (point_fields.hpp).
+constexpr int kRingSrcField = 16;      // ring from the field, time from the azimuth
+constexpr int kRingSrcFieldTime = 17;  // ring and time from the fields: no angle is computed
+
 struct SrParams {
   int R;
   int ring_model;

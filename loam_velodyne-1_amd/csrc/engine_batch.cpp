@@ -57,8 +57,8 @@ int loam_batch_upload(loam_ctx* x, uint32_t n, const loam_cloud_in* prev, const 
   if (!x || !prev || !cur || n == 0) return fail(LOAM_E_INVAL, "bad batch arguments");
   HIP_TRY(hipSetDevice(x->device));
   for (uint32_t i = 0; i < n; ++i) {
-    int rc = check_cloud_in(prev[i], x->cap);
-    if (!rc) rc = check_cloud_in(cur[i], x->cap);
+    int rc = check_cloud_in(prev[i], x->cap, x->pf);
+    if (!rc) rc = check_cloud_in(cur[i], x->cap, x->pf);
     if (rc) return rc;
   }
   // (a step ahead may still read the raw sweeps or write its buffer set)
@@ -103,7 +103,7 @@ int loam_batch_upload(loam_ctx* x, uint32_t n, const loam_cloud_in* prev, const 
   for (uint32_t i = 0; i < n; ++i)
     for (int k = 0; k < 2; ++k) {
       const loam_cloud_in& c = k == 0 ? prev[i] : cur[i];
-      pack(c, h.data(), 0, c.count);
+      pack(c, h.data(), 0, c.count, x->pf);
       counts[2 * i + k] = (int)c.count;
       HIP_TRY(hipMemcpy(x->srb.raw + (size_t)(2 * i + k) * x->cap, h.data(), (size_t)c.count * sizeof(float4),
                         hipMemcpyHostToDevice));
@@ -120,8 +120,9 @@ int loam_batch_upload(loam_ctx* x, uint32_t n, const loam_cloud_in* prev, const 
 
 namespace {
 // sweeps [s0, s1) of a batch (sweep 2i = prev[i], 2i + 1 = cur[i]) packed back to back (pack_tight_of)
-void pack_tight(const loam_cloud_in* prev, const loam_cloud_in* cur, size_t s0, size_t s1, const int* off, float4* dst) {
-  pack_tight_of([&](size_t s) -> const loam_cloud_in& { return (s & 1) ? cur[s / 2] : prev[s / 2]; }, s0, s1, off, dst);
+void pack_tight(const loam_cloud_in* prev, const loam_cloud_in* cur, size_t s0, size_t s1, const int* off, float4* dst,
+                const PointFields& pf) {
+  pack_tight_of([&](size_t s) -> const loam_cloud_in& { return (s & 1) ? cur[s / 2] : prev[s / 2]; }, s0, s1, off, dst, pf);
 }
 
 // The second scan-registration set and the second mapping set, which only the modes that alternate
@@ -449,8 +450,8 @@ int loam_batch_feed(loam_ctx* x, uint32_t n, const loam_cloud_in* prev, const lo
     return fail(LOAM_E_INVAL, "loam_batch_feed: n must equal the uploaded batch size (loam_batch_upload first)");
   HIP_TRY(hipSetDevice(x->device));
   for (uint32_t i = 0; i < n; ++i) {
-    int rc = check_cloud_in(prev[i], x->cap);
-    if (!rc) rc = check_cloud_in(cur[i], x->cap);
+    int rc = check_cloud_in(prev[i], x->cap, x->pf);
+    if (!rc) rc = check_cloud_in(cur[i], x->cap, x->pf);
     if (rc) return rc;
   }
   const int P = x->P;
@@ -499,7 +500,7 @@ int loam_batch_feed(loam_ctx* x, uint32_t n, const loam_cloud_in* prev, const lo
   constexpr size_t kFeedChunk = 128;  // sweeps
   for (size_t s0 = 0; s0 < S; s0 += kFeedChunk) {
     const size_t s1 = std::min(S, s0 + kFeedChunk);
-    pack_tight(prev, cur, s0, s1, off, x->feed_pin[i]);
+    pack_tight(prev, cur, s0, s1, off, x->feed_pin[i], x->pf);
     const size_t a = (size_t)off[s0], b = (size_t)off[s1 - 1] + (size_t)nn[s1 - 1];
     if (b > a)
       HIP_TRY(hipMemcpyAsync(x->feed_dev + a, x->feed_pin[i] + a, (b - a) * sizeof(float4), hipMemcpyHostToDevice, x->st3));

@@ -17,6 +17,7 @@
 #include "lanes.hpp"
 #include "mp.hpp"
 #include "od.hpp"
+#include "point_fields.hpp"
 #include "pose_math.hpp"
 #include "score.hpp"
 
@@ -40,6 +41,10 @@ struct loam_ctx {
   float tb_bound[LOAM_RING_TABLE_MAX + 1];
   int32_t tb_ring[LOAM_RING_TABLE_MAX];
   bool seen_sweep = false;
+  // loam_set_point_fields: ring, or ring and time, from the records' own fields
+  // (pf.on = 0: none, the ring model or table rules); pf_map_d: the map for the device push's gather
+  PointFields pf;
+  int16_t* pf_map_d = nullptr;
   SrBuffers odin;       // odometry input feature set (host topics uploaded here)
   OdBuffers od1;        // one odometry problem
   bool od_inited = false;
@@ -247,13 +252,17 @@ inline SrParams sr_params(const loam_ctx* c) {
   p.ring_lo = c->cfg.ring_lo_deg;
   p.ring_hi = c->cfg.ring_hi_deg;
   c->ring_tab.fill(p);  // (a table's bounds and rings too: the device copies)
+  // (fields set: the model or table above is kept but not consulted; the ring kernels' field
+  // instantiations read the word pack() or the device push's gather left in raw's w)
+  if (c->pf.on) p.ring_model = c->pf.time_type != LOAM_FIELD_NONE ? kRingSrcFieldTime : kRingSrcField;
   return p;
 }
 
 // ---- engine.cpp
-int check_cloud_in(const loam_cloud_in& c, int cap);
-// points [i0, i1) of c into dst[i0 ..) as float4
-void pack(const loam_cloud_in& c, float4* dst, size_t i0, size_t i1);
+// pf: the context's point fields (every record must reach the end of both)
+int check_cloud_in(const loam_cloud_in& c, int cap, const PointFields& pf);
+// points [i0, i1) of c into dst[i0 ..) as float4; with fields set, w is the point's word (point_fields.hpp)
+void pack(const loam_cloud_in& c, float4* dst, size_t i0, size_t i1, const PointFields& pf);
 // device cloud -> caller storage through the pinned arena (completed by pin.finish() after a sync)
 int copy_out(hipStream_t st, Staging& pin, const float4* dev, int n, loam_cloud_out* o);
 int sr_errors(int e);
@@ -261,11 +270,11 @@ void count_bytes(loam_stats& s);
 
 // sweeps [s0, s1) (sweep s = sweep(s)) packed back to back (sweep s at off[s]) into dst, on up to eight threads
 template <class Sweep>
-void pack_tight_of(Sweep sweep, size_t s0, size_t s1, const int* off, float4* dst) {
+void pack_tight_of(Sweep sweep, size_t s0, size_t s1, const int* off, float4* dst, const PointFields& pf) {
   auto run = [&](size_t a, size_t b) {
     for (size_t s = a; s < b; ++s) {
       const loam_cloud_in& c = sweep(s);
-      pack(c, dst + off[s], 0, c.count);
+      pack(c, dst + off[s], 0, c.count, pf);
     }
   };
   const size_t S = s1 - s0;

@@ -11,9 +11,10 @@
 // clouds, the map store) is the batch buffers' per-problem state, never cleared between steps.
 namespace {
 // what is wrong with a lane's pushed sweep before any kernel sees it (LOAM_OK: nothing)
-int lane_sweep_code(const loam_cloud_in& c, int cap) {
+// (fields_end: the end of the context's point fields in a record, 0 without them)
+int lane_sweep_code(const loam_cloud_in& c, int cap, uint32_t fields_end) {
   if (c.count == 0) return LOAM_E_INVAL;
-  if (c.data == nullptr || c.stride_bytes < 12 || c.stride_bytes % 4 != 0) return LOAM_E_INVAL;
+  if (c.data == nullptr || c.stride_bytes < 12 || c.stride_bytes % 4 != 0 || c.stride_bytes < fields_end) return LOAM_E_INVAL;
   if (c.count > (uint32_t)cap) return LOAM_E_CAPACITY;
   return LOAM_OK;
 }
@@ -603,7 +604,7 @@ int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud
   size_t run = 0;
   for (int l = 0; l < S; ++l) {
     const bool waits = L.life[l].kind == kLaneWaits;
-    L.fail_new[l] = waits ? LOAM_OK : lane_sweep_code(raw[l], x->cap);
+    L.fail_new[l] = waits ? LOAM_OK : lane_sweep_code(raw[l], x->cap, x->pf.on ? x->pf.end : 0);
     eff[l] = raw[l];
     if (waits || L.fail_new[l] != LOAM_OK || L.fail[l] != LOAM_OK) eff[l].count = 0;
     nn[l] = (int)eff[l].count;
@@ -616,7 +617,7 @@ int lanes_push(loam_ctx* x, const double* stamps, double stamp, const loam_cloud
   constexpr int kPushChunk = 128;  // sweeps
   for (int s0 = 0; s0 < S; s0 += kPushChunk) {
     const int s1 = std::min(S, s0 + kPushChunk);
-    pack_tight_of([&](size_t s) -> const loam_cloud_in& { return eff[s]; }, (size_t)s0, (size_t)s1, off, L.stage_h);
+    pack_tight_of([&](size_t s) -> const loam_cloud_in& { return eff[s]; }, (size_t)s0, (size_t)s1, off, L.stage_h, x->pf);
     const size_t a = (size_t)off[s0], b = (size_t)off[s1 - 1] + (size_t)nn[s1 - 1];
     if (b > a)
       HIP_TRY(hipMemcpyAsync(L.stage_d + a, L.stage_h + a, (b - a) * sizeof(float4), hipMemcpyHostToDevice, st));
@@ -650,7 +651,8 @@ void lanes_feed_lookup(const void* p, int device, LaneFeedIn& q) {
 // raw[0..S) and the lanes' states into the plan's input, with HIP's answer for every pointer the
 // step would read.  A pointer inside the allocation found for the previous lane of this call takes
 // that answer; nothing is kept between calls (the memory may have been freed).
-void lanes_feed_inputs(const loam_cloud_in* raw, int S, int cap, int device, const int* state, std::vector<LaneFeedIn>& in) {
+void lanes_feed_inputs(const loam_cloud_in* raw, int S, int cap, int device, const int* state, std::vector<LaneFeedIn>& in,
+                       uint32_t fields_end = 0) {
   in.resize((size_t)S);
   const LaneFeedIn* prev = nullptr;
   for (int l = 0; l < S; ++l) {
@@ -661,7 +663,7 @@ void lanes_feed_inputs(const loam_cloud_in* raw, int S, int cap, int device, con
     q.ptr = (uintptr_t)raw[l].data;
     q.count = raw[l].count;
     q.stride = raw[l].stride_bytes;
-    if (!lanes_feed_looks(q, cap)) continue;
+    if (!lanes_feed_looks(q, cap, fields_end)) continue;
     if (prev && q.ptr >= prev->base && (uint64_t)(q.ptr - prev->base) < prev->size) {
       q.on_device = 1;
       q.base = prev->base;
@@ -702,12 +704,13 @@ extern "C" int loam_lanes_push_device(loam_ctx* x, const double* stamp, const lo
     std::vector<int> state((size_t)S);
     for (int l = 0; l < S; ++l) state[l] = L.fail[l] != LOAM_OK ? kFeedFailed : L.life[l].wait > 0 ? kFeedWaits : kFeedRuns;
     std::vector<LaneFeedIn> in;
-    lanes_feed_inputs(raw, S, x->cap, x->device, state.data(), in);
+    const uint32_t fields_end = x->pf.on ? x->pf.end : 0;
+    lanes_feed_inputs(raw, S, x->cap, x->device, state.data(), in, fields_end);
     // (the last step was pulled: its copy of the descriptor block is done; the lanes' codes go into
     // fail_new only when nothing can refuse the call any more)
     std::vector<int32_t> code((size_t)S);
     uint32_t bad = 0;
-    const int verdict = lanes_feed_plan(in.data(), (uint32_t)S, x->cap, L.fd_h, code.data(), &bad);
+    const int verdict = lanes_feed_plan(in.data(), (uint32_t)S, x->cap, L.fd_h, code.data(), &bad, fields_end);
     if (verdict != kFeedOk) {
       char msg[128];
       lanes_feed_message(verdict, bad, msg, sizeof(msg));
@@ -728,7 +731,7 @@ extern "C" int loam_lanes_push_device(loam_ctx* x, const double* stamp, const lo
     HIP_TRY(hipEventRecord(L.feed_wait, prod));
     HIP_TRY(hipStreamWaitEvent(st, L.feed_wait, 0));
   }
-  HIP_TRY(lanes_gather_dev(L, x->cap, st));
+  HIP_TRY(lanes_gather_dev(L, x->cap, st, x->pf.on ? &x->pf : nullptr, x->pf_map_d));
   x->prof.mark("k_lanes_gather_dev");
   if (feeds && (flags & LOAM_FEED_RELEASE)) {  // the producer's later work behind the gather
     HIP_TRY(hipEventRecord(L.feed_release, st));

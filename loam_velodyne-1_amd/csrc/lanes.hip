@@ -587,6 +587,41 @@ __global__ __launch_bounds__(256) void k_lanes_gather_dev(const LaneFeedDesc* __
     dst[t] = make_uint4(p[0], p[1], p[2], d.stride == 16 ? p[3] : 0u);
   }
 }
+
+// The same with point fields (loam_set_point_fields): x, y, z as three dword loads
+// and w = the point's word, as pack() forms it on the host (point_fields.hpp: one statement of the
+// ring map, the conversion and the word).  A sub-dword field is read as the dword that holds it and
+// shifted; an F64 time as two dwords (its address may be 4 mod 8).  The plan has checked that every
+// record reaches the end of both fields inside the caller's allocation.
+struct GatherFields {
+  uint32_t ring_type, ring_offset, time_type, time_offset, map_n, n_rings;
+  double time_scale, time_bias;
+  const int16_t* map;
+};
+__global__ __launch_bounds__(256) void k_lanes_gather_dev_fields(const LaneFeedDesc* __restrict__ desc, uint4* __restrict__ raw,
+                                                                 int* __restrict__ raw_n, int cap, GatherFields f) {
+  const int s = blockIdx.y;
+  const LaneFeedDesc d = desc[s];
+  const int n = min(d.n, cap);
+  if (blockIdx.x == 0 && threadIdx.x == 0) raw_n[s] = n;
+  uint4* dst = raw + (size_t)s * cap;
+  const int step = gridDim.x * 256;
+  const char* base = (const char*)d.ptr;
+  const size_t stride = (uint32_t)d.stride;
+  const bool timed = f.time_type != LOAM_FIELD_NONE;
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += step) {
+    const uint32_t* p = (const uint32_t*)(base + (size_t)t * stride);
+    const uint32_t v = field_uint_of_dword(p[f.ring_offset >> 2], f.ring_type, f.ring_offset);
+    const int r = field_ring(v, f.map_n, f.map, f.n_rings);
+    float tau = 0.0f;
+    if (timed) {
+      const uint32_t lo = p[f.time_offset >> 2];
+      const uint32_t hi = f.time_type == LOAM_FIELD_F64 ? p[(f.time_offset >> 2) + 1] : 0u;
+      tau = field_tau(field_time_of_dwords(lo, hi, f.time_type), f.time_scale, f.time_bias);
+    }
+    dst[t] = make_uint4(p[0], p[1], p[2], __float_as_uint(field_word(r, timed, tau)));
+  }
+}
 }  // namespace
 
 hipError_t lanes_gather_launch(const LaneFeedDesc* desc_d, float4* raw, int* raw_n, int cap, int S, hipStream_t st) {
@@ -596,9 +631,17 @@ hipError_t lanes_gather_launch(const LaneFeedDesc* desc_d, float4* raw, int* raw
   return hipGetLastError();
 }
 
-hipError_t lanes_gather_dev(Lanes& L, int cap, hipStream_t st) {
+hipError_t lanes_gather_dev(Lanes& L, int cap, hipStream_t st, const PointFields* pf, const int16_t* map_d) {
   const hipError_t e = hipMemcpyAsync(L.fd_d, L.fd_h, (size_t)L.S * sizeof(LaneFeedDesc), hipMemcpyHostToDevice, st);
-  return e != hipSuccess ? e : lanes_gather_launch(L.fd_d, L.sr.raw, L.sr.raw_n, cap, L.S, st);
+  if (e != hipSuccess) return e;
+  if (!pf) return lanes_gather_launch(L.fd_d, L.sr.raw, L.sr.raw_n, cap, L.S, st);
+  if (L.S <= 0) return hipSuccess;
+  if (!map_d) return hipErrorInvalidValue;
+  const GatherFields f = {pf->ring_type, pf->ring_offset, pf->time_type, pf->time_offset, pf->map_n, pf->n_rings,
+                          pf->time_scale, pf->time_bias, map_d};
+  hipLaunchKernelGGL(k_lanes_gather_dev_fields, dim3(std::max(1, std::min(64, (cap + 255) / 256)), L.S), dim3(256), 0, st,
+                     L.fd_d, (uint4*)L.sr.raw, L.sr.raw_n, cap, f);
+  return hipGetLastError();
 }
 
 hipError_t lanes_feed_alloc(Lanes& L) {

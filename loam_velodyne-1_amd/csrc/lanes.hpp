@@ -12,6 +12,7 @@
 #include "engine.hpp"
 #include "lanes_clouds_plan.hpp"
 #include "lanes_feed_plan.hpp"
+#include "point_fields.hpp"
 #include "mp.hpp"
 #include "od.hpp"
 
@@ -160,7 +161,9 @@ hipError_t lanes_imu_commit(Lanes& L, bool od_init, bool mapping, hipStream_t st
 hipError_t lanes_feed_alloc(Lanes& L);
 // k_lanes_gather_dev: L.fd_h's S descriptors to the device, then every feeding lane's sweep from the
 // caller's device memory into sr.raw at its stride and every lane's size into sr.raw_n
-hipError_t lanes_gather_dev(Lanes& L, int cap, hipStream_t st);
+// pf (optional): the context's point fields and their map on the device: the gather's field form
+// writes each point's word into w (point_fields.hpp)
+hipError_t lanes_gather_dev(Lanes& L, int cap, hipStream_t st, const PointFields* pf = nullptr, const int16_t* map_d = nullptr);
 // the kernel alone on device descriptors (loam_dev_lanes_gather)
 hipError_t lanes_gather_launch(const LaneFeedDesc* desc_d, float4* raw, int* raw_n, int cap, int S, hipStream_t st);
 

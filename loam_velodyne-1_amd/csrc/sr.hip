@@ -70,7 +70,9 @@ namespace {
 // The ring kernels exist twice (template parameter TAB): for the built-in models, whose code, LDS
 // and arguments are what they were before ring tables, and for a LOAM_RING_TABLE model, whose
 // device block (p.ring_tab, the fixed layout SrRingTab describes) also holds the guess LUT and the
-// table's bounds and rings.  sr_launch picks the instantiation from p.ring_model.
+// table's bounds and rings.  sr_launch picks the instantiation from p.ring_model.  Two more
+// instantiations read the ring, or the ring and the time, from the raw point's w (kSrcField,
+// kSrcFieldTime below: loam_set_point_fields).
 constexpr int kRingTabMax = kRingTableMax;  // intervals (65 boundaries: the linear model's 64 rings)
 constexpr int kRingLutMax = 2048;           // cells (bytes) of a table model's guess LUT
 constexpr int kRingHdr = kRingTabMax;                       // float4 index of the block's header
@@ -151,6 +153,21 @@ LOAM_D int ring_of(const SrParams& p, const float4* tab, float px, float py, flo
   }
   return ring_of_exact<TAB>(p, px, py, pz);
 }
+// Where a ring kernel takes a point's ring (and time) from: the template parameter SRC of the ring
+// kernels.  kSrcModel and kSrcTable are the two instantiations above.  With point fields
+// (loam_set_point_fields) the ring is (int)w of the raw point just loaded (a
+// negative w: dropped): nothing is read from p.ring_tab and the table's LDS block is not
+// allocated.  kSrcField keeps the azimuth, the sweep's ends and halfPassed; kSrcFieldTime has the
+// point's time in w too (w = (float)r + tau: intensity = w, pointTime = w - (float)r, exact) and
+// computes no angle at all.
+enum { kSrcModel = 0, kSrcTable = 1, kSrcField = 2, kSrcFieldTime = 3 };
+LOAM_HD int ring_src_of(int ring_model) {
+  return ring_model == LOAM_RING_TABLE ? kSrcTable
+         : ring_model == kRingSrcField ? kSrcField
+         : ring_model == kRingSrcFieldTime ? kSrcFieldTime
+                                           : kSrcModel;
+}
+LOAM_D float word_time(float w) { return w - (float)(int)w; }  // tau of a kept point's word
 template <bool TAB>
 LOAM_D void ring_tab_load(const SrParams& p, float4* tab) {  // a barrier before the first ring_of
   if ((int)threadIdx.x < p.ring_n) tab[threadIdx.x] = p.ring_tab[threadIdx.x];
@@ -159,6 +176,21 @@ LOAM_D void ring_tab_load(const SrParams& p, float4* tab) {  // a barrier before
     const int cells16 = (__float_as_int(p.ring_tab[kRingHdr].x) + 15) >> 4;
     for (int i = threadIdx.x; i < cells16; i += blockDim.x) tab[kRingLutAt + i] = p.ring_tab[kRingLutAt + i];
   }
+}
+
+// the ring of raw point q (before the axis swap) under SRC; the caller checks it against [0, R)
+template <int SRC>
+LOAM_D int ring_of_src(const SrParams& p, const float4* tab, const float4& q) {
+  if constexpr (SRC >= kSrcField) {
+    return (q.w >= 0.0f && q.w < 65.0f) ? (int)q.w : -1;
+  } else {
+    const float px = q.y, py = q.z, pz = q.x;
+    return ring_of<SRC == kSrcTable>(p, tab, px, py, pz);
+  }
+}
+template <int SRC>
+LOAM_D void ring_src_load(const SrParams& p, float4* tab) {
+  if constexpr (SRC < kSrcField) ring_tab_load<SRC == kSrcTable>(p, tab);
 }
 
 using loamimu::kNoOri;
@@ -170,8 +202,9 @@ LOAM_D bool finite3(const float4& q) {
 }
 
 // ---------------------------------------------------------------- ring sort
-template <bool IMU, bool TAB>
+template <bool IMU, int SRC>
 __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrParams p) {
+  constexpr bool TAB = SRC == kSrcTable, FT = SRC == kSrcFieldTime;
   const int s = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int n = b.raw_n[s];
   const float4* raw = b.raw + (size_t)s * b.cap;
@@ -186,7 +219,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
   __shared__ int sh_wcnt[kSrThreads / 64][64];
   __shared__ int sh_base[64];
   __shared__ float4 sh_rtab[kRingLds<TAB>];
-  ring_tab_load<TAB>(p, sh_rtab);
+  ring_src_load<SRC>(p, sh_rtab);
   if (tid == 0) { sh_first = 0x7fffffff; sh_last = -1; sh_F = 0x7fffffff; }
   __syncthreads();
   int f = 0x7fffffff, l = -1;
@@ -201,7 +234,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
     if (tid == 0) { b.n_full[s] = 0; b.err[s] |= ERR_EMPTY; }
     return;
   }
-  if (tid == 0) {  // :230-238
+  if (!FT && tid == 0) {  // :230-238
     float4 a = raw[sh_first], z = raw[sh_last];
     float startOri = -atan2f_fdlibm(a.y, a.x);
     float endOri = (float)(D(-atan2f_fdlibm(z.y, z.x)) + 2 * M_PI);
@@ -211,7 +244,11 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
     sh_end = endOri;
   }
   __syncthreads();
-  const float startOri = sh_start, endOri = sh_end;
+  float startOri = 0.0f, endOri = 0.0f;  // (kSrcFieldTime: neither written nor read)
+  if constexpr (!FT) {
+    startOri = sh_start;
+    endOri = sh_end;
+  }
   // phase A: ring id + first-branch orientation; the halfPassed flip point F
   int Floc = 0x7fffffff;
   for (int t = 0; t < ntiles; ++t) {
@@ -223,17 +260,19 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
       uint8_t sid = 255;
       float ori = 0.0f;
       if (finite3(q)) {
-        const float px = q.y, py = q.z, pz = q.x;
-        int scanID = ring_of<TAB>(p, sh_rtab, px, py, pz);
+        const float px = q.y, pz = q.x;
+        int scanID = ring_of_src<SRC>(p, sh_rtab, q);
         if (scanID >= 0 && scanID <= R - 1) {
           sid = (uint8_t)scanID;
-          ori = -atan2f_fdlibm(px, pz);
-          float o1 = ori_first(ori, startOri);
-          if (D(o1 - startOri) > M_PI) Floc = min(Floc, i);
+          if constexpr (!FT) {
+            ori = -atan2f_fdlibm(px, pz);
+            float o1 = ori_first(ori, startOri);
+            if (D(o1 - startOri) > M_PI) Floc = min(Floc, i);
+          }
           atomicAdd(&sh_cnt[scanID], 1);
         }
       }
-      tori[i] = ori;
+      if constexpr (!FT) tori[i] = ori;
       tsid[i] = sid;
     }
     __syncthreads();
@@ -274,9 +313,14 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
   if (imu && tid == 0) {
     loamimu::Cur c;
     if (tsid[i0] != 255) {
-      const float ori = ori_first(tori[i0], startOri);  // i0 <= F
-      const float relTime = (ori - startOri) / (endOri - startOri);
-      const float pointTime = (float)(D(relTime) * 0.1);  // scanPeriod (double, :55)
+      float pointTime;
+      if constexpr (FT) {
+        pointTime = word_time(raw[i0].w);
+      } else {
+        const float ori = ori_first(tori[i0], startOri);  // i0 <= F
+        const float relTime = (ori - startOri) / (endOri - startOri);
+        pointTime = (float)(D(relTime) * 0.1);  // scanPeriod (double, :55)
+      }
       const int g = loamimu::first_later(*imu, front0, p.time_scan + pointTime);
       c = loamimu::interpolate(*imu, (front0 + g) % loamimu::kQue, p.time_scan, pointTime);
       imu->rollStart = c.roll; imu->pitchStart = c.pitch; imu->yawStart = c.yaw;
@@ -304,9 +348,13 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
     if (imu) {
       int g = -1;
       if (valid) {
-        const float ori = (i <= F) ? ori_first(tori[i], startOri) : ori_second(tori[i], endOri);
-        const float relTime = (ori - startOri) / (endOri - startOri);
-        pointTime = (float)(D(relTime) * 0.1);
+        if constexpr (FT) {
+          pointTime = word_time(raw[i].w);
+        } else {
+          const float ori = (i <= F) ? ori_first(tori[i], startOri) : ori_second(tori[i], endOri);
+          const float relTime = (ori - startOri) / (endOri - startOri);
+          pointTime = (float)(D(relTime) * 0.1);
+        }
         g = loamimu::first_later(*imu, front0, p.time_scan + pointTime);
       }
       int tmax;
@@ -327,14 +375,18 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_sort(SrBuffers b, SrPara
       int pos = sh_base[sid] + tc[t * R + sid] + rank;
       for (int v = 0; v < w; ++v) pos += sh_wcnt[v][sid];
       const float4 q = raw[i];
-      float ori = tori[i];
-      ori = (i <= F) ? ori_first(ori, startOri) : ori_second(ori, endOri);
-      float relTime = (ori - startOri) / (endOri - startOri);
       float4 o;
       o.x = q.y;
       o.y = q.z;
       o.z = q.x;
-      o.w = (float)(sid + 0.1 * D(relTime));
+      if constexpr (FT) {
+        o.w = q.w;
+      } else {
+        float ori = tori[i];
+        ori = (i <= F) ? ori_first(ori, startOri) : ori_second(ori, endOri);
+        float relTime = (ori - startOri) / (endOri - startOri);
+        o.w = (float)(sid + 0.1 * D(relTime));
+      }
       if (imu) {
         cur = loamimu::interpolate(*imu, (front0 + front_i) % loamimu::kQue, p.time_scan, pointTime);
         if (i != i0) {  // ShiftToStartIMU, VeloToStartIMU, TransformToStartIMU (:343-347)
@@ -400,8 +452,13 @@ constexpr int kRingTile = kSrThreads * kRingE;
 // loamimu::tile_ori_key picks among them (imu.hpp; tests/lanes_imu_walk_check.cpp runs the rule on
 // the host against the sequential walk).
 
-template <bool IMU, bool TAB>
+// (SRC = kSrcFieldTime: only tile 0 looks for the sweep's first finite point, for ERR_EMPTY and
+// the IMU Start rule; no orientation, no flip; the tile's IMU key is one value, the largest point
+// time of its kept points, kept as key [0] with [1] and [2] left at kNoOri: first_later is
+// monotone in the time, and times need not be monotone along the sweep, the maximum handles that)
+template <bool IMU, int SRC>
 __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrParams p) {
+  constexpr bool TAB = SRC == kSrcTable, FT = SRC == kSrcFieldTime;
   const int s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int n = b.raw_n[s], R = p.R;
   const bool imu = IMU && p.imu_lane[s].has != 0;
@@ -424,7 +481,17 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
     const int i = t * kRingTile + e * kSrThreads + tid;
     q[e] = i < n ? raw[i] : make_float4(0, 0, 0, 0);
   }
-  if (w == 0) {
+  if constexpr (FT) {  // only tile 0, and only the first finite point (sh_last: its sign is read)
+    if (t == 0 && w == 0) {
+      int f = -1;
+      for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        const uint64_t m = __ballot(i < n && finite3(raw[i]));
+        if (m) { f = base + __ffsll((unsigned long long)m) - 1; break; }
+      }
+      if (lane == 0) sh_first = sh_last = f;
+    }
+  } else if (w == 0) {
     int f = -1;
     for (int base = 0; base < n; base += 64) {
       const int i = base + lane;
@@ -442,19 +509,22 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
     if (lane == 0) sh_last = l;
   }
   __shared__ float4 sh_rtab[kRingLds<TAB>];
-  ring_tab_load<TAB>(p, sh_rtab);
+  ring_src_load<SRC>(p, sh_rtab);
   if (tid < R) sh_cnt[tid] = 0;
   if (tid == 0) sh_F = 0x7fffffff;
   __syncthreads();
   // :230-238, the two orientations on two waves; only tile 0 needs endOri
-  if (tid == 0) sh_start = sh_last >= 0 ? -atan2f_fdlibm(raw[sh_first].y, raw[sh_first].x) : 0.0f;
-  if (tid == 64 && (t == 0 || imu) && sh_last >= 0) sh_end_raw = -atan2f_fdlibm(raw[sh_last].y, raw[sh_last].x);
-  __syncthreads();
-  const float startOri = sh_start;
+  float startOri = 0.0f;
+  if constexpr (!FT) {
+    if (tid == 0) sh_start = sh_last >= 0 ? -atan2f_fdlibm(raw[sh_first].y, raw[sh_first].x) : 0.0f;
+    if (tid == 64 && (t == 0 || imu) && sh_last >= 0) sh_end_raw = -atan2f_fdlibm(raw[sh_last].y, raw[sh_last].x);
+    __syncthreads();
+    startOri = sh_start;
+  }
   if (IMU && imu) {  // every tile needs endOri (ori_second); tile 0 publishes it below as ever
     if (tid == 0) {
       float endOri = 0.0f;
-      if (sh_last >= 0) {
+      if (!FT && sh_last >= 0) {
         endOri = (float)(D(sh_end_raw) + 2 * M_PI);
         if (D(endOri - startOri) > 3 * M_PI) endOri = (float)(D(endOri) - 2 * M_PI);
         else if (D(endOri - startOri) < M_PI) endOri = (float)(D(endOri) + 2 * M_PI);
@@ -468,14 +538,18 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
   if (tid == 0 && t == 0) {
     float endOri = 0.0f;
     if (sh_last >= 0) {
-      endOri = (float)(D(sh_end_raw) + 2 * M_PI);
-      if (D(endOri - startOri) > 3 * M_PI) endOri = (float)(D(endOri) - 2 * M_PI);
-      else if (D(endOri - startOri) < M_PI) endOri = (float)(D(endOri) + 2 * M_PI);
+      if constexpr (!FT) {
+        endOri = (float)(D(sh_end_raw) + 2 * M_PI);
+        if (D(endOri - startOri) > 3 * M_PI) endOri = (float)(D(endOri) - 2 * M_PI);
+        else if (D(endOri - startOri) < M_PI) endOri = (float)(D(endOri) + 2 * M_PI);
+      }
     } else {
       b.err[s] |= ERR_EMPTY;
     }
-    b.sweep_ori[2 * s] = startOri;
-    b.sweep_ori[2 * s + 1] = endOri;
+    if constexpr (!FT) {
+      b.sweep_ori[2 * s] = startOri;
+      b.sweep_ori[2 * s + 1] = endOri;
+    }
   }
   int Floc = 0x7fffffff;
   int k1[kRingE], k2[kRingE];  // (IMU) keys of the point's ori_first / ori_second, kNoOri for a dropped point
@@ -487,21 +561,26 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
       uint8_t sid = 255;
       float ori = 0.0f;
       if (finite3(q[e])) {
-        const float px = q[e].y, py = q[e].z, pz = q[e].x;
-        const int scanID = ring_of<TAB>(p, sh_rtab, px, py, pz);
+        const float px = q[e].y, pz = q[e].x;
+        const int scanID = ring_of_src<SRC>(p, sh_rtab, q[e]);
         if (scanID >= 0 && scanID <= R - 1) {
           sid = (uint8_t)scanID;
-          ori = -atan2f_fdlibm(px, pz);
-          const float o1 = ori_first(ori, startOri);
-          if (D(o1 - startOri) > M_PI) Floc = min(Floc, i);
-          atomicAdd(&sh_cnt[scanID], 1);
-          if (IMU && imu) {
-            k1[e] = ori_key(o1);
-            k2[e] = ori_key(ori_second(ori, sh_end));
+          if constexpr (FT) {
+            atomicAdd(&sh_cnt[scanID], 1);
+            if (IMU && imu) k1[e] = ori_key(word_time(q[e].w));
+          } else {
+            ori = -atan2f_fdlibm(px, pz);
+            const float o1 = ori_first(ori, startOri);
+            if (D(o1 - startOri) > M_PI) Floc = min(Floc, i);
+            atomicAdd(&sh_cnt[scanID], 1);
+            if (IMU && imu) {
+              k1[e] = ori_key(o1);
+              k2[e] = ori_key(ori_second(ori, sh_end));
+            }
           }
         }
       }
-      b.tmp_ori[(size_t)s * b.cap + i] = ori;
+      if constexpr (!FT) b.tmp_ori[(size_t)s * b.cap + i] = ori;
       b.tmp_sid[(size_t)s * b.cap + i] = sid;
     }
   }
@@ -509,9 +588,11 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
   if (lane == 0 && Floc != 0x7fffffff) atomicMin(&sh_F, Floc);
   __syncthreads();
   if (tid < R) b.tilecnt[((size_t)s * b.ntiles() + t) * R + tid] = sh_cnt[tid];
-  if (tid == 0) b.tileF[(size_t)s * b.ntiles() + t] = sh_F;
+  if constexpr (!FT) {
+    if (tid == 0) b.tileF[(size_t)s * b.ntiles() + t] = sh_F;
+  }
   if (IMU && imu) {
-    const int ownF = sh_F;
+    const int ownF = sh_F;  // (kSrcFieldTime: no flip, every point's key is k1)
     int m1 = kNoOri, m2 = kNoOri, m3 = kNoOri;
 #pragma unroll
     for (int e = 0; e < kRingE; ++e) {
@@ -532,7 +613,9 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_count(SrBuffers b, SrPar
 // every tile from the first finite point (or read from the queue's tail); the last tile with a
 // ring-filtered point writes the tail the sweep leaves into imu_tail[s], never into the queue,
 // which the other tiles are still reading.
-template <bool IMU>
+// FT (the counting kernel's SRC was kSrcFieldTime): the point's time and intensity are its raw w;
+// tmp_ori, tileF and sweep_ori are neither written nor read.
+template <bool IMU, bool FT>
 __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrParams p) {
   constexpr int kW = kSrThreads / 64, kSlots = kRingE * kW;  // (sub-tile, wave) slots in point order
   static_assert(kSlots <= 64 && (kSlots & (kSlots - 1)) == 0, "slot scan width");
@@ -558,7 +641,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
     if (i < n) {
       sid[e] = (int)b.tmp_sid[(size_t)s * b.cap + i];
       q[e] = b.raw[(size_t)s * b.cap + i];
-      ori[e] = b.tmp_ori[(size_t)s * b.cap + i];
+      if constexpr (!FT) ori[e] = b.tmp_ori[(size_t)s * b.cap + i];
     }
   }
   if (tid < R) { sh_tot[tid] = 0; sh_pre[tid] = 0; }
@@ -576,9 +659,11 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
     }
   }
   int F = 0x7fffffff;
-  for (int k = tid; k < nt; k += kSrThreads) F = min(F, b.tileF[(size_t)s * b.ntiles() + k]);
-  F = wave_min_i(F);
-  if (lane == 0 && F != 0x7fffffff) atomicMin(&sh_F, F);
+  if constexpr (!FT) {
+    for (int k = tid; k < nt; k += kSrThreads) F = min(F, b.tileF[(size_t)s * b.ntiles() + k]);
+    F = wave_min_i(F);
+    if (lane == 0 && F != 0x7fffffff) atomicMin(&sh_F, F);
+  }
   // stable ranks within each (sub-tile, wave) slot by wave ballots
 #pragma unroll
   for (int e = 0; e < kRingE; ++e) {
@@ -611,7 +696,11 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
   __syncthreads();
   if (nt == 0) return;
   F = sh_F;
-  const float startOri = b.sweep_ori[2 * s], endOri = b.sweep_ori[2 * s + 1];
+  float startOri = 0.0f, endOri = 0.0f;
+  if constexpr (!FT) {
+    startOri = b.sweep_ori[2 * s];
+    endOri = b.sweep_ori[2 * s + 1];
+  }
   if (IMU && imu) {
     const loamimu::SrQueue& Q = p.imu[s];
     const double time_scan = p.imu_lane[s].time_scan;
@@ -628,8 +717,13 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
       const int tF = F == 0x7fffffff ? 0x7fffffff : F / kRingTile;
       const int k = loamimu::tile_ori_key(p.imu_tile_key + ((size_t)s * b.ntiles() + u) * 3, u, tF);
       if (k != kNoOri) {
-        const float relTime = (loamimu::ori_of_key(k) - startOri) / (endOri - startOri);
-        const float pointTime = (float)(D(relTime) * 0.1);
+        float pointTime;
+        if constexpr (FT) {
+          pointTime = loamimu::ori_of_key(k);  // (the tile's largest point time itself)
+        } else {
+          const float relTime = (loamimu::ori_of_key(k) - startOri) / (endOri - startOri);
+          pointTime = (float)(D(relTime) * 0.1);
+        }
         atomicMax(&sh_carry, loamimu::first_later_of(sh_time, qlast, front0, time_scan + pointTime));
       }
     }
@@ -637,9 +731,14 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
     if (tid == 64) {
       loamimu::Cur c;
       if (i0 >= 0 && b.tmp_sid[(size_t)s * b.cap + i0] != 255) {
-        const float o = ori_first(b.tmp_ori[(size_t)s * b.cap + i0], startOri);  // i0 <= F
-        const float relTime = (o - startOri) / (endOri - startOri);
-        const float pointTime = (float)(D(relTime) * 0.1);  // scanPeriod (double, :55)
+        float pointTime;
+        if constexpr (FT) {
+          pointTime = word_time(b.raw[(size_t)s * b.cap + i0].w);
+        } else {
+          const float o = ori_first(b.tmp_ori[(size_t)s * b.cap + i0], startOri);  // i0 <= F
+          const float relTime = (o - startOri) / (endOri - startOri);
+          pointTime = (float)(D(relTime) * 0.1);  // scanPeriod (double, :55)
+        }
         const int g = loamimu::first_later_of(sh_time, qlast, front0, time_scan + pointTime);
         c = loamimu::interpolate(Q, (front0 + g) % loamimu::kQue, time_scan, pointTime);
       } else {
@@ -657,9 +756,13 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
       g[e] = -1;
       pointTime[e] = 0.0f;
       if (sid[e] != 255) {
-        const float o = (i <= F) ? ori_first(ori[e], startOri) : ori_second(ori[e], endOri);
-        const float relTime = (o - startOri) / (endOri - startOri);
-        pointTime[e] = (float)(D(relTime) * 0.1);
+        if constexpr (FT) {
+          pointTime[e] = word_time(q[e].w);
+        } else {
+          const float o = (i <= F) ? ori_first(ori[e], startOri) : ori_second(ori[e], endOri);
+          const float relTime = (o - startOri) / (endOri - startOri);
+          pointTime[e] = (float)(D(relTime) * 0.1);
+        }
         g[e] = loamimu::first_later_of(sh_time, qlast, front0, time_scan + pointTime[e]);
         li = i;
       }
@@ -675,9 +778,14 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
       carry = max(carry, tmax);
       if (sid[e] != 255) {
         const int pos = sh_base[sid[e]] + sh_pre[sid[e]] + sh_wcnt[sid[e]][e * kW + w] + rank[e];
-        const float o = (i <= F) ? ori_first(ori[e], startOri) : ori_second(ori[e], endOri);
-        const float relTime = (o - startOri) / (endOri - startOri);
-        float4 out = make_float4(q[e].y, q[e].z, q[e].x, (float)(sid[e] + 0.1 * D(relTime)));
+        float4 out;
+        if constexpr (FT) {
+          out = make_float4(q[e].y, q[e].z, q[e].x, q[e].w);
+        } else {
+          const float o = (i <= F) ? ori_first(ori[e], startOri) : ori_second(ori[e], endOri);
+          const float relTime = (o - startOri) / (endOri - startOri);
+          out = make_float4(q[e].y, q[e].z, q[e].x, (float)(sid[e] + 0.1 * D(relTime)));
+        }
         const loamimu::Cur cur = loamimu::interpolate(Q, (front0 + front_i) % loamimu::kQue, time_scan, pointTime[e]);
         float fs[6];
         if (i != i0) {  // ShiftToStartIMU, VeloToStartIMU, TransformToStartIMU (:343-347)
@@ -704,9 +812,13 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_scatter(SrBuffers b, SrP
     const int i = t * kRingTile + e * kSrThreads + tid;
     if (sid[e] != 255) {
       const int pos = sh_base[sid[e]] + sh_pre[sid[e]] + sh_wcnt[sid[e]][e * kW + w] + rank[e];
-      const float o = (i <= F) ? ori_first(ori[e], startOri) : ori_second(ori[e], endOri);
-      const float relTime = (o - startOri) / (endOri - startOri);
-      b.full[(size_t)s * b.cap + pos] = make_float4(q[e].y, q[e].z, q[e].x, (float)(sid[e] + 0.1 * D(relTime)));
+      if constexpr (FT) {
+        b.full[(size_t)s * b.cap + pos] = make_float4(q[e].y, q[e].z, q[e].x, q[e].w);
+      } else {
+        const float o = (i <= F) ? ori_first(ori[e], startOri) : ori_second(ori[e], endOri);
+        const float relTime = (o - startOri) / (endOri - startOri);
+        b.full[(size_t)s * b.cap + pos] = make_float4(q[e].y, q[e].z, q[e].x, (float)(sid[e] + 0.1 * D(relTime)));
+      }
     }
   }
 }
@@ -777,8 +889,11 @@ __global__ __launch_bounds__(kPrepThreads) void k_sr_ring_prep(SrBuffers b, int 
     if (tid == 0) b.sweep_ends[s] = make_int4(sh_last, __float_as_int(sh_start), __float_as_int(sh_end_raw), 0);
   }
 }
-template <bool TAB>
+// (SRC = kSrcFieldTime: of the sweep's ends only "is there a finite point" is read, for ERR_EMPTY;
+// no orientation, no flip: tileF is neither published nor waited for)
+template <int SRC>
 __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrParams p, int rtiles) {
+  constexpr bool TAB = SRC == kSrcTable, FT = SRC == kSrcFieldTime;
   constexpr int kW = kSrThreads / 64, kSlots = kRingE * kW;
   static_assert(kSlots <= 64 && (kSlots & (kSlots - 1)) == 0, "slot scan width");
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
@@ -872,7 +987,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
   }
 #endif
   __shared__ float4 sh_rtab[kRingLds<TAB>];
-  ring_tab_load<TAB>(p, sh_rtab);
+  ring_src_load<SRC>(p, sh_rtab);
   if (tid < R) sh_cnt[tid] = 0;
   if (tid == 0) sh_F = 0x7fffffff;
   for (int k = tid; k < 64 * kSlots; k += kSrThreads) (&sh_wcnt[0][0])[k] = 0;
@@ -883,15 +998,17 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
   const int last = sh_last;
 #endif
   float endOri = 0.0f;
-  if (last >= 0) {
+  if (!FT && last >= 0) {
     endOri = (float)(D(end_raw) + 2 * M_PI);
     if (D(endOri - startOri) > 3 * M_PI) endOri = (float)(D(endOri) - 2 * M_PI);
     else if (D(endOri - startOri) < M_PI) endOri = (float)(D(endOri) + 2 * M_PI);
   }
   if (tid == 0 && t == 0) {
     if (last < 0) b.err[s] |= ERR_EMPTY;
-    b.sweep_ori[2 * s] = startOri;
-    b.sweep_ori[2 * s + 1] = endOri;
+    if constexpr (!FT) {
+      b.sweep_ori[2 * s] = startOri;
+      b.sweep_ori[2 * s + 1] = endOri;
+    }
   }
   int sid[kRingE], rank[kRingE];
   float ori[kRingE];
@@ -902,12 +1019,14 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
     sid[e] = 255;
     ori[e] = 0.0f;
     if (i < n && finite3(q[e])) {
-      const float px = q[e].y, py = q[e].z, pz = q[e].x;
-      const int scanID = ring_of<TAB>(p, sh_rtab, px, py, pz);
+      const float px = q[e].y, pz = q[e].x;
+      const int scanID = ring_of_src<SRC>(p, sh_rtab, q[e]);
       if (scanID >= 0 && scanID <= R - 1) {
         sid[e] = scanID;
-        ori[e] = -atan2f_fdlibm(px, pz);
-        if (D(ori_first(ori[e], startOri) - startOri) > M_PI) Floc = min(Floc, i);
+        if constexpr (!FT) {
+          ori[e] = -atan2f_fdlibm(px, pz);
+          if (D(ori_first(ori[e], startOri) - startOri) > M_PI) Floc = min(Floc, i);
+        }
         atomicAdd(&sh_cnt[scanID], 1);
       }
     }
@@ -920,7 +1039,7 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
   // presets them to -1), so no fence orders them (an agent-scope fence writes back / invalidates
   // the XCD's whole L2)
   if (tid < R) __hip_atomic_store(&b.tilecnt[((size_t)s * rtiles + t) * R + tid], sh_cnt[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (tid == 0) __hip_atomic_store(&b.tileF[(size_t)s * rtiles + t], sh_F, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!FT && tid == 0) __hip_atomic_store(&b.tileF[(size_t)s * rtiles + t], sh_F, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   // stable ranks within each (sub-tile, wave) slot by wave ballots, while the other tiles count
 #pragma unroll
   for (int e = 0; e < kRingE; ++e) {
@@ -954,11 +1073,13 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
     }
   }
   int F = 0x7fffffff;
-  for (int k = tid; k < nt; k += kSrThreads) {
-    int v;
-    while ((v = __hip_atomic_load(&b.tileF[(size_t)s * rtiles + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < 0)
-      __builtin_amdgcn_s_sleep(1);
-    F = min(F, v);
+  if constexpr (!FT) {
+    for (int k = tid; k < nt; k += kSrThreads) {
+      int v;
+      while ((v = __hip_atomic_load(&b.tileF[(size_t)s * rtiles + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < 0)
+        __builtin_amdgcn_s_sleep(1);
+      F = min(F, v);
+    }
   }
   F = wave_min_i(F);
   if (tid == 0) sh_F = 0x7fffffff;
@@ -979,9 +1100,13 @@ __global__ __launch_bounds__(kSrThreads) void k_sr_ring_fused(SrBuffers b, SrPar
     const int i = t * kRingTile + e * kSrThreads + tid;
     if (sid[e] != 255) {
       const int pos = sh_base[sid[e]] + sh_pre[sid[e]] + sh_wcnt[sid[e]][e * kW + w] + rank[e];
-      const float o = (i <= F) ? ori_first(ori[e], startOri) : ori_second(ori[e], endOri);
-      const float relTime = (o - startOri) / (endOri - startOri);
-      b.full[(size_t)s * b.cap + pos] = make_float4(q[e].y, q[e].z, q[e].x, (float)(sid[e] + 0.1 * D(relTime)));
+      if constexpr (FT) {
+        b.full[(size_t)s * b.cap + pos] = make_float4(q[e].y, q[e].z, q[e].x, q[e].w);
+      } else {
+        const float o = (i <= F) ? ori_first(ori[e], startOri) : ori_second(ori[e], endOri);
+        const float relTime = (o - startOri) / (endOri - startOri);
+        b.full[(size_t)s * b.cap + pos] = make_float4(q[e].y, q[e].z, q[e].x, (float)(sid[e] + 0.1 * D(relTime)));
+      }
     }
   }
 #ifdef LOAM_SR_PHASES
@@ -2491,41 +2616,41 @@ void sr_free(SrBuffers& b) {
 // and LDS allow, queried once per device) times the CUs.  Other streams' kernels may hold slots
 // for a while, but they never wait on this launch, so the bound is the idle device's.
 // (per instantiation: a table model's carries the LUT in LDS)
-template <bool TAB>
+template <int SRC>
 static int sr_ring_fused_capacity_of() {
   static int cap[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
   if (cap[dev] == 0) {
     int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sr_ring_fused<TAB>, kSrThreads, 0) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sr_ring_fused<SRC>, kSrThreads, 0) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       per_cu = cus = 0;
     cap[dev] = std::max(1, per_cu * cus);  // (1: a failed query keeps the two-kernel form below)
   }
   return cap[dev];
 }
-int sr_ring_fused_capacity() { return sr_ring_fused_capacity_of<false>(); }
+int sr_ring_fused_capacity() { return sr_ring_fused_capacity_of<kSrcModel>(); }
 
-// the ring sort of sr_launch for the built-in models (TAB = false) or a table model
-template <bool TAB>
+// the ring sort of sr_launch for the built-in models (kSrcModel), a table model, or point fields
+template <int SRC>
 static void sr_launch_ring_sort(const SrBuffers& b, const SrParams& p, hipStream_t st, bool lanes_imu) {
   if (lanes_imu) {  // (never the fused kernel: its tiles wait for each other)
     const int rtiles = (b.cap + kRingTile - 1) / kRingTile;
-    hipLaunchKernelGGL((k_sr_ring_count<true, TAB>), dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
-    hipLaunchKernelGGL(k_sr_ring_scatter<true>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+    hipLaunchKernelGGL((k_sr_ring_count<true, SRC>), dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+    hipLaunchKernelGGL((k_sr_ring_scatter<true, SRC == kSrcFieldTime>), dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
   } else if (p.imu) {
-    hipLaunchKernelGGL((k_sr_ring_sort<true, TAB>), dim3(b.S), dim3(kSrThreads), 0, st, b, p);
+    hipLaunchKernelGGL((k_sr_ring_sort<true, SRC>), dim3(b.S), dim3(kSrThreads), 0, st, b, p);
   } else {
     const int rtiles = (b.cap + kRingTile - 1) / kRingTile;  // <= b.ntiles(): tilecnt rows fit
     // (a margin of 2: a sweep's tiles fit in half the co-resident slots; HDL-64E's 160k-point
     // sweeps are 79 tiles against several per CU x 256 CUs on MI355X)
-    if (kSrRingFused && b.S >= kSrRingFusedMin && 2 * rtiles <= sr_ring_fused_capacity_of<TAB>()) {
+    if (kSrRingFused && b.S >= kSrRingFusedMin && 2 * rtiles <= sr_ring_fused_capacity_of<SRC>()) {
       hipLaunchKernelGGL(k_sr_ring_prep, dim3(b.S), dim3(kPrepThreads), 0, st, b, b.R, rtiles);
-      hipLaunchKernelGGL(k_sr_ring_fused<TAB>, dim3(rtiles * b.S), dim3(kSrThreads), 0, st, b, p, rtiles);
+      hipLaunchKernelGGL(k_sr_ring_fused<SRC>, dim3(rtiles * b.S), dim3(kSrThreads), 0, st, b, p, rtiles);
     } else {
-      hipLaunchKernelGGL((k_sr_ring_count<false, TAB>), dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
-      hipLaunchKernelGGL(k_sr_ring_scatter<false>, dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+      hipLaunchKernelGGL((k_sr_ring_count<false, SRC>), dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
+      hipLaunchKernelGGL((k_sr_ring_scatter<false, SRC == kSrcFieldTime>), dim3(rtiles, b.S), dim3(kSrThreads), 0, st, b, p);
     }
   }
 }
@@ -2538,8 +2663,12 @@ void sr_launch(const SrBuffers& b, const SrParams& p, hipStream_t st, Prof* prof
     HIPCHK(hipMemsetAsync(b.err, 0, (size_t)b.S * sizeof(int), st));
   }
   mark("sr_memset");
-  if (p.ring_model == LOAM_RING_TABLE) sr_launch_ring_sort<true>(b, p, st, lanes_imu);
-  else sr_launch_ring_sort<false>(b, p, st, lanes_imu);
+  switch (ring_src_of(p.ring_model)) {
+    case kSrcTable: sr_launch_ring_sort<kSrcTable>(b, p, st, lanes_imu); break;
+    case kSrcField: sr_launch_ring_sort<kSrcField>(b, p, st, lanes_imu); break;
+    case kSrcFieldTime: sr_launch_ring_sort<kSrcFieldTime>(b, p, st, lanes_imu); break;
+    default: sr_launch_ring_sort<kSrcModel>(b, p, st, lanes_imu);
+  }
   mark("k_sr_ring_sort");
   if (sorted) HIPCHK(hipEventRecord(sorted, st));  // the ring-sorted full cloud is final here
   hipLaunchKernelGGL(k_sr_features, dim3((b.cap + kFeatSpan - 1) / kFeatSpan, b.S), dim3(kFeatTile), 0,

@@ -12,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from . import CloudIn, LOAM_OK, _check, lib
+from . import CloudIn, LOAM_OK, PointFields, _check, lib
 
 LOAM_BAG_END = 1
 
@@ -40,6 +40,7 @@ def _bag_lib():
         L.loam_bag_next.argtypes = [PP, P(BagMsg)]
         L.loam_pc2_parse.argtypes = [ctypes.c_void_p, ctypes.c_uint32, P(Pc2)]
         L.loam_pc2_cloud.argtypes = [P(Pc2), ctypes.c_void_p, ctypes.c_uint32, P(CloudIn)]
+        L.loam_pc2_point_fields.argtypes = [ctypes.c_void_p, ctypes.c_uint32, P(PointFields)]
         L.loam_imu_parse.argtypes = [ctypes.c_void_p, ctypes.c_uint32, P(ctypes.c_double), P(ctypes.c_double),
                                      P(ctypes.c_double)]
         L._bag_ready = True
@@ -112,6 +113,16 @@ def pc2_cloud_in(data, size):
     return pc.stamp, ci, (scratch if ci.data == scratch.ctypes.data else None)
 
 
+def pc2_point_fields(data, size=None):
+    """loam_pc2_point_fields: the PointFields of a serialized PointCloud2 (bytes, or an address and
+    a size): its "ring" field and its "time" / "t" field; LoamError when it has no usable ring"""
+    if size is None:
+        data, size = ctypes.create_string_buffer(data, len(data)), len(data)
+    f = PointFields()
+    _check(_bag_lib().loam_pc2_point_fields(data, size, ctypes.byref(f)))
+    return f
+
+
 def parse_imu(payload):
     """sensor_msgs/Imu -> (header stamp, quaternion x, y, z, w, linear acceleration)"""
     buf = ctypes.create_string_buffer(payload, len(payload))
@@ -122,20 +133,30 @@ def parse_imu(payload):
     return t.value, np.array(q[:]), np.array(a[:])
 
 
-def replay(path, engine, cloud_topic="/velodyne_points", imu_topic="/imu/data", max_sweeps=None):
+def replay(path, engine, cloud_topic="/velodyne_points", imu_topic="/imu/data", max_sweeps=None, fields=None):
     """Feeds a bag through the node path of one engine context: /imu/data -> loam_imu, every cloud
     -> scan registration -> odometry -> mapping on the frames odometry publishes (Q20).  Returns
     dict(odometry=[(stamp, pose6)], mapping=[(stamp, aft pose6)], sweeps=int).
     A checker engine without `takes_cloud_in` (the CPU oracle) gets the cloud decoded into an
     (n, 4) array instead; the product engine reads the message's records in place (zero-copy:
-    the scan registration's upload is the only copy of the points)."""
+    the scan registration's upload is the only copy of the points).
+    fields: None (the engine's ring model), a PointFields, or "auto" (the first cloud's own ring and
+    time fields, pc2_point_fields): set on the engine before its first sweep."""
     odo, mapped, n = [], [], 0
     zero_copy = getattr(engine, "takes_cloud_in", False)
+    if fields is not None and not isinstance(fields, str):
+        engine.set_point_fields(fields=fields)
+        fields = None
+    elif fields is not None and fields != "auto":
+        raise ValueError('fields is None, "auto" or a PointFields')
     for topic, _type, _t, data, size in Bag(path).views():
         if topic == imu_topic:
             stamp, q, a = parse_imu(ctypes.string_at(data, size))
             engine.imu(stamp, q, a)
         elif topic == cloud_topic:
+            if fields == "auto":
+                engine.set_point_fields(fields=pc2_point_fields(data, size))
+                fields = None
             if zero_copy:
                 stamp, cloud, _keep = pc2_cloud_in(data, size)
             else:

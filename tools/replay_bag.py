@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--oracle", action="store_true", help="also run the CPU oracle (test infrastructure)")
     ap.add_argument("--trajectory", default="", help="write stamp + mapping pose per published frame (CSV)")
     ap.add_argument("--elevations", default="", help="beam elevations in degrees, comma separated: a ring table")
+    ap.add_argument("--fields", action="store_true",
+                    help="ring and time from the clouds' own ring / time (or t) fields instead of the ring model")
     args = ap.parse_args()
     if args.elevations and args.oracle:
         ap.error("--oracle knows only the built-in ring models; drop it or --elevations")
@@ -49,7 +51,8 @@ def main():
     if table is not None:
         eng.set_ring_table(*table)
     t0 = time.perf_counter()
-    out = rb.replay(args.bag, eng, args.cloud_topic, args.imu_topic, args.max_sweeps or None)
+    out = rb.replay(args.bag, eng, args.cloud_topic, args.imu_topic, args.max_sweeps or None,
+                    fields="auto" if args.fields else None)
     dt = time.perf_counter() - t0
     res = {"bag": args.bag, "sweeps": out["sweeps"], "seconds": dt, "scans_per_s": out["sweeps"] / dt if dt else None,
            "odometry_frames": len(out["odometry"]), "mapping_frames": len(out["mapping"]),
